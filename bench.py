@@ -3,7 +3,10 @@
 GRCh38-scale index, SAM bit-identical to `bwa mem`.
 
 Contract (driver): `python bench.py --gpus N --steps K --warmup W`; for N > 1 it is launched by torch.distributed.run with one
-rank per GPU.  Rank 0 prints ONE JSON line.
+rank per GPU.  Rank 0 prints ONE JSON line.  Such a plain run does only what that line's headline needs: it sets up (index, batches),
+warms up, times the K steps, writes the outputs of the last ones with --dump-outputs DIR, and prints `value`, `ms_per_step`, the
+workload and its result digest.  Everything below that (parity gate, CPU baseline, roofline, end-to-end and long-read legs, variants)
+runs with --full.
 
 Workload (BASELINE.json configs[2] layout, the configuration the metric is quoted on): per GPU and step one batch of
 `--reads` (default 1 M = 500 k pairs, mates interleaved as mem_process_seqs takes them, bwamem.h:146-150) synthetic 2x150 bp
@@ -14,14 +17,14 @@ extend -> dedup) over a batch that is already resident in HBM: `value` is the RE
 host finalize; the end-to-end `bwa-amd mem` rates (FASTQ in -> SAM out) are reported beside it.  Reads shard across ranks with
 no data-path collective ("weak" scaling: every rank aligns its own `--reads`); the index reaches ranks > 0 by RCCL broadcast.
 
-Parity gate: the unmodified reference (`oracle/_ref/bwa mem`, also the CPU baseline) and the product command line
+Parity gate (--full): the unmodified reference (`oracle/_ref/bwa mem`, also the CPU baseline) and the product command line
 (`bwa-amd mem`) align the same samples with the same -K -- a single-end sample in one batch and a paired-end sample in TWELVE
 batches (four per device handle: arenas, learnt sizes and packed buffers are re-used from batch to batch) -- and their
 SAM must be byte-identical apart from @PG, otherwise the run exits non-zero.  With --gpus N > 1 (`python bench.py --gpus N` starts the N
 ranks itself) rank 0 runs the gate on device 0 as ever, then the paired-end sample and the end-to-end run once more over all N devices
 (BWAGPU_DEVICES) -- reported as parity.pe_all_devices / end_to_end_pe, not part of the exit code: that path has never met hardware.
 
-Extra objects on the JSON line:
+Extra objects on the JSON line of a --full run:
   roofline       the longest kernel's algorithmic bytes / its measured duration (HIP events on the library's stream)
   cpu_baseline   the reference on the paired-end sample (and the single-end one under "se"), on this box's host cores
   parity         result of the gate (se, pe, multibatch)
@@ -53,28 +56,38 @@ def log(*a):
     print(f"[{time.time() - _T0:7.1f}s]", *a, file=sys.stderr, flush=True)
 
 
-def build_or_load_index(genome_mbp: float, cache: str, rank: int, barrier, lib_path=None):
+def build_or_load_index(genome_mbp: float, cache: str, rank: int, barrier, lib_path=None, on_genome=None):
     """Seeded synthetic genome + reference-format index files, built on the GPU by bwagpu_index_build and cached on the box.
-    Rank 0 builds; the genome's base codes are shared with the other ranks through a memory-mapped file."""
+    Rank 0 builds; the genome's base codes are shared with the other ranks through a memory-mapped file.  on_genome(codes), when given, is
+    called as soon as the genome exists (on a first run: before the index is built), for work that needs the genome alone."""
     from bwa_amd import simdata
     total = int(genome_mbp * 1_000_000)
     prefix = os.path.join(cache, f"g{total}_s42")
     info = {}
     if rank == 0 and not (os.path.exists(prefix + ".sa") and os.path.exists(prefix + ".codes.npy")):
+        from concurrent.futures import ThreadPoolExecutor
         from bwa_amd.index import build_index
         os.makedirs(cache, exist_ok=True)
         t = time.time()
         g, lens = simdata.make_genome_large(total, n_contigs=24, seed=42, threads=4)
         t_gen = time.time() - t
+        if on_genome is not None:
+            on_genome(g)
+            on_genome = None
         t = time.time()
-        info = build_index(prefix, g, [(f"chr{i + 1}", l) for i, l in enumerate(lens)], lib_path=lib_path)
+        with ThreadPoolExecutor(max_workers=1) as ex:          # (the codes are written while the device builds the index)
+            saved = ex.submit(np.save, prefix + ".codes.npy", g)
+            info = build_index(prefix, g, [(f"chr{i + 1}", l) for i, l in enumerate(lens)], lib_path=lib_path)
+            saved.result()
         t_idx = time.time() - t
-        np.save(prefix + ".codes.npy", g)
         del g
         log(f"[bench] {genome_mbp:g} Mbp genome generated in {t_gen:.1f}s; index built on the device in {info['build_ms'] / 1e3:.2f}s "
             f"({t_idx:.1f}s with packing, D2H and file output)")
     barrier()
-    return prefix, np.load(prefix + ".codes.npy", mmap_mode="r"), info
+    g = np.load(prefix + ".codes.npy", mmap_mode="r")
+    if on_genome is not None:
+        on_genome(g)
+    return prefix, g, info
 
 
 def sam_body_digest(path: str):
@@ -266,6 +279,96 @@ def interleave(r1: np.ndarray, r2: np.ndarray) -> np.ndarray:
     return out
 
 
+def load_index(args, prefix, dist, dev_id, lib_path, barrier):
+    """The index resident in this GPU's HBM (no CPU fallback: raises without a GPU); with ranks, rank 0 loads + uploads and the others receive it
+    over RCCL/xGMI.  Returns (handle, broadcast seconds or None)."""
+    from bwa_amd.api import BwaGpu
+    bcast_s = None
+    if dist is not None:
+        from bwa_amd import dist as bdist
+        t_b = time.perf_counter()
+        gpu = bdist.broadcast_index(prefix, device=dev_id, src=0, lib_path=lib_path)
+        barrier()
+        bcast_s = time.perf_counter() - t_b
+        if dist.get_rank() == 0:
+            log(f"[bench] index loaded on rank 0 and broadcast to {dist.get_world_size()} ranks over RCCL in {bcast_s:.2f}s")
+    else:
+        gpu = BwaGpu(prefix, device=dev_id, lib_path=lib_path)
+    if args.dense_sa:
+        gpu.densify_sa(args.dense_sa)
+    gpu.set_taps(False)
+    return gpu, bcast_s
+
+
+def solo_passes(gpu, opt):
+    """Untimed instrumented solo passes of batch 0 (--full): algorithmic work counters (roofline numerator) and solo kernel times.
+    Returns (work, work_product, stage_ms)."""
+    # (the algorithm's own work: with the seeding kernel's iteration budget off no read is given up half-way and seeded again by the task kernels;
+    # the product's counters, rework included, are reported beside it)
+    gpu.set_option("share", 100)      # (the solo passes: every kernel with the whole chip, whatever the handle count makes the default -- bwagpu_config.h)
+    gpu.set_stats(True)
+    gpu.set_option("seed_budget", 0)
+    gpu.run(opt)
+    work = gpu.stats()
+    gpu.set_option("seed_budget", -1)
+    gpu.run(opt)
+    work_product = gpu.stats()
+    try:        # k_seed's stats instance counts the lane steps that fetch an interval-stack entry back from its HBM spill area (bwagpu_debug_prof[10])
+        import ctypes as C_
+        prof_ = (C_.c_ulonglong * 16)()
+        gpu.L.bwagpu_debug_prof.argtypes = [C_.c_void_p, C_.c_void_p]
+        if gpu.L.bwagpu_debug_prof(gpu.h, prof_) == 0:
+            work_product["n_stack_spill"] = int(prof_[10])
+    except Exception:
+        pass
+    gpu.set_stats(False)
+    gpu.run(opt)
+    solo = gpu.stats()
+    stage_keys = ("ms_seed", "ms_publish", "ms_sa", "ms_chain", "ms_seedsw", "ms_extend", "ms_dedup", "ms_total")
+    stage_ms = {k: solo[k] for k in stage_keys}
+    gpu.set_option("share", -1)
+    return work, work_product, stage_ms
+
+
+DUMP_BYTES = 60 << 20        # --dump-outputs writes at most this much in all
+DUMP_COUNT_READS = 1 << 20   # region counts of up to this many reads per batch (all of them at the default size)
+DUMP_REG_READS = 1 << 14     # reads per batch whose regions are written in full
+DUMP_SEED = 20261016
+
+
+def dump_outputs(path, results):
+    """--dump-outputs: what the timed path left for each batch, as float arrays (every value exact).
+      batch<i>_counts.npy  float32 [n]      regions per read (mem_align1_core's n), for every read, or for a seeded sample of DUMP_COUNT_READS reads when the
+                                            batch is larger
+      batch<i>_regs.npy    float64 [m, 21]  the mem_alnreg_t records of a seeded sample of DUMP_REG_READS reads, in the order the library returns them; columns:
+                                            read, then ALNREG_DTYPE's fields in order with the 64-bit hash split into its low and high 32 bits
+    results: [(i, counts, regs)].  The samples depend on the seed and the batch size alone, so runs with the same arguments write the same reads' records."""
+    from bwa_amd.structs import ALNREG_DTYPE
+    os.makedirs(path, exist_ok=True)
+    fields = [f for f in ALNREG_DTYPE.names if f != "hash"]
+    n_col = 1 + len(fields) + 2
+    per_batch = DUMP_BYTES // max(1, len(results))
+    written = 0
+    for i, counts, regs in results:
+        n = counts.shape[0]
+        rng = np.random.default_rng(DUMP_SEED)
+        pick_c = np.arange(n) if n <= DUMP_COUNT_READS else np.sort(rng.choice(n, DUMP_COUNT_READS, replace=False))
+        np.save(os.path.join(path, f"batch{i}_counts.npy"), counts[pick_c].astype(np.float32))
+        pick = np.sort(rng.choice(n, min(n, DUMP_REG_READS), replace=False))
+        start = np.zeros(n + 1, dtype=np.int64)
+        np.cumsum(counts, out=start[1:])
+        cnt = counts[pick].astype(np.int64)
+        first = np.repeat(start[pick], cnt)
+        rows = first + (np.arange(int(cnt.sum())) - np.repeat(np.cumsum(cnt) - cnt, cnt))      # each picked read's own records, in order
+        rows = rows[:max(0, (per_batch - 4 * pick_c.size) // (8 * n_col))]                      # (the byte budget: ~60 % of it at the default sizes)
+        sub = regs[rows]
+        cols = [np.repeat(pick, cnt)[:rows.size].astype(np.float64)] + [sub[f].astype(np.float64) for f in fields] + \
+               [(sub["hash"] & np.uint64(0xffffffff)).astype(np.float64), (sub["hash"] >> np.uint64(32)).astype(np.float64)]
+        np.save(os.path.join(path, f"batch{i}_regs.npy"), np.stack(cols, axis=1) if rows.size else np.zeros((0, n_col)))
+        written += 4 * pick_c.size + 8 * n_col * rows.size
+    return written
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -299,7 +402,14 @@ def main():
     ap.add_argument("--variants-timeout", type=float, default=70.0, help="seconds for the short-read child process (the long-read one gets 0.8 of it)")
     ap.add_argument("--wall-budget", type=float, default=330.0, help="seconds since start after which no variants child may still run: the two legs share what is left "
                     "when the line's own measurements are done (they end first; a leg that gets less than 20 s is skipped)")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline: solo stage times and roofline, CIGAR stage, counter passes, parity gates and "
+                    "CPU baseline, end-to-end and long-read legs, variants (the --no-* options above apply to this mode).  Without it the run sets up, warms up, "
+                    "times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what they computed (every timed handle's last batch: region "
+                    "counts and a fixed sample of the regions) as DIR/<name>.npy in float32 / float64")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     # --gpus N > 1 means N ranks, one per GPU.  Launched bare (`python bench.py --gpus N`, no WORLD_SIZE in the environment) the script
     # re-executes itself under torch.distributed.run with N ranks on this node; launched by the driver's own torch.distributed.run line it finds
@@ -343,81 +453,50 @@ def main():
             torch.cuda.synchronize()
 
     from bwa_amd import simdata
-    from bwa_amd.api import BwaGpu
     from bwa_amd.structs import default_opt
 
     t_all = time.time()
-    prefix, g, idx_info = build_or_load_index(args.genome_mbp, args.cache, rank, barrier, lib_path)
-    bcast_s = None
-    if dist is not None:                     # rank 0 loads + uploads, the others receive the index over RCCL/xGMI
-        from bwa_amd import dist as bdist
-        t_b = time.perf_counter()
-        gpu = bdist.broadcast_index(prefix, device=dev_id, src=0, lib_path=lib_path)
-        barrier()
-        bcast_s = time.perf_counter() - t_b
-        if rank == 0:
-            log(f"[bench] index loaded on rank 0 and broadcast to {world} ranks over RCCL in {bcast_s:.2f}s")
-    else:
-        gpu = BwaGpu(prefix, device=dev_id, lib_path=lib_path)   # index resident in this GPU's HBM (no CPU fallback: raises without a GPU)
-    if args.dense_sa:
-        gpu.densify_sa(args.dense_sa)
-    gpu.set_taps(False)
-    opt = default_opt()
     pe = args.layout == "pe"
+    S = max(1, args.streams)
+
+    def make_batch(codes, seed):
+        if pe:
+            r1, r2 = simdata.make_reads_pe(codes, args.reads // 2, length=args.read_len, seed=seed)
+            return interleave(r1, r2)
+        return simdata.make_reads_se(codes, args.reads, length=args.read_len, seed=seed)
+
+    # S batches in flight per GPU (below); their reads need the genome alone and are drawn on host threads, each batch from its own seed, while
+    # the index is built and loaded
+    from concurrent.futures import ThreadPoolExecutor
+    with ThreadPoolExecutor(max_workers=S) as pool_:
+        drawn = []
+        prefix, g, idx_info = build_or_load_index(args.genome_mbp, args.cache, rank, barrier, lib_path,
+                                                  on_genome=lambda codes: drawn.extend(pool_.submit(make_batch, codes, 1000 + rank * 64 + si) for si in range(S)))   # this rank's shard(s)
+        gpu, bcast_s = load_index(args, prefix, dist, dev_id, lib_path, barrier)
+        log("[bench] index loaded")
+        batches = [f_.result() for f_ in drawn]
+    opt = default_opt()
     if pe:
         opt.flag |= 0x2                      # MEM_F_PE (bwamem.h:43): mates interleaved; the hot path aligns them independently (bwamem.c:1209-1213)
 
-    def make_batch(seed):
-        if pe:
-            r1, r2 = simdata.make_reads_pe(g, args.reads // 2, length=args.read_len, seed=seed)
-            return interleave(r1, r2)
-        return simdata.make_reads_se(g, args.reads, length=args.read_len, seed=seed)
-
-    # S batches in flight per GPU: S handles share the resident index (bwagpu_clone), each with its own stream and arenas and
-    # driven by its own host thread, so the latency-bound tails of one batch overlap the throughput-bound kernels of another.
+    # S handles share the resident index (bwagpu_clone), each with its own stream and arenas and driven by its own host thread, so the
+    # latency-bound tails of one batch overlap the throughput-bound kernels of another.
     import threading
-    S = max(1, args.streams)
     handles = [gpu] + [gpu.clone() for _ in range(S - 1)]
-    batches = []
-    for si, hdl in enumerate(handles):
-        rd = make_batch(1000 + rank * 64 + si)            # this rank's shard(s)
+    for hdl, rd in zip(handles, batches):
         hdl.set_taps(False)
         hdl.upload(np.ascontiguousarray(rd.reshape(-1)), np.arange(0, rd.shape[0] + 1, dtype=np.int64) * args.read_len)   # resident in HBM
-        batches.append(rd)
     n_batch = batches[0].shape[0]
     variant_files = []
-    if world == 1 and ((args.variants.strip() and not args.no_cpu_baseline) or not args.no_pmc):       # the variants leg and the counter passes (child processes at the end) run on these very batches
+    if args.full and world == 1 and ((args.variants.strip() and not args.no_cpu_baseline) or not args.no_pmc):       # the variants leg and the counter passes (child processes at the end) run on these very batches
         for si, rd in enumerate(batches):
             if si == 0 or (args.variants.strip() and not args.no_cpu_baseline):
                 variant_files.append(os.path.join(os.path.dirname(prefix), f"variant_batch{si}.npy"))
                 np.save(variant_files[-1], rd)
 
     log(f"[bench] index resident, {S} batches of {n_batch} reads uploaded")
-    # one untimed instrumented solo pass: algorithmic work counters of batch 0 (roofline numerator) and solo kernel times
-    # (the algorithm's own work: with the seeding kernel's iteration budget off no read is given up half-way and seeded again by the task kernels;
-    # the product's counters, rework included, are reported beside it)
-    gpu.set_option("share", 100)      # (the solo passes: every kernel with the whole chip, whatever the handle count makes the default -- bwagpu_config.h)
-    gpu.set_stats(True)
-    gpu.set_option("seed_budget", 0)
-    gpu.run(opt)
-    work = gpu.stats()
-    gpu.set_option("seed_budget", -1)
-    gpu.run(opt)
-    work_product = gpu.stats()
-    try:        # k_seed's stats instance counts the lane steps that fetch an interval-stack entry back from its HBM spill area (bwagpu_debug_prof[10])
-        import ctypes as C_
-        prof_ = (C_.c_ulonglong * 16)()
-        gpu.L.bwagpu_debug_prof.argtypes = [C_.c_void_p, C_.c_void_p]
-        if gpu.L.bwagpu_debug_prof(gpu.h, prof_) == 0:
-            work_product["n_stack_spill"] = int(prof_[10])
-    except Exception:
-        pass
-    gpu.set_stats(False)
-    gpu.run(opt)
-    solo = gpu.stats()
-    stage_keys = ("ms_seed", "ms_publish", "ms_sa", "ms_chain", "ms_seedsw", "ms_extend", "ms_dedup", "ms_total")
-    stage_ms = {k: solo[k] for k in stage_keys}
-    gpu.set_option("share", -1)
+    if args.full:
+        work, work_product, stage_ms = solo_passes(gpu, opt)
 
     def worker(hdl, n_pass):
         for _ in range(n_pass):
@@ -451,23 +530,28 @@ def main():
             sys.exit(f"bench.py: the collective reports {ranks_seen} ranks (world size {dist.get_world_size()}), expected {world}")
     counts, regs = gpu.download()
     digest = hashlib.sha256(counts.tobytes() + regs.tobytes()).hexdigest()[:16]
+    if args.dump_outputs and rank == 0:       # (before anything else runs on the handles: each one's last timed batch)
+        res_ = [(0, counts, regs)] + [(i, *handles[i].download()) for i in range(1, S) if share[i]]
+        log(f"[bench] outputs of the timed steps: {dump_outputs(args.dump_outputs, res_) / 1e6:.1f} MB in {args.dump_outputs}")
+        del res_
     cigar_stage = None
-    try:       # the CIGAR stage of the same batch, alone on the chip (bwagpu_batch_cigars with the command line's XA-aware filter): kernels' time, DP cells
-        import ctypes as C_
-        gpu.L.bwagpu_set_cigar_filter.argtypes = [C_.c_void_p, C_.c_int]
-        gpu.L.bwagpu_set_cigar_filter(gpu.h, 1)
-        gpu.set_stats(True); cg = gpu.cigars(opt); st_c = gpu.stats(); gpu.set_stats(False)
-        ms_c = []
-        for _ in range(2):
-            cg = gpu.cigars(opt); ms_c.append(gpu.stats()["ms_cigar_kernels"])
-        gpu.L.bwagpu_set_cigar_filter(gpu.h, 0)
-        cigar_stage = {"kernels_ms": round(min(ms_c), 3), "regions": int(regs.shape[0]), "served": int((cg["n_cigar"] > 0).sum()), "filtered": int(((cg["n_cigar"] < 0) & (cg["score"] == 1)).sum()),
-                       "left_to_host": int(((cg["n_cigar"] < 0) & (cg["score"] != 1)).sum()), "dp_fills": int(st_c["n_cig_dp"]), "cigar_cells_per_read": round(st_c["n_cig_cells"] / max(1, n_batch), 1),
-                       "gcups": round(st_c["n_cig_cells"] / (min(ms_c) * 1e-3) / 1e9, 1) if min(ms_c) > 0 else None,
-                       "what": "bwagpu_batch_cigars on timed batch 0 alone (k_cigar's two tiers + k_cigar_long, NM/MD included), with `bwa-amd mem`'s filter: regions that can appear neither as a record nor in an XA tag are skipped"}
-        del cg
-    except Exception as e:
-        cigar_stage = {"error": repr(e)}
+    if args.full:
+        try:       # the CIGAR stage of the same batch, alone on the chip (bwagpu_batch_cigars with the command line's XA-aware filter): kernels' time, DP cells
+            import ctypes as C_
+            gpu.L.bwagpu_set_cigar_filter.argtypes = [C_.c_void_p, C_.c_int]
+            gpu.L.bwagpu_set_cigar_filter(gpu.h, 1)
+            gpu.set_stats(True); cg = gpu.cigars(opt); st_c = gpu.stats(); gpu.set_stats(False)
+            ms_c = []
+            for _ in range(2):
+                cg = gpu.cigars(opt); ms_c.append(gpu.stats()["ms_cigar_kernels"])
+            gpu.L.bwagpu_set_cigar_filter(gpu.h, 0)
+            cigar_stage = {"kernels_ms": round(min(ms_c), 3), "regions": int(regs.shape[0]), "served": int((cg["n_cigar"] > 0).sum()), "filtered": int(((cg["n_cigar"] < 0) & (cg["score"] == 1)).sum()),
+                           "left_to_host": int(((cg["n_cigar"] < 0) & (cg["score"] != 1)).sum()), "dp_fills": int(st_c["n_cig_dp"]), "cigar_cells_per_read": round(st_c["n_cig_cells"] / max(1, n_batch), 1),
+                           "gcups": round(st_c["n_cig_cells"] / (min(ms_c) * 1e-3) / 1e9, 1) if min(ms_c) > 0 else None,
+                           "what": "bwagpu_batch_cigars on timed batch 0 alone (k_cigar's two tiers + k_cigar_long, NM/MD included), with `bwa-amd mem`'s filter: regions that can appear neither as a record nor in an XA tag are skipped"}
+            del cg
+        except Exception as e:
+            cigar_stage = {"error": repr(e)}
     for hdl in handles[1:]:
         hdl.close()
     if dist is not None:
@@ -480,12 +564,36 @@ def main():
             sys.exit(0)
 
     rc_exit = 0
-    log(f"[bench] hot path timed: {dt / args.steps * 1e3:.1f} ms/step; solo stages {stage_ms}")
+    log(f"[bench] hot path timed: {dt / args.steps * 1e3:.1f} ms/step" + (f"; solo stages {stage_ms}" if args.full else ""))
     total_reads = n_batch * world * args.steps
     value = total_reads / dt / 1e6
-    nr = float(work["n_reads"])
+    layout = f"{n_batch // 2} pairs of 2x{args.read_len} bp (mates interleaved)" if pe else f"{n_batch} single-end {args.read_len} bp reads"
     occ32 = os.environ.get("BWAGPU_OCC32", "1") != "0"
     blk_bytes = 32.0 if occ32 else 64.0
+    head = {
+        "metric": "Mreads/s (whole job) 2x150 bp vs GRCh38-scale index; SAM bit-identical to bwa mem (gate: `parity`).  `value` = the hot path (mem_align1_core of every read) on batches resident in HBM, "
+                  "as the bench contract times it; the SAM-producing FASTQ->SAM rate of the same build is `end_to_end_pe.value` (also in `summary`)",
+        "value": round(value, 4), "unit": "Mreads/s", "n_gpus": ranks_seen, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(dt / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "int32/u64 (integer DP + FM-index ranks)", "data": "synthetic", "full": args.full,
+        "config": {"workload": f"{layout} per GPU per step vs seeded synthetic {args.genome_mbp:g} Mbp genome (GRCh38 stand-in, seq_len {2 * int(args.genome_mbp * 1e6):.3g}; BASELINE configs[{2 if pe else 1}] layout)",
+                   "reads_per_gpu": n_batch, "read_len": args.read_len, "layout": args.layout, "genome_mbp": args.genome_mbp, "sa_intv": args.dense_sa or 32,
+                   "occ_block_bytes": int(blk_bytes),
+                   "sharding": f"reads x{world}, no collective", "batches_in_flight": S, "result_sha256_16": digest,
+                   "timed": "kernels of the hot path on batches resident in HBM (no PCIe, no host finalize); see end_to_end_* for FASTQ->SAM"},
+    }
+    extra = {}
+    if per_rank is not None:
+        extra["ranks"] = {"n": ranks_seen, "backend": backend + (" (RCCL)" if on_gpu else ""), "per_rank_Mreads_s": per_rank,
+                          "what": "n = all-reduce of ones over the collective library; every rank's own hot-path rate (its reads x steps / its own time); `value` = all ranks' reads / the slowest rank's time"}
+    if bcast_s is not None:
+        extra["index_broadcast"] = {"ranks": world, "seconds": round(bcast_s, 3), "what": "rank 0 loads the index files and uploads; RCCL broadcast of .bwt/.sa/.pac buffers over xGMI; every rank then builds its 32-byte blocks and prefix tables"}
+    if not args.full:
+        # the headline alone (parity gates, baselines, roofline and the other legs are --full's): the contract's fields, the workload and its result digest
+        gpu.close()
+        print(json.dumps(dict(head, **extra)), flush=True)
+        sys.exit(0)
+    nr = float(work["n_reads"])
     # algorithmic bytes per launch: one index block per Occ lookup / LF step (64 bytes in the reference's layout; the
     # device's default layout answers the same query from a 32-byte block), 16 bytes per prefix-table entry, 8 bytes per SA sample, the
     # read bases; chaining: the slot records it reads (20 B) and the 160-byte B-tree nodes and 64-byte chain records it touches (counted
@@ -539,7 +647,6 @@ def main():
                                ", taken " + str(pj.get("_meta", {}).get("date", "in an earlier run of the same workload")) + ")")
         except Exception:
             traffic = None
-    layout = f"{n_batch // 2} pairs of 2x{args.read_len} bp (mates interleaved)" if pe else f"{n_batch} single-end {args.read_len} bp reads"
     # the chip's measured ceiling for lane-private dependent random reads (tools/randbw4.hip, profiles/r05_randbw4.md): the memory pipeline charges
     # 19 ps per DISTINCT block a lane asks for -- 52.5e9 requests/s -- whatever the request's size (16 or 32 bytes) or the number of load instructions.
     # (Rounds 2-4 quoted 48.3 / 37.8 / 23.0e9 by request size: that benchmark's own 64-bit modulo, not the memory system.)
@@ -547,17 +654,7 @@ def main():
     n_blk, n_tab = work["n_occ_blocks"], work["n_tab_lookups"]
     spill_per_read = round(work_product["n_stack_spill"] / nr, 1) if work_product.get("n_stack_spill") is not None else None     # interval-stack entries the lanes fetched back from HBM
     seed_s = stage_ms["ms_seed"] * 1e-3
-    out = {
-        "metric": "Mreads/s (whole job) 2x150 bp vs GRCh38-scale index; SAM bit-identical to bwa mem (gate: `parity`).  `value` = the hot path (mem_align1_core of every read) on batches resident in HBM, "
-                  "as the bench contract times it; the SAM-producing FASTQ->SAM rate of the same build is `end_to_end_pe.value` (also in `summary`)",
-        "value": round(value, 4), "unit": "Mreads/s", "n_gpus": ranks_seen, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": round(dt / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "int32/u64 (integer DP + FM-index ranks)", "data": "synthetic",
-        "config": {"workload": f"{layout} per GPU per step vs seeded synthetic {args.genome_mbp:g} Mbp genome (GRCh38 stand-in, seq_len {2 * int(args.genome_mbp * 1e6):.3g}; BASELINE configs[{2 if pe else 1}] layout)",
-                   "reads_per_gpu": n_batch, "read_len": args.read_len, "layout": args.layout, "genome_mbp": args.genome_mbp, "sa_intv": args.dense_sa or 32,
-                   "occ_block_bytes": int(blk_bytes),
-                   "sharding": f"reads x{world}, no collective", "batches_in_flight": S, "result_sha256_16": digest,
-                   "timed": "kernels of the hot path on batches resident in HBM (no PCIe, no host finalize); see end_to_end_* for FASTQ->SAM"},
+    out = dict(head, **{
         "roofline": {"bound": "hbm", "kernel": roof_k + (" (+ k_seed3: the seeding stage)" if roof_k == "k_seed" else ""), "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                      "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": traffic, "traffic_detail": traffic_detail, "traffic_source": traffic_src,
                      "alg_bytes_per_launch": alg[roof_k], "kernel_ms": round(dur[roof_k], 3),
@@ -587,12 +684,7 @@ def main():
                           "ext_fast": round(work["n_ext_fast"] / nr, 2), "regs": round(work["n_regs"] / nr, 3)},
         "index_build": {"device_s": round(idx_info.get("build_ms", 0) / 1e3, 3) if idx_info else None,
                         "what": "bwagpu_index_build: suffix sort of forward+reverse text in HBM, BWT/Occ/SA in the reference's layout (byte-identical to bwa index)"},
-    }
-    if per_rank is not None:
-        out["ranks"] = {"n": ranks_seen, "backend": backend + (" (RCCL)" if on_gpu else ""), "per_rank_Mreads_s": per_rank,
-                        "what": "n = all-reduce of ones over the collective library; every rank's own hot-path rate (its reads x steps / its own time); `value` = all ranks' reads / the slowest rank's time"}
-    if bcast_s is not None:
-        out["index_broadcast"] = {"ranks": world, "seconds": round(bcast_s, 3), "what": "rank 0 loads the index files and uploads; RCCL broadcast of .bwt/.sa/.pac buffers over xGMI; every rank then builds its 32-byte blocks and prefix tables"}
+    }, **extra)
     gpu.close()
     devices = list(range(world))              # the command-line product splits every batch over these (BWAGPU_DEVICES)
     if not args.no_cpu_baseline:

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Profiles of one round on the GPU box (run through gpurun): kernel trace + stats, then FETCH_SIZE and WRITE_SIZE in passes of
-# their own (the TCC block cannot count both at once, MI355X_MICROARCH.md), all on `bench.py --steps 1 --warmup 0 --streams 1`
+# their own (the TCC block cannot count both at once, MI355X_MICROARCH.md), all on `bench.py --full --steps 1 --warmup 0 --streams 1`
 # (default workload: 500 k pairs of 2x150 bp vs the 3.1 Gbp stand-in).  Results land under gpurun_out/<tag>/; copy what is to be
 # kept into profiles/.  Kernel variants are chosen through the environment as everywhere else, e.g.
 #   BWAGPU_SEED_MRG=2 tools/profile_round.sh r04_mrg2
@@ -8,7 +8,7 @@ tag=${1:-r03}
 cd /tmp && export TMPDIR=/tmp
 cd $GRAFT_REPO_ROOT
 out=gpurun_out/$tag; mkdir -p $out
-B="python bench.py --steps 1 --warmup 0 --streams 1 --no-cpu-baseline --no-e2e --no-longread --no-pmc"
+B="python bench.py --full --steps 1 --warmup 0 --streams 1 --no-cpu-baseline --no-e2e --no-longread --no-pmc"
 rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -o t -- $B > $out/trace.log 2>&1
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $out/fetch -o f -- $B > $out/fetch.log 2>&1
 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $out/write -o w -- $B > $out/write.log 2>&1

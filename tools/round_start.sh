@@ -17,7 +17,7 @@ out=gpurun_out/$tag; mkdir -p $out
 if [ -e tests/_data/quick/expected.txt ]; then bash tools/quick_gpu_check.sh > $out/quick.log 2>&1; bash tools/quick_gpu_variants.sh >> $out/quick.log 2>&1; grep -c OK $out/quick.log; grep MISMATCH $out/quick.log; fi
 timeout 900 python -m pytest tests -m gpu -x -q > $out/pytest_gpu.log 2>&1 || { tail -30 $out/pytest_gpu.log; echo "GPU SUITE FAILED"; exit 1; }
 tail -3 $out/pytest_gpu.log
-timeout 800 python bench.py > $out/bench.json 2> $out/bench.log; echo "bench rc $?"; tail -c 800 $out/bench.json; echo
+timeout 800 python bench.py --full > $out/bench.json 2> $out/bench.log; echo "bench rc $?"; tail -c 800 $out/bench.json; echo
 C=/tmp/bwa_amd_bench
 P=$(ls $C/*.bwt 2>/dev/null | head -1); P=${P%.bwt}
 if [ -n "$P" ] && [ $# -gt 0 ]; then
