@@ -24,7 +24,8 @@ def build(force: bool = False, verbose: bool = True) -> str:
     # two translation units (the index builder pulls in rocPRIM's sort templates and rarely changes): objects are rebuilt
     # only when one of their own sources is newer
     objs = []
-    for tu, deps in (("bwagpu.hip", [s for s in srcs if not s.endswith("bwagpu_index.hip")]), ("bwagpu_index.hip", [os.path.join(CSRC, "bwagpu_index.hip"), srcs[-1]])):
+    index_srcs = [os.path.join(CSRC, f) for f in ("bwagpu_index.hip", "dev_fasta.h")] + [srcs[-1]]
+    for tu, deps in (("bwagpu.hip", [s for s in srcs if s not in index_srcs[:2]]), ("bwagpu_index.hip", index_srcs)):
         obj = os.path.join(CSRC, tu.replace(".hip", ".o"))
         if force or not os.path.exists(obj) or any(os.path.getmtime(obj) < os.path.getmtime(d) for d in deps):
             cmd = [HIPCC] + [f for f in FLAGS if f != "-shared"] + ["-c", os.path.join(CSRC, tu), "-o", obj]
@@ -56,7 +57,7 @@ def build_host(force: bool = False, verbose: bool = True):
             print(" ".join(cmd), flush=True)
         subprocess.run(cmd, check=True)
     if force or not os.path.exists(CLI) or os.path.getmtime(CLI) < max(newest, os.path.getmtime(OUT)):
-        cmd = ["g++"] + HOST_FLAGS + lib_cpp + [os.path.join(HOST, "main_mem.cpp"), "-o", CLI, "-L" + CSRC, "-lbwagpu",
+        cmd = ["g++"] + HOST_FLAGS + lib_cpp + [os.path.join(HOST, "main_mem.cpp"), os.path.join(HOST, "main_index.cpp"), "-o", CLI, "-L" + CSRC, "-lbwagpu",
                                                "-Wl,-rpath,$ORIGIN/csrc", "-Wl,-rpath,/opt/rocm/lib", "-lz", "-lpthread"]
         if verbose:
             print(" ".join(cmd), flush=True)

@@ -39,6 +39,8 @@ typedef unsigned char u8;
 #define IDX_KEY_BASES 29          // bases of a first-pass sort key (58 bits) + 6 bits of valid length
 #define IDX_RANK_BITS 34          // rows < 2^34: l_pac up to 8.5 Gbp
 
+#include "dev_fasta.h"            // FASTA -> .pac / holes (bwagpu_fasta_*)
+
 namespace {
 
 struct Buf {
@@ -571,5 +573,270 @@ done:
 	if (ev0) (void)hipEventDestroy(ev0);
 	if (ev1) (void)hipEventDestroy(ev1);
 	(void)hipStreamDestroy(bl.st);
+	return rc;
+}
+
+// ---- FASTA -> .pac / .ann / .amb (bns_fasta2bntseq, bntseq.c:280-333) ----------------------------------------------------------
+// The device walks the bytes (dev_fasta.h); the host strips the bytes before the first record, parses the header lines whose
+// positions the device reports, keeps the carry between chunks, and gathers the .pac bytes and the hole list.
+struct bwagpu_fasta_parser_s {
+	struct Contig { std::string name, anno; u64 offset; };
+	hipStream_t st = nullptr;
+	hipEvent_t ev0 = nullptr, ev1 = nullptr;
+	size_t chunk = 0;
+	u8 *stage = nullptr; size_t n_stage = 0;     // page-locked: chunk + 1 bytes (a held-back '\r' and a full chunk)
+	u64 stage_pos = 0;                           // stream offset of stage[0]
+	bool started = false;                        // the first '>' has been seen
+	u64 skipped = 0;                             // bytes before it
+	FaSum carry;
+	bool ls = true;                              // the next byte starts a line
+	bool in_hdr = false; std::string hdr;        // a header line still open at the end of the last chunk, its text so far
+	std::vector<Contig> contigs;
+	std::vector<u64> hole_off, hole_end; std::vector<char> hole_chr;
+	u8 *pac = nullptr; size_t pac_cap = 0;
+	Buf d_buf, d_tsum, d_tscan, d_codes, d_pac, d_hoff, d_hchr, d_hend, d_hpos, d_hdoff, d_err, d_jump, d_tmp;
+	std::vector<u8> h_pac, h_hchr; std::vector<u64> h_hoff, h_hend, h_hpos, h_hdoff;
+	float parse_ms = 0;
+	int rc = 0; std::string err;
+
+	~bwagpu_fasta_parser_s()
+	{
+		if (stage) (void)hipHostFree(stage);
+		free(pac);
+		if (ev0) (void)hipEventDestroy(ev0);
+		if (ev1) (void)hipEventDestroy(ev1);
+		if (st) (void)hipStreamDestroy(st);
+	}
+	int fail(int code, const std::string &msg) { if (!rc) { rc = code; err = msg; } return rc; }
+	int hip(const char *what, hipError_t e) { return e == hipSuccess ? 0 : fail(BWAGPU_EHIP, std::string(what) + ": " + hipGetErrorString(e)); }
+	int scan(FaSum *in, FaSum *out, u64 m)
+	{
+		size_t bytes = 0;
+		hipError_t e = rocprim::inclusive_scan(nullptr, bytes, in, out, (size_t)m, FaCombine(), st);
+		if (e != hipSuccess) return hip("inclusive_scan(size)", e);
+		if (d_tmp.ensure(bytes)) return fail(BWAGPU_ENOMEM, "hipMalloc failed (scan scratch)");
+		return hip("inclusive_scan", rocprim::inclusive_scan(d_tmp.p, bytes, in, out, (size_t)m, FaCombine(), st));
+	}
+	static bool space(u8 c) { return c == ' ' || c == '\t' || c == '\n' || c == '\v' || c == '\f' || c == '\r'; }
+	// a complete header line (the text after '>', without the '\n'): name up to the first white space; the rest of the line is the
+	// comment unless that delimiter ended the line (kseq.h:195-196, ks_getuntil2's '\r' rule); strdup stops at a NUL (bntseq.c:241-242)
+	void finish_header(Contig &c, const std::string &t)
+	{
+		size_t i = 0;
+		while (i < t.size() && !space((u8)t[i])) ++i;
+		c.name = std::string(t.c_str(), strnlen(t.c_str(), i));
+		std::string com = i < t.size() ? t.substr(i + 1) : std::string();
+		if (com.size() > 1 && com.back() == '\r') com.pop_back();
+		c.anno = com.empty() ? std::string("(null)") : std::string(com.c_str());
+	}
+	int grow_pac(u64 bytes)
+	{
+		if (bytes <= pac_cap) return 0;
+		size_t want = pac_cap ? pac_cap : ((size_t)1 << 20);
+		while (want < bytes) want <<= 1;
+		u8 *np = (u8*)realloc(pac, want);
+		if (!np) return fail(BWAGPU_ENOMEM, "malloc failed (.pac)");
+		memset(np + pac_cap, 0, want - pac_cap);
+		pac = np; pac_cap = want;
+		return 0;
+	}
+	// parse stage[0..n) (the whole stage when eof, else all but a trailing '\r')
+	int process(bool eof)
+	{
+		size_t n = n_stage;
+		if (!eof && n && stage[n - 1] == '\r') --n;
+		if (n == 0) return 0;
+		const u64 T = (n + FA_TILE - 1) / FA_TILE;
+		if (d_buf.ensure(n) || d_tsum.ensure(T * sizeof(FaSum)) || d_tscan.ensure(T * sizeof(FaSum)) || d_err.ensure(8))
+			return fail(BWAGPU_ENOMEM, "hipMalloc failed (FASTA chunk)");
+		if (hip("copy chunk", hipMemcpyAsync(d_buf.p, stage, n, hipMemcpyHostToDevice, st)) || hip("memset", hipMemsetAsync(d_err.p, 0, 8, st))) return rc;
+		(void)hipEventRecord(ev0, st);
+		FaOut o; memset(&o, 0, sizeof o);
+		o.err = d_err.as<u64>(); o.jump = d_jump.as<u64>();
+		const u8 *b = d_buf.as<u8>();
+		FaSum *ts = d_tsum.as<FaSum>(), *tc = d_tscan.as<FaSum>();
+		hipLaunchKernelGGL(k_fa_pass<1>, dim3((unsigned)T), dim3(FA_BLOCK), 0, st, b, (u64)n, (int)eof, (int)ls, carry, tc, ts, o);
+		if (scan(ts, tc, T)) return rc;
+		hipLaunchKernelGGL(k_fa_pass<2>, dim3((unsigned)T), dim3(FA_BLOCK), 0, st, b, (u64)n, (int)eof, (int)ls, carry, tc, ts, o);
+		if (scan(ts, tc, T)) return rc;
+		hipLaunchKernelGGL(k_fa_pass<3>, dim3((unsigned)T), dim3(FA_BLOCK), 0, st, b, (u64)n, (int)eof, (int)ls, carry, tc, ts, o);
+		if (scan(ts, tc, T)) return rc;
+		FaSum last;
+		if (hip("read back chunk totals", hipMemcpyAsync(&last, tc + (T - 1), sizeof last, hipMemcpyDeviceToHost, st)) || hip("sync", hipStreamSynchronize(st))) return rc;
+		const FaSum tot = FaCombine()(carry, last);
+		const u64 nk = tot.nk - carry.nk, ns = tot.ns - carry.ns, ne = tot.ne - carry.ne, nh = tot.nh - carry.nh;
+		const u64 l0 = carry.nk, n_pac = nk ? ((l0 + nk - 1) >> 2) - (l0 >> 2) + 1 : 0;
+		if (d_codes.ensure(nk + 1) || d_pac.ensure(n_pac + 1) || d_hoff.ensure(ns * 8 + 8) || d_hchr.ensure(ns + 1) || d_hend.ensure(ne * 8 + 8) ||
+			d_hpos.ensure(nh * 8 + 8) || d_hdoff.ensure(nh * 8 + 8)) return fail(BWAGPU_ENOMEM, "hipMalloc failed (FASTA outputs)");
+		o.codes = d_codes.as<u8>(); o.hole_off = d_hoff.as<u64>(); o.hole_chr = d_hchr.as<u8>(); o.hole_end = d_hend.as<u64>();
+		o.hdr_pos = d_hpos.as<u64>(); o.hdr_off = d_hdoff.as<u64>();
+		hipLaunchKernelGGL(k_fa_pass<4>, dim3((unsigned)T), dim3(FA_BLOCK), 0, st, b, (u64)n, (int)eof, (int)ls, carry, tc, ts, o);
+		if (n_pac) hipLaunchKernelGGL(k_fa_pack, dim3(grid_for(n_pac)), dim3(IDX_BLOCK), 0, st, d_codes.as<u8>(), l0, nk, d_pac.as<u8>(), n_pac);
+		(void)hipEventRecord(ev1, st);
+		u64 errw = 0;
+		h_pac.resize(n_pac); h_hoff.resize(ns); h_hchr.resize(ns); h_hend.resize(ne); h_hpos.resize(nh); h_hdoff.resize(nh);
+		if (hip("download", hipMemcpyAsync(&errw, d_err.p, 8, hipMemcpyDeviceToHost, st)) ||
+			(n_pac && hip("download", hipMemcpyAsync(h_pac.data(), d_pac.p, n_pac, hipMemcpyDeviceToHost, st))) ||
+			(ns && hip("download", hipMemcpyAsync(h_hoff.data(), d_hoff.p, ns * 8, hipMemcpyDeviceToHost, st))) ||
+			(ns && hip("download", hipMemcpyAsync(h_hchr.data(), d_hchr.p, ns, hipMemcpyDeviceToHost, st))) ||
+			(ne && hip("download", hipMemcpyAsync(h_hend.data(), d_hend.p, ne * 8, hipMemcpyDeviceToHost, st))) ||
+			(nh && hip("download", hipMemcpyAsync(h_hpos.data(), d_hpos.p, nh * 8, hipMemcpyDeviceToHost, st))) ||
+			(nh && hip("download", hipMemcpyAsync(h_hdoff.data(), d_hdoff.p, nh * 8, hipMemcpyDeviceToHost, st))) ||
+			hip("sync", hipStreamSynchronize(st))) return rc;
+		{ float ms = 0; if (hipEventElapsedTime(&ms, ev0, ev1) == hipSuccess) parse_ms += ms; }
+		if (errw) {
+			const u64 pos = stage_pos + ((1ull << 40) - (errw >> 8));
+			char m[200];
+			snprintf(m, sizeof m, (errw & 0xFF) == FA_ERR_FASTQ ? "FASTQ record structure ('+' or '@' at the start of a sequence line) at byte offset %llu"
+																 : "NUL or non-ASCII byte in a sequence line at byte offset %llu", (unsigned long long)(skipped + pos));
+			return fail(BWAGPU_EINVAL, m);
+		}
+		// header lines: the one left open by the last chunk ends before any that starts here
+		size_t hp = 0;
+		auto read_line = [&](size_t from) -> bool {        // append stage[from..) up to '\n' to hdr; true when the line ended in this chunk
+			const u8 *q = (const u8*)memchr(stage + from, '\n', n - from);
+			const size_t e = q ? (size_t)(q - stage) : n;
+			hdr.append((const char*)stage + from, e - from);
+			return q != nullptr;
+		};
+		if (in_hdr && read_line(0)) { finish_header(contigs.back(), hdr); in_hdr = false; }
+		for (; hp < nh; ++hp) {
+			contigs.push_back(Contig());
+			contigs.back().offset = h_hdoff[hp];
+			hdr.clear();
+			if (read_line((size_t)h_hpos[hp] + 1)) finish_header(contigs.back(), hdr);
+			else in_hdr = true;
+		}
+		if (n_pac) {
+			if (grow_pac((l0 >> 2) + n_pac + 1)) return rc;
+			pac[l0 >> 2] |= h_pac[0];
+			if (n_pac > 1) memcpy(pac + (l0 >> 2) + 1, h_pac.data() + 1, n_pac - 1);
+		}
+		hole_off.insert(hole_off.end(), h_hoff.begin(), h_hoff.end());
+		hole_chr.insert(hole_chr.end(), h_hchr.begin(), h_hchr.end());
+		hole_end.insert(hole_end.end(), h_hend.begin(), h_hend.end());
+		carry = tot;
+		ls = stage[n - 1] == '\n';
+		memmove(stage, stage + n, n_stage - n);
+		n_stage -= n; stage_pos += n;
+		return 0;
+	}
+};
+
+static void fa_err(const bwagpu_fasta_parser_t *p, char *errbuf, size_t errlen)
+{
+	if (errbuf && errlen) snprintf(errbuf, errlen, "%s", p->err.c_str());
+}
+
+extern "C" int bwagpu_fasta_begin(bwagpu_fasta_parser_t **out, int device, int64_t chunk_bytes, char *errbuf, size_t errlen)
+{
+	if (errbuf && errlen) errbuf[0] = 0;
+	if (!out) return BWAGPU_EINVAL;
+	*out = nullptr;
+	int ndev = 0;
+	if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev || hipSetDevice(device) != hipSuccess) return BWAGPU_ENODEV;
+	bwagpu_fasta_parser_t *p = new bwagpu_fasta_parser_t();
+	p->carry = fa_zero();
+	p->chunk = chunk_bytes > 0 ? (size_t)chunk_bytes : ((size_t)256 << 20);
+	if (hipStreamCreate(&p->st) != hipSuccess || hipEventCreate(&p->ev0) != hipSuccess || hipEventCreate(&p->ev1) != hipSuccess) { delete p; return BWAGPU_ENODEV; }
+	if (hipHostMalloc((void**)&p->stage, p->chunk + 1, hipHostMallocDefault) != hipSuccess || p->d_jump.ensure(96 * 8)) {
+		p->stage = nullptr; delete p;
+		if (errbuf && errlen) snprintf(errbuf, errlen, "allocation of the FASTA staging buffers failed");
+		return BWAGPU_ENOMEM;
+	}
+	u64 jump[96];                 // the lrand48 step x -> a x + c (mod 2^48) applied 2^j times
+	u64 a = 0x5DEECE66Dull, c = 0xBull;
+	const u64 M = (1ull << 48) - 1;
+	for (int j = 0; j < 48; ++j) { jump[2 * j] = a; jump[2 * j + 1] = c; c = (a * c + c) & M; a = (a * a) & M; }
+	if (hipMemcpy(p->d_jump.p, jump, sizeof jump, hipMemcpyHostToDevice) != hipSuccess) { delete p; return BWAGPU_EHIP; }
+	*out = p;
+	return 0;
+}
+
+extern "C" int bwagpu_fasta_feed(bwagpu_fasta_parser_t *p, const void *data, int64_t len, char *errbuf, size_t errlen)
+{
+	if (errbuf && errlen) errbuf[0] = 0;
+	if (!p || len < 0 || (len && !data)) return BWAGPU_EINVAL;
+	const u8 *s = (const u8*)data;
+	size_t left = (size_t)len;
+	while (left && !p->rc) {
+		if (!p->started) {              // kseq_read: skip to the first '>' or '@' (kseq.h:181-184); '@' would make it FASTQ
+			size_t i = 0;
+			while (i < left && s[i] != '>' && s[i] != '@') ++i;
+			p->skipped += i; s += i; left -= i;
+			if (!left) break;
+			if (*s == '@') { char m[160]; snprintf(m, sizeof m, "FASTQ input: '@' before the first '>' at byte offset %llu", (unsigned long long)p->skipped); p->fail(BWAGPU_EINVAL, m); break; }
+			p->started = true;
+		}
+		const size_t room = p->chunk + 1 - p->n_stage, k = left < room ? left : room;
+		memcpy(p->stage + p->n_stage, s, k);
+		p->n_stage += k; s += k; left -= k;
+		if (p->n_stage == p->chunk + 1) p->process(false);
+	}
+	if (p->rc) fa_err(p, errbuf, errlen);
+	return p->rc;
+}
+
+extern "C" void bwagpu_fasta_free(bwagpu_fasta_t *r)
+{
+	if (!r) return;
+	free(r->pac); free(r->seq_offset); free(r->seq_len); free(r->seq_n_ambs); free(r->names);
+	free(r->hole_offset); free(r->hole_len); free(r->hole_amb);
+	memset(r, 0, sizeof *r);
+}
+
+extern "C" int bwagpu_fasta_end(bwagpu_fasta_parser_t *p, bwagpu_fasta_t *out, char *errbuf, size_t errlen)
+{
+	if (errbuf && errlen) errbuf[0] = 0;
+	if (!p) return BWAGPU_EINVAL;
+	if (out) memset(out, 0, sizeof *out);
+	if (!p->rc) p->process(true);
+	if (!p->rc && p->in_hdr) {
+		// a header line at the end of the stream: a '>' with nothing after it makes no record (ks_getuntil returns -1, kseq.h:190)
+		if (p->hdr.empty()) p->contigs.pop_back();
+		else p->finish_header(p->contigs.back(), p->hdr);
+	}
+	if (!p->rc && p->contigs.empty()) p->fail(BWAGPU_EINVAL, p->started ? "no FASTA record" : "no FASTA record (no '>' in the input)");
+	const u64 l_pac = p->carry.nk;
+	if (!p->rc && l_pac == 0) p->fail(BWAGPU_EINVAL, "the FASTA records hold no base");
+	if (!p->rc && p->hole_end.size() + 1 == p->hole_off.size()) p->hole_end.push_back(l_pac);       // a hole open at the end
+	if (!p->rc && p->hole_end.size() != p->hole_off.size()) p->fail(BWAGPU_EHIP, "internal: hole starts and ends do not pair up");
+	const size_t n_seqs = p->contigs.size(), n_holes = p->hole_off.size();
+	for (size_t i = 0; !p->rc && i < n_seqs; ++i) {
+		const u64 e = i + 1 < n_seqs ? p->contigs[i + 1].offset : l_pac;
+		if (e - p->contigs[i].offset >= (1ull << 31)) p->fail(BWAGPU_EINVAL, "contig '" + p->contigs[i].name + "' has 2^31 bases or more (bntann1_t::len is 32-bit)");
+	}
+	for (size_t i = 0; !p->rc && i < n_holes; ++i)
+		if (p->hole_end[i] - p->hole_off[i] >= (1ull << 31)) p->fail(BWAGPU_EINVAL, "a run of ambiguous bases of 2^31 or more (bntamb1_t::len is 32-bit)");
+	if (!p->rc && out) {
+		size_t nb = 0;
+		for (auto &c : p->contigs) nb += c.name.size() + c.anno.size() + 2;
+		if (p->grow_pac(l_pac / 4 + 1)) goto done;
+		out->pac = p->pac; p->pac = nullptr;
+		out->l_pac = (int64_t)l_pac; out->n_seqs = (int32_t)n_seqs; out->n_holes = (int64_t)n_holes; out->names_bytes = (int64_t)nb;
+		out->seq_offset = (int64_t*)malloc(n_seqs * 8 + 8); out->seq_len = (int32_t*)malloc(n_seqs * 4 + 4); out->seq_n_ambs = (int32_t*)malloc(n_seqs * 4 + 4);
+		out->names = (char*)malloc(nb + 1);
+		out->hole_offset = (int64_t*)malloc(n_holes * 8 + 8); out->hole_len = (int32_t*)malloc(n_holes * 4 + 4); out->hole_amb = (char*)malloc(n_holes + 1);
+		if (!out->seq_offset || !out->seq_len || !out->seq_n_ambs || !out->names || !out->hole_offset || !out->hole_len || !out->hole_amb) { bwagpu_fasta_free(out); p->fail(BWAGPU_ENOMEM, "malloc failed (FASTA tables)"); goto done; }
+		size_t w = 0, h = 0;
+		for (size_t i = 0; i < n_seqs; ++i) {
+			const auto &c = p->contigs[i];
+			const u64 e = i + 1 < n_seqs ? p->contigs[i + 1].offset : l_pac;
+			out->seq_offset[i] = (int64_t)c.offset; out->seq_len[i] = (int32_t)(e - c.offset);
+			int32_t na = 0;
+			while (h < n_holes && p->hole_off[h] < e) { ++na; ++h; }       // (holes never cross contigs and come in offset order)
+			out->seq_n_ambs[i] = na;
+			memcpy(out->names + w, c.name.c_str(), c.name.size() + 1); w += c.name.size() + 1;
+			memcpy(out->names + w, c.anno.c_str(), c.anno.size() + 1); w += c.anno.size() + 1;
+		}
+		for (size_t i = 0; i < n_holes; ++i) {
+			out->hole_offset[i] = (int64_t)p->hole_off[i]; out->hole_len[i] = (int32_t)(p->hole_end[i] - p->hole_off[i]); out->hole_amb[i] = p->hole_chr[i];
+		}
+		out->parse_ms = p->parse_ms;
+	}
+done:
+	const int rc = p->rc;
+	if (rc) fa_err(p, errbuf, errlen);
+	delete p;
 	return rc;
 }

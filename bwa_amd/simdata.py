@@ -218,3 +218,48 @@ def write_fastq(path: str, reads: np.ndarray, name_prefix: str = "r", suffix: st
             rec[:, k] = 10
             rec.tofile(f)
             lo = hi
+
+
+def write_fasta_ambiguous(path: str, g: np.ndarray, lens, seed: int = 5, n_frac: float = 0.05, width: int = 60, prefix: str = "chr"):
+    """write_fasta with the ambiguity structure of a real assembly (GRCh38: ~5 % N in runs of tens of bp to 100 kbp, N at the
+    contig ends, scattered IUPAC codes, soft-masked lower-case stretches) and `width`-column lines.  Every contig keeps at
+    least one A/C/G/T base.  Returns the number of non-ACGT bytes written."""
+    rng = np.random.default_rng(seed)
+    total = int(sum(int(x) for x in lens))
+    a = _ASCII[:4][g[:total]]
+    n_amb = 0
+    off = 0
+    starts = np.cumsum([0] + [int(x) for x in lens])
+    for ln in lens:                                   # telomere-like N at both ends of every contig
+        e = min(10_000, int(ln) // 20)
+        if e:
+            a[off:off + e] = ord("N"); a[off + int(ln) - e:off + int(ln)] = ord("N")
+        off += int(ln)
+    budget = int(total * n_frac)
+    while budget > 0:                                 # N runs, log-uniform 10 bp .. 100 kbp
+        ln = int(10 ** rng.uniform(1, 5))
+        s = int(rng.integers(0, max(1, total - ln)))
+        a[s:s + ln] = ord("N")
+        budget -= ln
+    k = max(1, total // 50_000)                       # soft-masked stretches (lower case: acgt and n)
+    for s, ln in zip(rng.integers(0, total, k), rng.integers(50, 5000, k)):
+        a[s:s + ln] |= 0x20
+    k = max(1, total // 20_000)                       # scattered IUPAC codes
+    a[rng.integers(0, total, k)] = np.frombuffer(b"RYKMSWBDHVN", dtype=np.uint8)[rng.integers(0, 11, k)]
+    for i in range(len(lens)):                        # (an all-N contig is legal, but keep the index's contigs alignable)
+        a[starts[i] + int(lens[i]) // 2] = ord("A")
+    up = a & 0xDF
+    n_amb = int(np.count_nonzero((up != 65) & (up != 67) & (up != 71) & (up != 84)))
+    with open(path, "wb") as f:
+        for i, ln in enumerate(lens):
+            f.write(f">{prefix}{i + 1} AC:{prefix}{i + 1}.1 len={int(ln)}\n".encode())
+            seq = a[starts[i]:starts[i] + int(ln)]
+            full = int(ln) // width * width
+            if full:
+                body = np.empty((full // width, width + 1), dtype=np.uint8)
+                body[:, :width] = seq[:full].reshape(-1, width)
+                body[:, width] = 10
+                f.write(body.tobytes())
+            if full < int(ln):
+                f.write(seq[full:].tobytes() + b"\n")
+    return n_amb

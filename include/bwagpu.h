@@ -280,6 +280,35 @@ typedef struct {
 int bwagpu_index_build(const uint8_t *pac, int64_t l_pac, int sa_intv, int device, bwagpu_built_t *out, char *errbuf, size_t errlen);
 void bwagpu_built_free(bwagpu_built_t *b);
 
+/* ---- FASTA -> .pac/.ann/.amb on the device (what bns_fasta2bntseq computes, bntseq.c:280-333) ------------------------------- */
+/* A streaming parser: begin, feed the FASTA text (uncompressed) in pieces of any size, end.  The per-byte work -- which bytes
+ * are bases, their codes (ambiguity codes replaced by the lrand48() stream after srand48(11), as bwa index does), the holes --
+ * runs on the device in chunks of chunk_bytes (<= 0: 256 MiB); the host parses the header lines.  Input that the reference
+ * reads as FASTQ or does not define (an '@' before the first '>', a sequence line starting with '+' or '@', a NUL or a byte
+ * >= 0x80 in a sequence line, no record, no base, a contig or hole of 2^31 bases or more) fails with BWAGPU_EINVAL and a
+ * message naming the byte offset.  After a failure the parser only accepts bwagpu_fasta_end (which reports it again).
+ * bwagpu_fasta_end always releases the parser and its device memory; the result's arrays are freed with bwagpu_fasta_free
+ * (each is also freeable with bwagpu_free).  result.pac goes to bwagpu_index_build unchanged. */
+typedef struct bwagpu_fasta_parser_s bwagpu_fasta_parser_t;
+typedef struct {
+	uint8_t *pac;            /* forward strand, l_pac / 4 + 1 bytes in the .pac layout (bntseq.c:229) */
+	int64_t l_pac;
+	int32_t n_seqs;
+	int64_t *seq_offset;     /* per contig: bntann1_t offset, len, n_ambs */
+	int32_t *seq_len, *seq_n_ambs;
+	char *names;             /* per contig: name NUL anno NUL (anno "(null)" for an empty comment, as bntann1_t::anno) */
+	int64_t names_bytes;
+	int64_t n_holes;
+	int64_t *hole_offset;    /* per hole: bntamb1_t offset, len, amb */
+	int32_t *hole_len;
+	char *hole_amb;
+	float parse_ms;          /* device time of the parse kernels */
+} bwagpu_fasta_t;
+int bwagpu_fasta_begin(bwagpu_fasta_parser_t **p, int device, int64_t chunk_bytes, char *errbuf, size_t errlen);
+int bwagpu_fasta_feed(bwagpu_fasta_parser_t *p, const void *data, int64_t len, char *errbuf, size_t errlen);
+int bwagpu_fasta_end(bwagpu_fasta_parser_t *p, bwagpu_fasta_t *out, char *errbuf, size_t errlen);
+void bwagpu_fasta_free(bwagpu_fasta_t *r);
+
 /* ---- lifetime ------------------------------------------------------------------------------------------ */
 
 /* Create a handle on HIP device `device` and upload the index once (replaces nothing in the reference; it is
