@@ -36,6 +36,8 @@ CIGAR_DTYPE = np.dtype([("score", "<i4"), ("n_cigar", "<i4"), ("cigar", "<u4", (
 assert CIGAR_DTYPE.itemsize == 48
 DP_CASE_DTYPE = np.dtype([("q_off", "<i4"), ("q_len", "<i4"), ("t_off", "<i4"), ("t_len", "<i4"), ("w", "<i4"), ("h0", "<i4"), ("end_bonus", "<i4"), ("flags", "<i4")])   # bwagpu_dp_case_t
 assert DP_CASE_DTYPE.itemsize == 32
+SORT_KEY_DTYPE = np.dtype([("a", "<i8"), ("b", "<i4"), ("c", "<i4")])   # bwagpu_sort_key_t
+assert SORT_KEY_DTYPE.itemsize == 16
 
 
 class Stats(C.Structure):
@@ -57,7 +59,7 @@ EXPORTS = [
     "bwagpu_index_info", "bwagpu_densify_sa", "bwagpu_set_stats", "bwagpu_get_stats", "bwagpu_align_bseq", "bwagpu_align_flat",
     "bwagpu_free", "bwagpu_batch_upload", "bwagpu_batch_run", "bwagpu_batch_download", "bwagpu_set_taps", "bwagpu_tap_intervals",
     "bwagpu_tap_chains", "bwagpu_tap_regs_raw", "bwagpu_index_buffers", "bwagpu_index_export", "bwagpu_clone", "bwagpu_index_ready",
-    "bwagpu_batch_cigars", "bwagpu_batch_cigar_ops", "bwagpu_debug_phase", "bwagpu_batch_matesw", "bwagpu_clone_to_device", "bwagpu_index_build", "bwagpu_built_free", "bwagpu_abi_sizes", "bwagpu_debug_prof", "bwagpu_debug_hist", "bwagpu_debug_seed_x2", "bwagpu_debug_chain_hist", "bwagpu_debug_dp", "bwagpu_set_cigar_filter", "bwagpu_batch_reserve", "bwagpu_batch_footprint", "bwagpu_mem_info",
+    "bwagpu_batch_cigars", "bwagpu_batch_cigar_ops", "bwagpu_debug_phase", "bwagpu_batch_matesw", "bwagpu_clone_to_device", "bwagpu_index_build", "bwagpu_built_free", "bwagpu_abi_sizes", "bwagpu_debug_prof", "bwagpu_debug_hist", "bwagpu_debug_seed_x2", "bwagpu_debug_chain_hist", "bwagpu_debug_dp", "bwagpu_debug_sort", "bwagpu_debug_sort_limits", "bwagpu_set_cigar_filter", "bwagpu_batch_reserve", "bwagpu_batch_footprint", "bwagpu_mem_info",
     "bwagpu_trim", "bwagpu_set_option", "bwagpu_get_option", "bwagpu_set_default_option", "bwagpu_clear_default_options", "bwagpu_option_name",
 ]
 
@@ -105,6 +107,7 @@ def load_library(path: str | None = None) -> C.CDLL:
     L.bwagpu_index_buffers.argtypes = [C.c_void_p] + [C.c_void_p] * 6
     L.bwagpu_index_export.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.bwagpu_debug_dp.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+    L.bwagpu_debug_sort.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     L.bwagpu_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_longlong]
     L.bwagpu_get_option.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p]
     L.bwagpu_set_default_option.argtypes = [C.c_char_p, C.c_longlong]
@@ -273,6 +276,22 @@ class BwaGpu:
         out = np.zeros((cases.shape[0], 72), dtype=np.int32)
         self._chk(self.L.bwagpu_debug_dp(self.h, C.byref(opt), kind, cases.shape[0], cases.ctypes.data, seqs.ctypes.data, seqs.shape[0], out.ctypes.data))
         return out
+
+    def debug_sort_limits(self) -> dict:
+        """bwagpu_debug_sort_limits: the sizes at which the library's sorts change their method, as compiled."""
+        out = (C.c_int32 * 8)()
+        self.L.bwagpu_debug_sort_limits(out)
+        return dict(zip(("pub_max", "cw_pw_lds", "cw_flt_lds", "dedup_keysort_min", "par_cap_max", "chain_sort_lane_max", "dd_net_default"), list(out)))
+
+    def debug_sort(self, kind: int, keys: np.ndarray, off: np.ndarray, dd_net: int = 129, par_cap: int = 128, chain_flt_lds: int = 256):
+        """bwagpu_debug_sort: one of the device's sorts on every case keys[off[k]:off[k + 1]] (SORT_KEY_DTYPE) -> (perm int32[len(keys)], status int32[n_cases])."""
+        keys = np.ascontiguousarray(keys, dtype=SORT_KEY_DTYPE)
+        off = np.ascontiguousarray(off, dtype=np.int64)
+        assert off.shape[0] >= 1 and int(off[-1]) == keys.shape[0]
+        perm = np.full(keys.shape[0], -1, dtype=np.int32)
+        status = np.full(off.shape[0] - 1, -1, dtype=np.int32)
+        self._chk(self.L.bwagpu_debug_sort(self.h, kind, off.shape[0] - 1, keys.ctypes.data, off.ctypes.data, dd_net, par_cap, chain_flt_lds, perm.ctypes.data, status.ctypes.data))
+        return perm, status
 
     def align(self, opt: MemOpt, seqs: np.ndarray, off: np.ndarray):
         self.upload(seqs, off)

@@ -1251,7 +1251,7 @@ extern "C" int bwagpu_batch_run(bwagpu_t *h, const bwagpu_opt_t *opt)
 			// Lane per read for the reads with one or two regions (nine in ten of the headline's); the others are listed by k_dedup and done by two more
 			// launches, one wavefront per read with the decisions' operands in LDS (dedup_read_par, dev_dedupp.h): the reads of up to dedup_stage regions
 			// (16.6 KB of LDS per wave, nine to a CU), then the few with more (up to dedup_big regions in 64 KB; beyond that, in place in HBM).
-			B.dd_heavy_min = dd_heavy_min; B.dd_list = h->d_heavy.as<i32>(); B.dd_prio = cfg.dedup_prio != 0; B.dd_net = (int)(cfg.dedup_net < 0 ? 129 : cfg.dedup_net);
+			B.dd_heavy_min = dd_heavy_min; B.dd_list = h->d_heavy.as<i32>(); B.dd_prio = cfg.dedup_prio != 0; B.dd_net = (int)(cfg.dedup_net < 0 ? DEDUP_NET_DEFAULT : cfg.dedup_net);
 			B.dd_stage_cap = dd.cap_m > 0 ? dd.cap_m : 0x3fffffff;      // (no LDS arrays: one list, every read in place)
 			hipLaunchKernelGGL(k_dedup, dim3((unsigned)share(grid.x)), block, 0, h->stream, h->ix, *opt, B);
 			if (B.dd_heavy_min > 0) {
@@ -1708,6 +1708,74 @@ done:
 	(void)hipStreamSynchronize(h->stream);
 	d_seq.release(); d_pac.release(); d_cases.release(); d_out.release(); d_scr.release(); d_pac2.release();
 	return rc;
+}
+
+// ---- differential tests of the sorts (dev_debug.h) ----------------------------------------------------------------------------
+extern "C" int bwagpu_debug_sort(bwagpu_t *h, int kind, int n_cases, const bwagpu_sort_key_t *keys, const int64_t *off, int dd_net, int par_cap, int chain_flt_lds, int32_t *perm, int32_t *status)
+{
+	if (!h || kind < 0 || kind > DBG_SORT_PAR_BEST || n_cases < 0 || (n_cases > 0 && (!off || !status))) return BWAGPU_EINVAL;
+	if (n_cases == 0) return BWAGPU_OK;
+	static_assert(sizeof(bwagpu_sort_key_t) == 16, "layout");
+	if (off[0] != 0) return BWAGPU_EINVAL;
+	for (int i = 0; i < n_cases; ++i) if (off[i + 1] < off[i] || off[i + 1] - off[i] > (1 << 20)) return BWAGPU_EINVAL;
+	const size_t tot = (size_t)off[n_cases];
+	if (tot > 0 && (!keys || !perm)) return BWAGPU_EINVAL;
+	const bool par = kind == DBG_SORT_PAR_END || kind == DBG_SORT_PAR_BEST;
+	if (par && (par_cap < 2 || par_cap > DBG_SORT_PAR_CAP_MAX || dd_net < 0)) return BWAGPU_EINVAL;
+	if (kind == DBG_SORT_CHAIN_W && chain_flt_lds < 0) return BWAGPU_EINVAL;
+	if (chain_flt_lds > CW_FLT_LDS) chain_flt_lds = CW_FLT_LDS;                  // (as the option is read, batch_run)
+	HIPCHK(h, hipSetDevice(h->device));
+	DevBuf d_keys, d_off, d_perm, d_st, d_a, d_b;      // d_a: the records a kind sorts (or its seeds), d_b: its second array (key scratch, srt[], the block kernel's staging records)
+	int rc = BWAGPU_OK;
+	hipError_t e = hipSuccess;
+	const bool lane_kind = kind == DBG_SORT_U64 || kind == DBG_SORT_INTV || kind == DBG_SORT_REG_END || kind == DBG_SORT_REG_BEST;
+	const int blk_grid = n_cases < 128 ? n_cases : 128;
+	size_t bytes_a = 16, bytes_b = 16;
+	if (kind == DBG_SORT_U64) bytes_a = tot * 8;
+	else if (kind == DBG_SORT_INTV) bytes_a = tot * sizeof(Intv3);
+	else if (kind == DBG_SORT_INTV_BLK) { bytes_a = tot * sizeof(Intv3); bytes_b = (size_t)blk_grid * PUB_MAX * sizeof(Intv3); }
+	else if (kind == DBG_SORT_REG_END || kind == DBG_SORT_REG_BEST) { bytes_a = tot * sizeof(bwagpu_alnreg_t); bytes_b = tot * sizeof(RegKey); }
+	else if (kind == DBG_SORT_CHAIN_SEEDS) { bytes_a = tot * sizeof(bwagpu_seed_t); bytes_b = tot * 8; }
+	else if (kind == DBG_SORT_CHAIN_W) { bytes_a = tot * 4; bytes_b = tot * 8; }
+	if (d_keys.ensure(tot * sizeof(bwagpu_sort_key_t) + 16) || d_off.ensure((size_t)(n_cases + 1) * 8) || d_perm.ensure(tot * 4 + 16) || d_st.ensure((size_t)n_cases * 4) || d_a.ensure(bytes_a + 16) || d_b.ensure(bytes_b + 16)) {
+		h->err = "hipMalloc failed (debug)"; rc = BWAGPU_ENOMEM; goto done;
+	}
+	if (tot) e = hipMemcpyAsync(d_keys.p, keys, tot * sizeof(bwagpu_sort_key_t), hipMemcpyHostToDevice, h->stream);
+	if (e == hipSuccess) e = hipMemcpyAsync(d_off.p, off, (size_t)(n_cases + 1) * 8, hipMemcpyHostToDevice, h->stream);
+	if (e == hipSuccess) e = hipMemsetAsync(d_perm.p, 0xff, tot * 4 + 16, h->stream);           // -1: a place nothing was written to
+	if (e == hipSuccess) e = hipMemsetAsync(d_st.p, 0xff, (size_t)n_cases * 4, h->stream);
+	if (e == hipSuccess) {
+		const bwagpu_sort_key_t *dk = d_keys.as<bwagpu_sort_key_t>(); const i64 *dof = d_off.as<i64>(); i32 *dp = d_perm.as<i32>(), *ds = d_st.as<i32>();
+		if (lane_kind) {
+			const dim3 grid((unsigned)((n_cases + 255) / 256 < 1024 ? (n_cases + 255) / 256 : 1024)), blk(256);
+			if (kind == DBG_SORT_U64) hipLaunchKernelGGL((k_debug_sort_lane<DBG_SORT_U64>), grid, blk, 0, h->stream, n_cases, dk, dof, d_a.as<u64>(), (Intv3*)nullptr, (bwagpu_alnreg_t*)nullptr, (RegKey*)nullptr, dp, ds);
+			else if (kind == DBG_SORT_INTV) hipLaunchKernelGGL((k_debug_sort_lane<DBG_SORT_INTV>), grid, blk, 0, h->stream, n_cases, dk, dof, (u64*)nullptr, d_a.as<Intv3>(), (bwagpu_alnreg_t*)nullptr, (RegKey*)nullptr, dp, ds);
+			else if (kind == DBG_SORT_REG_END) hipLaunchKernelGGL((k_debug_sort_lane<DBG_SORT_REG_END>), grid, blk, 0, h->stream, n_cases, dk, dof, (u64*)nullptr, (Intv3*)nullptr, d_a.as<bwagpu_alnreg_t>(), d_b.as<RegKey>(), dp, ds);
+			else hipLaunchKernelGGL((k_debug_sort_lane<DBG_SORT_REG_BEST>), grid, blk, 0, h->stream, n_cases, dk, dof, (u64*)nullptr, (Intv3*)nullptr, d_a.as<bwagpu_alnreg_t>(), d_b.as<RegKey>(), dp, ds);
+		} else if (kind == DBG_SORT_INTV_BLK) {
+			hipLaunchKernelGGL(k_debug_sort_blk, dim3(blk_grid), dim3(256), 0, h->stream, n_cases, dk, dof, d_a.as<Intv3>(), d_b.as<Intv3>(), dp, ds);
+		} else {
+			const dim3 grid((unsigned)(n_cases < 2048 ? n_cases : 2048)), blk(64);
+			if (kind == DBG_SORT_CHAIN_SEEDS) hipLaunchKernelGGL((k_debug_sort_wave<DBG_SORT_CHAIN_SEEDS>), grid, blk, 0, h->stream, n_cases, dk, dof, d_a.as<bwagpu_seed_t>(), d_b.as<u64>(), (i32*)nullptr, 0, 0, 0, dp, ds);
+			else if (kind == DBG_SORT_CHAIN_W) hipLaunchKernelGGL((k_debug_sort_wave<DBG_SORT_CHAIN_W>), grid, blk, (size_t)CW_LDS_BYTES, h->stream, n_cases, dk, dof, (bwagpu_seed_t*)nullptr, d_b.as<u64>(), d_a.as<i32>(), 0, 0, chain_flt_lds, dp, ds);
+			else if (kind == DBG_SORT_PAR_END) hipLaunchKernelGGL((k_debug_sort_wave<DBG_SORT_PAR_END>), grid, blk, DDW_PAR_BYTES(par_cap), h->stream, n_cases, dk, dof, (bwagpu_seed_t*)nullptr, (u64*)nullptr, (i32*)nullptr, dd_net, par_cap, 0, dp, ds);
+			else hipLaunchKernelGGL((k_debug_sort_wave<DBG_SORT_PAR_BEST>), grid, blk, DDW_PAR_BYTES(par_cap), h->stream, n_cases, dk, dof, (bwagpu_seed_t*)nullptr, (u64*)nullptr, (i32*)nullptr, dd_net, par_cap, 0, dp, ds);
+		}
+		e = hipGetLastError();
+	}
+	if (e == hipSuccess && tot) e = hipMemcpyAsync(perm, d_perm.p, tot * 4, hipMemcpyDeviceToHost, h->stream);
+	if (e == hipSuccess) e = hipMemcpyAsync(status, d_st.p, (size_t)n_cases * 4, hipMemcpyDeviceToHost, h->stream);
+	if (e == hipSuccess) e = wait_stream(h);
+	if (e != hipSuccess) { h->err = std::string("bwagpu_debug_sort: ") + hipGetErrorString(e); rc = BWAGPU_EHIP; }
+done:
+	(void)hipStreamSynchronize(h->stream);
+	d_keys.release(); d_off.release(); d_perm.release(); d_st.release(); d_a.release(); d_b.release();
+	return rc;
+}
+
+extern "C" void bwagpu_debug_sort_limits(int32_t out[8])
+{
+	out[0] = PUB_MAX; out[1] = CW_PW_LDS; out[2] = CW_FLT_LDS; out[3] = DEDUP_KEYSORT_MIN; out[4] = DBG_SORT_PAR_CAP_MAX; out[5] = CHAIN_SORT_LANE_MAX; out[6] = DEDUP_NET_DEFAULT; out[7] = 0;
 }
 
 // ---- stage taps ----------------------------------------------------------------------------------------------

@@ -349,6 +349,35 @@ __device__ int chain_seeds_regs(const DevIndex &ix, const bwagpu_opt_t &opt, int
 	return n_ch;
 }
 
+// Where chain_read_wave keeps the weight sort's arrays for a read of n chains (also bwagpu_debug_sort's, dev_debug.h): the {weight, index} pairs in the wave's LDS
+// area up to CW_PW_LDS of them (unless option chain_flt_lds is 0), else in the read's HBM scratch; the sorted order in LDS up to chain_flt_lds chains, else in HBM
+DEVFN unsigned char *cw_area(unsigned char *lds) { return lds + CW_STACK_INTS * 4 + CW_FLT_LDS * 4; }
+DEVFN int2 *cw_pw_place(int n, int chain_flt_lds, unsigned char *area, void *hbm) { return n <= CW_PW_LDS && chain_flt_lds > 0 ? (int2*)area : (int2*)hbm; }
+DEVFN i32 *cw_sord_place(int n, int chain_flt_lds, unsigned char *lds, i32 *hbm) { return n <= chain_flt_lds ? (i32*)(lds + CW_STACK_INTS * 4) : hbm; }
+
+// ks_introsort of the {weight, index} pairs pw[0 .. n) (bwamem.c:367; n >= 1) by the wave: sord[place] = index.  (Also bwagpu_debug_sort's entry,
+// dev_debug.h.  The caller puts a wave_sync behind it.)
+DEVFN void cw_weight_order(int2 *pw, int n, i32 *sord, int lane)
+{
+	if (n >= 3) {
+		if (lane == 0) dev_introsort<int2, ChainWGreater, false>(pw, n, ChainWGreater());
+		wave_sync();
+	}
+	for (int x0 = 0; x0 < n; x0 += 64) {
+		const int x = x0 + lane;
+		const int2 e = x < n ? pw[x] : make_int2(0, 0);
+		const u64 kx = (u64)(u32)e.x << 32 | (u32)~x;
+		int place = 0;
+		for (int c = 0; c < n; c += 64) {
+			const int yy = c + lane;
+			const u64 ky = yy < n ? ((u64)(u32)pw[yy].x << 32 | (u32)~yy) : 0ull;      // (0: greater than no key)
+			const int cnt = n - c < 64 ? n - c : 64;
+			for (int t = 0; t < cnt; ++t) place += (u64)readlane_i64((i64)ky, t) > kx;
+		}
+		if (x < n) sord[place] = e.y;
+	}
+}
+
 // stats runs: 10 ns ticks spent per phase, summed over the reads (row 2 of chain_hist: [0] register-form seed loop, [1] tree-form seed loop, [2] repeat fraction and
 // in-order list, [3] weights, [4] sort, [5] pairwise filter, [6] publishing, [7] the longest read, [8] reads)
 #define CW_PHASE(i) do { if (B.stats) { const long long t_ = wall_clock64(); ph[i] += (u64)(t_ - t_ph); t_ph = t_; } } while (0)
@@ -370,7 +399,7 @@ __device__ void chain_read_wave(const DevIndex &ix, const bwagpu_opt_t &opt, con
 	const RegionView R = region_of(B.slot_blob, so, ns);
 	// ---- storage: the read's region of HBM; LDS for the traversal stack and, for reads of up to CW_FLT_LDS chains, what the sort and the filter work on ----
 	i32 *nd = B.nodes + uni64(no_) * BT_NODE_INTS; ChainRec *ch = R.chain; i32 *ord = R.ord, *stk = (i32*)lds;
-	unsigned char *const area = lds + CW_STACK_INTS * 4 + CW_FLT_LDS * 4;
+	unsigned char *const area = cw_area(lds);
 	const i64 *pos = (const i64*)(B.slot_pos + so);
 	const i32 *sqb = B.slot_qbeg + so, *sln = B.slot_len + so, *srid = B.slot_rid + so;
 	i32 *next = R.next;
@@ -477,7 +506,7 @@ __device__ void chain_read_wave(const DevIndex &ix, const bwagpu_opt_t &opt, con
 	int n = tree ? cw_inorder(nd, root, ord, stk, lane) : n_ch;
 	CW_PHASE(2);
 	// ---- mem_chain_flt (bwamem.c:353-411): weights (lane per chain), drop light chains keeping the order ----
-	int2 *pw = n <= CW_PW_LDS && B.chain_flt_lds > 0 ? (int2*)area : (int2*)R.srt;
+	int2 *pw = cw_pw_place(n, B.chain_flt_lds, area, R.srt);
 	int k = 0;
 	for (int base = 0; base < n; base += 64) {
 		const int i = base + lane;
@@ -513,25 +542,9 @@ __device__ void chain_read_wave(const DevIndex &ix, const bwagpu_opt_t &opt, con
 	// lane 0: the quicksort passes (dev_sort.h).  The insertion sort that ends ks_introsort is a stable sort of the arrangement they leave, and a stable
 	// sort's result is its definition: a chain's place is the number of chains that are heavier, or equally heavy and ahead of it -- counted by every lane
 	// for its own chain, the others' {weight, ~place} keys read lane by lane from registers.
-	if (n >= 3) {
-		if (lane == 0) dev_introsort<int2, ChainWGreater, false>(pw, n, ChainWGreater());
-		wave_sync();
-	}
 	const bool flt_lds = n <= B.chain_flt_lds;         // (option chain_flt_lds: CW_FLT_LDS, or less to send ordinary reads down the HBM path in tests)
-	i32 *sord = flt_lds ? (i32*)(lds + CW_STACK_INTS * 4) : ord;       // the chains in sorted order
-	for (int x0 = 0; x0 < n; x0 += 64) {
-		const int x = x0 + lane;
-		const int2 e = x < n ? pw[x] : make_int2(0, 0);
-		const u64 kx = (u64)(u32)e.x << 32 | (u32)~x;
-		int place = 0;
-		for (int c = 0; c < n; c += 64) {
-			const int yy = c + lane;
-			const u64 ky = yy < n ? ((u64)(u32)pw[yy].x << 32 | (u32)~yy) : 0ull;      // (0: greater than no key)
-			const int cnt = n - c < 64 ? n - c : 64;
-			for (int t = 0; t < cnt; ++t) place += (u64)readlane_i64((i64)ky, t) > kx;
-		}
-		if (x < n) sord[place] = e.y;
-	}
+	i32 *sord = cw_sord_place(n, B.chain_flt_lds, lds, ord);           // the chains in sorted order
+	cw_weight_order(pw, n, sord, lane);
 	wave_sync();
 	CW_PHASE(4);
 	// pairwise filter (bwamem.c:369-393): chain i against the kept chains, 64 at a time.  kinfo: the kept chains' {beg, end, weight, is_alt | has a shadow << 1};

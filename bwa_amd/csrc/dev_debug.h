@@ -1,4 +1,5 @@
-// dev_debug.h -- bwagpu_debug_dp: one wavefront of a device DP routine on caller-supplied sequences (differential tests).
+// dev_debug.h -- bwagpu_debug_dp: one wavefront of a device DP routine on caller-supplied sequences (differential tests); bwagpu_debug_sort (at the
+// end): the device's restatements of ks_introsort on caller-supplied keys.
 //
 // The whole-read parity tests feed the DP routines a narrow distribution of (h0, band, lengths); this entry lets a test drive
 // wave_ksw_extend2 (k_extend_wave, both modes), wave_ksw_global2 (k_cigar), wave_global2_score_ring (k_dedup_wave) and the
@@ -12,6 +13,8 @@
 #include "dev_cigar.h"
 #include "dev_dedupw.h"
 #include "dev_matesw.h"
+#include "dev_seed.h"
+#include "dev_chainw.h"
 
 #define DBG_OUT_INTS 72
 
@@ -209,5 +212,125 @@ __global__ void __launch_bounds__(256) k_debug_pack(const u8 *seqs, i64 n, u8 *p
 		u32 v = 0;
 		for (int k = 0; k < 4; ++k) { const i64 l = b * 4 + k; const u32 c = l < n ? seqs[l] & 3u : 0u; v |= c << ((3 - k) << 1); }   // _set_pac (bntseq.c:229)
 		pac[b] = (u8)v;
+	}
+}
+
+// ---- bwagpu_debug_sort: every form in which the device restates ks_introsort (ksort.h:176-226), on caller-supplied keys ---------------------------
+// BWA-MEM's output depends on the tie behaviour of that unstable sort, and several of the forms below are not its sequence of steps but an argument
+// that the result is the same; whole reads feed them only the key distributions that reads happen to produce (the depth limit's comb sort needs an
+// adversarial arrangement to run at all).  Each kernel calls the product's routine where the product calls it, with the arrays in the memory the product
+// keeps them in, and returns the permutation it produced: perm[place] = the element's index in the case.
+#define DBG_SORT_U64 0          // dev_ext.h's seed order: one lane's introsort of score << 32 | index
+#define DBG_SORT_CHAIN_SEEDS 1  // chain_sort_wave (dev_extw.h): lane 0's introsort up to 32 seeds, wave_sort_u64 above
+#define DBG_SORT_INTV 2         // k_publish: one lane's introsort of Intv3 records by info
+#define DBG_SORT_INTV_BLK 3     // k_publish_blk: the workgroup's network up to PUB_MAX intervals, one lane's introsort above
+#define DBG_SORT_CHAIN_W 4      // k_chain_wave: quicksort passes over {weight, index} pairs in LDS or HBM, the stable finish by counting
+#define DBG_SORT_REG_END 5      // k_dedup: one lane's sort of the 88-byte records (fewer than DEDUP_KEYSORT_MIN) or of their RegKey records, by end
+#define DBG_SORT_REG_BEST 6     //          ... by score, rb, qb
+#define DBG_SORT_PAR_END 7      // dedup_read_par: passes over DdKey in LDS, finish by counting or by the network (dd_net, par_cap), by end
+#define DBG_SORT_PAR_BEST 8     //          ... by score, rb, qb
+#define DBG_SORT_PAR_CAP_MAX 1100     // (DDP_LDS_PER_REG bytes of LDS each: within the 64 KB a launch gets without asking for more)
+
+// kinds 0, 2, 5, 6: a lane per case, as the product's lane-per-read kernels run these sorts (all arrays in HBM)
+template <int KIND> __global__ void __launch_bounds__(256) k_debug_sort_lane(int n_cases, const bwagpu_sort_key_t *keys, const i64 *off, u64 *srt_all, Intv3 *iv_all,
+																			 bwagpu_alnreg_t *reg_all, RegKey *rk_all, i32 *perm, i32 *status)
+{
+	for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < n_cases; k += gridDim.x * blockDim.x) {
+		const i64 o = off[k]; const int n = (int)(off[k + 1] - o);
+		const bwagpu_sort_key_t *kk = keys + o; i32 *pm = perm + o;
+		if (KIND == DBG_SORT_U64) {
+			u64 *srt = srt_all + o;
+			for (int i = 0; i < n; ++i) { bwagpu_seed_t s_; s_.rbeg = kk[i].a; s_.qbeg = kk[i].c; s_.len = 0; s_.score = kk[i].b; srt[i] = seed_order_key(s_, i); }   // dev_ext.h: the seeds by score
+			dev_introsort(srt, n, U64Less());
+			for (int i = 0; i < n; ++i) pm[i] = (i32)(u32)srt[i];
+		} else if (KIND == DBG_SORT_INTV) {
+			Intv3 *iv = iv_all + o;
+			for (int i = 0; i < n; ++i) { iv[i].x0 = (u64)i; iv[i].x2 = 0; iv[i].info = (u64)kk[i].a; }
+			if (n > 0) dev_introsort(iv, n, IntvInfoLess());
+			for (int i = 0; i < n; ++i) pm[i] = (i32)iv[i].x0;
+		} else {
+			bwagpu_alnreg_t *a = reg_all + o;
+			for (int i = 0; i < n; ++i) {
+				bwagpu_alnreg_t g; memset(&g, 0, sizeof g);
+				g.rb = kk[i].a; g.re = kk[i].a; g.score = kk[i].b; g.qb = kk[i].c; g.qe = kk[i].c + 1; g.seedlen0 = i;
+				a[i] = g;
+			}
+			if (n > 1) dedup_sort_regs<KIND == DBG_SORT_REG_BEST>(a, n, n >= DEDUP_KEYSORT_MIN ? rk_all + o : nullptr);     // (dedup_read: n > 1)
+			for (int i = 0; i < n; ++i) pm[i] = a[i].seedlen0;
+		}
+		status[k] = 0;
+	}
+}
+
+// kinds 1, 4, 7, 8: a wavefront per case
+template <int KIND> __global__ void __launch_bounds__(64) k_debug_sort_wave(int n_cases, const bwagpu_sort_key_t *keys, const i64 *off, bwagpu_seed_t *seed_all, u64 *srt_all, i32 *ord_all,
+																			int dd_net, int par_cap, int chain_flt_lds, i32 *perm, i32 *status)
+{
+	HIP_DYNAMIC_SHARED(unsigned char, dbg_lds)
+	const int lane = threadIdx.x & 63;
+	for (int k = blockIdx.x; k < n_cases; k += gridDim.x) {
+		const i64 o = off[k]; const int n = (int)(off[k + 1] - o);
+		const bwagpu_sort_key_t *kk = keys + o; i32 *pm = perm + o;
+		int st = 0;
+		wave_sync();                                             // (the LDS arrays' last readers: the case before)
+		if (KIND == DBG_SORT_CHAIN_SEEDS) {
+			bwagpu_seed_t *seeds = seed_all + o; u64 *srt = srt_all + o;
+			for (int i = lane; i < n; i += 64) { bwagpu_seed_t s_; s_.rbeg = kk[i].a; s_.qbeg = kk[i].c; s_.len = 0; s_.score = kk[i].b; seeds[i] = s_; }
+			wave_sync();
+			chain_sort_wave(seeds, srt, n);
+			wave_sync();
+			for (int i = lane; i < n; i += 64) pm[i] = (i32)(u32)srt[i];
+		} else if (KIND == DBG_SORT_CHAIN_W) {
+			// chain_read_wave's storage: the pairs in the wave's LDS area up to CW_PW_LDS of them, else in HBM; the sorted order in LDS up to chain_flt_lds chains
+			int2 *pw = cw_pw_place(n, chain_flt_lds, cw_area(dbg_lds), srt_all + o);
+			i32 *sord = cw_sord_place(n, chain_flt_lds, dbg_lds, ord_all + o);
+			for (int i = lane; i < n; i += 64) pw[i] = make_int2(kk[i].b, i);
+			wave_sync();
+			if (n > 0) cw_weight_order(pw, n, sord, lane);        // (chain_read_wave returns before its sort when no chain is left)
+			wave_sync();
+			for (int i = lane; i < n; i += 64) pm[i] = sord[i];
+		} else {
+			constexpr bool BEST = KIND == DBG_SORT_PAR_BEST;
+			DdHot *hot = (DdHot*)dbg_lds; DdKey *dk = (DdKey*)(hot + par_cap); i32 *ord = (i32*)(dk + par_cap);        // k_dedup_wave's layout: hot, keys, ord, ord2
+			if (n > par_cap) st = -2;                              // (k_dedup_wave takes such a read in place)
+			else if (n <= 1) { if (lane == 0 && n == 1) pm[0] = 0; }   // (dedup_read_par: nothing to sort)
+			else {
+				bool odd = false;
+				for (int i = lane; i < n; i += 64) {
+					DdHot h_; h_.rb = BEST ? kk[i].a : 0; h_.re = BEST ? 0 : kk[i].a; h_.qb = BEST ? kk[i].c : 0; h_.qe = h_.qb + 1; h_.rid = 0; h_.score = kk[i].b;
+					hot[i] = h_;
+					dk[i] = BEST ? ddp_key_best(h_, i) : ddp_key_end(h_, i);
+					odd |= ddp_odd(h_);                             // (rb and qb are the BEST order's: an END case carries its key in re alone)
+				}
+				if (wave_ballot(odd)) st = 1;
+				else {
+					wave_sync();
+					ddp_order<BEST>(dk, n, ord, dd_net, par_cap + par_cap / 2, lane);
+					wave_sync();
+					for (int i = lane; i < n; i += 64) pm[i] = ord[i];
+				}
+			}
+		}
+		if (lane == 0) status[k] = st;
+	}
+}
+
+// kind 3: a workgroup of 256 per case
+__global__ void __launch_bounds__(256) k_debug_sort_blk(int n_cases, const bwagpu_sort_key_t *keys, const i64 *off, Intv3 *iv_all, Intv3 *tmp_all, i32 *perm, i32 *status)
+{
+	__shared__ u64 s_key[PUB_MAX];
+	__shared__ unsigned short s_idx[PUB_MAX];
+	const int tid = threadIdx.x;
+	Intv3 *tmp = tmp_all + (size_t)blockIdx.x * PUB_MAX;
+	for (int k = blockIdx.x; k < n_cases; k += gridDim.x) {
+		const i64 o = off[k]; const int n = (int)(off[k + 1] - o);
+		Intv3 *iv = iv_all + o;
+		for (int i = tid; i < n; i += blockDim.x) { iv[i].x0 = (u64)i; iv[i].x2 = 0; iv[i].info = (u64)keys[o + i].a; }
+		__syncthreads();
+		if (n > 0) publish_sort_blk(iv, n, tmp, (size_t)PUB_MAX, s_key, s_idx);      // (k_publish_blk skips a read without intervals)
+		__syncthreads();
+		for (int i = tid; i < n; i += blockDim.x) perm[o + i] = (i32)iv[i].x0;
+		if (tid == 0) status[k] = 0;
+		__syncthreads();
 	}
 }

@@ -113,6 +113,14 @@ template <class LT> DEVFN void dev_sort_regs_by_key(bwagpu_alnreg_t *a, int n, R
 	}
 }
 
+// dedup_read's two sorts (also bwagpu_debug_sort's entry, dev_debug.h): by end (bwamem.c:467) or, BEST, by score, rb, qb (bwamem.c:504); keys: the read's
+// key scratch, null for a read that came with fewer than DEDUP_KEYSORT_MIN regions
+template <bool BEST> DEVFN void dedup_sort_regs(bwagpu_alnreg_t *a, int n, RegKey *keys)
+{
+	if (BEST) { if (keys && n >= DEDUP_KEYSORT_MIN) dev_sort_regs_by_key(a, n, keys, false, KeyBestLess()); else dev_introsort(a, n, RegBestLess()); }
+	else { if (keys) dev_sort_regs_by_key(a, n, keys, true, KeyEndLess()); else dev_introsort(a, n, RegEndLess()); }
+}
+
 __device__ void dedup_read(const DevIndex &ix, const bwagpu_opt_t &opt, const Batch &B, int r, i32 *H, i32 *E, u64 &calls, u64 &cells)
 {
 	int n = B.reg_n_raw[r];
@@ -123,7 +131,7 @@ __device__ void dedup_read(const DevIndex &ix, const bwagpu_opt_t &opt, const Ba
 		int m;
 		RegKey *keys = n >= DEDUP_KEYSORT_MIN ? (RegKey*)region_of(B.slot_blob, B.seed_off[r], B.seed_n[r]).chain : nullptr;
 		static_assert(sizeof(RegKey) <= sizeof(ChainRec), "a key record per seed slot must fit the chaining scratch");
-		if (keys) dev_sort_regs_by_key(a, n, keys, true, KeyEndLess()); else dev_introsort(a, n, RegEndLess());
+		dedup_sort_regs<false>(a, n, keys);
 		for (int i = 0; i < n; ++i) a[i].n_comp = 1;
 		for (int i = 1; i < n; ++i) {
 			bwagpu_alnreg_t &p = a[i];
@@ -154,7 +162,7 @@ __device__ void dedup_read(const DevIndex &ix, const bwagpu_opt_t &opt, const Ba
 		m = 0;
 		for (int i = 0; i < n; ++i) if (a[i].qe > a[i].qb) { if (m != i) a[m] = a[i]; ++m; }
 		n = m;
-		if (keys && n >= DEDUP_KEYSORT_MIN) dev_sort_regs_by_key(a, n, keys, false, KeyBestLess()); else dev_introsort(a, n, RegBestLess());
+		dedup_sort_regs<true>(a, n, keys);
 		for (int i = 1; i < n; ++i)
 			if (a[i].score == a[i - 1].score && a[i].rb == a[i - 1].rb && a[i].qb == a[i - 1].qb) a[i].qe = a[i].qb;
 		m = n > 0 ? 1 : 0;

@@ -18,6 +18,7 @@
 // At the end the kept records are gathered in their final order into the wave's staging area and copied back over the read's records.
 #pragma once
 
+#define DEDUP_NET_DEFAULT 129     // option dedup_net's default: regions from which a read's sorts are finished by the network (Batch::dd_net)
 struct DdHot { i64 rb, re; i32 qb, qe, rid, score; };     // what the decisions read
 // What the sorts move: 16 bytes, the order in the upper 96 bits, the region's index below (not compared: equal keys must stay equal, their order is
 // ks_introsort's).  By end (bwamem.c:467): hi = re.  By score, rb, qb (bwamem.c:504): hi = ~score : rb[47:16], lo = rb[15:0] : qb : index -- which needs
@@ -93,6 +94,23 @@ template <bool BEST> DEVFN void ddp_bitonic(DdKey *keys, int n, int N, i32 *out,
 	for (int x = lane; x < n; x += 64) out[x] = (int)(BEST ? (u32)keys[x].lo & 0xffffu : (u32)keys[x].lo);
 }
 
+// a coordinate outside DdKey's fields: the read is not for dedup_read_par
+DEVFN bool ddp_odd(const DdHot &h) { return h.rb < 0 || h.rb >= ((i64)1 << 48) || h.qb < 0 || h.qb >= (1 << 16); }
+
+// One of dedup_read_par's two sorts as a whole (also bwagpu_debug_sort's entry, dev_debug.h): keys[0 .. n) in LDS -> out[place] = index.  Lane 0's quicksort
+// passes, then the stable finish by counting or -- from dd_net elements on, where the LDS behind keys[] holds the network's cap_n >= N elements (and,
+// BEST, the place fits its 16 bits) -- by the network.  (The caller puts a wave_sync behind it.)
+template <bool BEST> DEVFN void ddp_order(DdKey *keys, int n, i32 *out, int dd_net, int cap_n, int lane)
+{
+	if (lane == 0) {
+		if (BEST) dev_introsort<DdKey, DdKeyLessBest, false>(keys, n, DdKeyLessBest());
+		else dev_introsort<DdKey, DdKeyLessEnd, false>(keys, n, DdKeyLessEnd());
+	}
+	wave_sync();
+	int N = 16; while (N < n) N <<= 1;
+	if (dd_net > 0 && n >= dd_net && N <= cap_n && (!BEST || n < 65536)) ddp_bitonic<BEST>(keys, n, N, out, lane); else ddp_rank<BEST>(keys, n, out, lane);
+}
+
 // mem_patch_reg's tests ahead of its alignment (bwamem.c:436-445), for a lane's own pair
 DEVFN bool ddp_patch_may(const DevIndex &ix, const bwagpu_opt_t &opt, const DdHot &a, const DdHot &b)
 {
@@ -129,19 +147,14 @@ template <bool BLK> __device__ bool dedup_read_par(const DevIndex &ix, const bwa
 		DdHot h_; h_.rb = g.rb; h_.re = g.re; h_.qb = g.qb; h_.qe = g.qe; h_.rid = g.rid; h_.score = g.score;
 		hot[i] = h_;
 		keys[i] = ddp_key_end(h_, i);
-		odd |= h_.rb < 0 || h_.rb >= ((i64)1 << 48) || h_.qb < 0 || h_.qb >= (1 << 16);
+		odd |= ddp_odd(h_);
 	}
 	if (wave_ballot(odd)) { wave_sync(); return false; }   // ... then in place, with the full-width keys
 	for (int i = lane; i < n; i += 64) ga[i].n_comp = 1;   // bwamem.c:468
 	wave_sync();
 	// ---- by end position (bwamem.c:467)
-	if (lane == 0) dev_introsort<DdKey, DdKeyLessEnd, false>(keys, n, DdKeyLessEnd());
-	wave_sync();
 	const int cap_n = L.par_cap + L.par_cap / 2;          // elements of 16 bytes the LDS from keys[] on holds (keys, ord, ord2)
-	{
-		int N = 16; while (N < n) N <<= 1;
-		if (B.dd_net > 0 && n >= B.dd_net && N <= cap_n) ddp_bitonic<false>(keys, n, N, ord, lane); else ddp_rank<false>(keys, n, ord, lane);
-	}
+	ddp_order<false>(keys, n, ord, B.dd_net, cap_n, lane);
 	wave_sync();
 	// ---- the redundancy scan (bwamem.c:470-497)
 	const float mlr = opt.mask_level_redun; const int gap = opt.max_chain_gap;
@@ -218,12 +231,7 @@ template <bool BLK> __device__ bool dedup_read_par(const DevIndex &ix, const bwa
 		m += __popcll(km);
 	}
 	wave_sync();
-	if (lane == 0) dev_introsort<DdKey, DdKeyLessBest, false>(keys, m, DdKeyLessBest());
-	wave_sync();
-	{
-		int N = 16; while (N < m) N <<= 1;
-		if (B.dd_net > 0 && m >= B.dd_net && N <= cap_n && m < 65536) ddp_bitonic<true>(keys, m, N, ord, lane); else ddp_rank<true>(keys, m, ord, lane);
-	}
+	ddp_order<true>(keys, m, ord, B.dd_net, cap_n, lane);
 	wave_sync();
 	// ---- identical hits (bwamem.c:505-513): every region that equals the one before it goes
 	int nf = 0;

@@ -89,6 +89,8 @@ __device__ ExtRes dev_ksw_extend2(const DevIndex &ix, const bwagpu_opt_t &opt, i
 }
 
 struct U64Less { DEVFN bool operator()(const u64 &a, const u64 &b) const { return a < b; } };
+// what mem_chain2aln sorts a chain's seeds by (bwamem.c:684): score << 32 | index
+DEVFN u64 seed_order_key(const bwagpu_seed_t &s, int i) { return (u64)s.score << 32 | (u32)i; }
 
 DEVFN int opt_mat_max(const bwagpu_opt_t &opt)
 {
@@ -140,7 +142,7 @@ __device__ void ext_read(const DevIndex &ix, const bwagpu_opt_t &opt, const Batc
 			if (rmax1 > fe) rmax1 = fe;
 		}
 		n_refb += (u64)(rmax1 - rmax0);
-		for (int i = 0; i < n; ++i) srt[i] = (u64)seeds[i].score << 32 | (u32)i;
+		for (int i = 0; i < n; ++i) srt[i] = seed_order_key(seeds[i], i);
 		dev_introsort(srt, n, U64Less());
 		for (int k = n - 1; k >= 0; --k) {
 			bwagpu_seed_t s = seeds[(u32)srt[k]];

@@ -791,17 +791,18 @@ DEVFN void chain_window_wave(const DevIndex &ix, const bwagpu_opt_t &opt, int l_
 	rmax0_ = uni64(rmax0); rmax1_ = uni64(rmax1);
 }
 // the seeds by score: keys score << 32 | index are distinct, so the order is the keys' own whatever sorts them
+#define CHAIN_SORT_LANE_MAX 32
 DEVFN void chain_sort_wave(const bwagpu_seed_t *seeds, u64 *srt, int n)
 {
 	const int lane = opaque_lane();
-	if (n <= 32) {
+	if (n <= CHAIN_SORT_LANE_MAX) {
 		if (lane == 0) {
-			for (int i = 0; i < n; ++i) srt[i] = (u64)seeds[i].score << 32 | (u32)i;
+			for (int i = 0; i < n; ++i) srt[i] = seed_order_key(seeds[i], i);
 			dev_introsort(srt, n, U64Less());
 		}
 		wave_sync();
 	} else {
-		for (int i = lane; i < n; i += 64) srt[i] = (u64)seeds[i].score << 32 | (u32)i;
+		for (int i = lane; i < n; i += 64) srt[i] = seed_order_key(seeds[i], i);
 		wave_sync();
 		wave_sort_u64(srt, n);
 	}

@@ -333,6 +333,33 @@ __global__ void __launch_bounds__(256) k_publish(bwagpu_opt_t opt, Batch B)
 // takes the serial path inside this kernel.  (Round 3 launched it with one workgroup per 256 lanes of the lane-per-read seeding kernel -- 24 workgroups
 // for a 6000-read batch, 48 ms; it needs 96 KB of scratch per workgroup, not a seeding block's 80 MB: up to 2048 workgroups now.)
 #define PUB_MAX 4096
+// k_publish_blk's sort of a read's n >= 1 intervals by the workgroup (also bwagpu_debug_sort's entry, dev_debug.h): s_key / s_idx are the block's
+// PUB_MAX-element LDS arrays, tmp its tmp_recs records of HBM.  (The caller puts a __syncthreads behind it.)
+DEVFN void publish_sort_blk(Intv3 *iv, int n, Intv3 *tmp, size_t tmp_recs, u64 *s_key, unsigned short *s_idx)
+{
+	const int tid = threadIdx.x;
+	if (n > PUB_MAX || (size_t)n > tmp_recs) { if (tid == 0) dev_introsort(iv, n, IntvInfoLess()); }
+	else if (n > 1) {
+		int N = 2; while (N < n) N <<= 1;
+		for (int i = tid; i < N; i += blockDim.x) { s_key[i] = i < n ? iv[i].info : ~0ull; s_idx[i] = (unsigned short)i; }
+		__syncthreads();
+		for (int k = 2; k <= N; k <<= 1)
+			for (int j = k >> 1; j > 0; j >>= 1) {
+				for (int i = tid; i < N; i += blockDim.x) {
+					const int p = i ^ j;
+					if (p > i) {
+						const u64 a = s_key[i], b = s_key[p];
+						const bool up = (i & k) == 0;
+						if (up ? a > b : a < b) { s_key[i] = b; s_key[p] = a; const unsigned short t = s_idx[i]; s_idx[i] = s_idx[p]; s_idx[p] = t; }
+					}
+				}
+				__syncthreads();
+			}
+		for (int i = tid; i < n; i += blockDim.x) tmp[i] = iv[s_idx[i]];
+		__syncthreads();
+		for (int i = tid; i < n; i += blockDim.x) iv[i] = tmp[i];
+	}
+}
 __global__ void __launch_bounds__(256) k_publish_blk(bwagpu_opt_t opt, Batch B)
 {
 	__shared__ u64 s_key[PUB_MAX];
@@ -350,27 +377,7 @@ __global__ void __launch_bounds__(256) k_publish_blk(bwagpu_opt_t opt, Batch B)
 		if (tid == 0) { B.intv_off[r] = (i64)r * B.mem_cap; B.seed_n[r] = 0; B.seed_off[r] = 0; B.node_off[r] = 0; if (n == 0) B.intv_n[r] = 0; }
 		if (n == 0) continue;                      // (uniform over the block)
 		Intv3 *iv = B.intv + (size_t)r * B.mem_cap;
-		if (n > PUB_MAX || (size_t)n > tmp_recs) { if (tid == 0) dev_introsort(iv, n, IntvInfoLess()); }
-		else if (n > 1) {
-			int N = 2; while (N < n) N <<= 1;
-			for (int i = tid; i < N; i += blockDim.x) { s_key[i] = i < n ? iv[i].info : ~0ull; s_idx[i] = (unsigned short)i; }
-			__syncthreads();
-			for (int k = 2; k <= N; k <<= 1)
-				for (int j = k >> 1; j > 0; j >>= 1) {
-					for (int i = tid; i < N; i += blockDim.x) {
-						const int p = i ^ j;
-						if (p > i) {
-							const u64 a = s_key[i], b = s_key[p];
-							const bool up = (i & k) == 0;
-							if (up ? a > b : a < b) { s_key[i] = b; s_key[p] = a; const unsigned short t = s_idx[i]; s_idx[i] = s_idx[p]; s_idx[p] = t; }
-						}
-					}
-					__syncthreads();
-				}
-			for (int i = tid; i < n; i += blockDim.x) tmp[i] = iv[s_idx[i]];
-			__syncthreads();
-			for (int i = tid; i < n; i += blockDim.x) iv[i] = tmp[i];
-		}
+		publish_sort_blk(iv, n, tmp, tmp_recs, s_key, s_idx);
 		__syncthreads();
 		// SA rows per interval (mem_chain's k-loop bounds, bwamem.c:304-305): block-wide sum, then one reservation
 		u32 mine = 0;

@@ -113,6 +113,26 @@ KswResult ksw_align2(int qlen, const uint8_t *query, int tlen, const uint8_t *ta
 int sort_dedup_nopatch(const bwagpu_opt_t &opt, Regs &a);           // mem_sort_dedup_patch with bns == 0 (bwamem_pair.c:201)
 
 template <class T, class LT> void introsort(T *a, long n, LT lt);   // ks_introsort (ksort.h:176-226), defined in host_sort.h
+// what the host code sorts by (here so that bwamem_host_debug_sort, host_api.cpp, runs the very comparators the stages use)
+struct HashLess {    // alnreg_hlt (bwamem.c:423)
+	bool operator()(const bwagpu_alnreg_t &a, const bwagpu_alnreg_t &b) const {
+		return a.score > b.score || (a.score == b.score && (a.is_alt < b.is_alt || (a.is_alt == b.is_alt && a.hash < b.hash)));
+	}
+};
+struct HashLess2 {   // alnreg_hlt2 (bwamem.c:426)
+	bool operator()(const bwagpu_alnreg_t &a, const bwagpu_alnreg_t &b) const {
+		return a.is_alt < b.is_alt || (a.is_alt == b.is_alt && (a.score > b.score || (a.score == b.score && a.hash < b.hash)));
+	}
+};
+struct U64Less { bool operator()(uint64_t a, uint64_t b) const { return a < b; } };
+struct Pair64 { uint64_t x, y; };
+struct Pair64Less { bool operator()(const Pair64 &a, const Pair64 &b) const { return a.x < b.x || (a.x == b.x && a.y < b.y); } };   // utils.c:44
+struct RegEndLess { bool operator()(const bwagpu_alnreg_t &a, const bwagpu_alnreg_t &b) const { return a.re < b.re; } };           // bwamem.c:417
+struct RegBestLess {                                                                                                                // bwamem.c:420
+	bool operator()(const bwagpu_alnreg_t &a, const bwagpu_alnreg_t &b) const {
+		return a.score > b.score || (a.score == b.score && (a.rb < b.rb || (a.rb == b.rb && a.qb < b.qb)));
+	}
+};
 
 bool load_refseqs(const std::string &prefix, RefSeqs &out, std::string &err);
 

@@ -7,6 +7,7 @@
 #include <atomic>
 #include <thread>
 #include "bwamem_host.h"
+#include "host_sort.h"
 
 namespace hostmem {
 
@@ -211,6 +212,48 @@ void bwamem_host_ksw_align2(int qlen, const uint8_t *query, int tlen, const uint
 {
 	KswResult r = ksw_align2(qlen, query, tlen, target, mat, o_del, e_del, o_ins, e_ins, xtra);
 	out[0] = r.score; out[1] = r.te; out[2] = r.qe; out[3] = r.score2; out[4] = r.te2; out[5] = r.tb; out[6] = r.qb;
+}
+
+// hostmem::introsort (host_sort.h) with each of the host stages' comparators on caller-supplied keys; the tests compare it with the reference's
+// ks_introsort_*.  Case k is keys[off[k] .. off[k + 1]) of {int64 a; int32 b, c}.  sorted[] receives the keys in sorted order; perm[off[k] + place] the
+// element's index within its case for the kinds that sort regions (kinds 2 and 3 sort bare numbers, whose equal elements cannot be told apart: perm is -1).
+// kind 0: HashLess and 1: HashLess2 (score = b, is_alt = c, hash = a), 2: U64Less (a), 3: Pair64Less (x = a, y = b : c), 4: RegEndLess (re = a),
+// 5: RegBestLess (score = b, rb = a, qb = c).  Returns 0, or -1 for an unknown kind.
+struct HostSortKey { int64_t a; int32_t b, c; };
+int bwamem_host_debug_sort(int kind, int n_cases, const HostSortKey *keys, const int64_t *off, HostSortKey *sorted, int32_t *perm)
+{
+	if (kind < 0 || kind > 5) return -1;
+	std::vector<bwagpu_alnreg_t> regs; std::vector<Pair64> pairs; std::vector<uint64_t> u;
+	for (int k = 0; k < n_cases; ++k) {
+		const HostSortKey *kk = keys + off[k]; HostSortKey *so = sorted + off[k]; int32_t *pm = perm + off[k];
+		const long n = (long)(off[k + 1] - off[k]);
+		if (kind == 2) {
+			u.resize(n);
+			for (long i = 0; i < n; ++i) u[i] = (uint64_t)kk[i].a;
+			introsort(u.data(), n, U64Less());
+			for (long i = 0; i < n; ++i) { so[i].a = (int64_t)u[i]; so[i].b = so[i].c = 0; pm[i] = -1; }
+		} else if (kind == 3) {
+			pairs.resize(n);
+			for (long i = 0; i < n; ++i) { pairs[i].x = (uint64_t)kk[i].a; pairs[i].y = (uint64_t)(uint32_t)kk[i].b << 32 | (uint32_t)kk[i].c; }
+			introsort(pairs.data(), n, Pair64Less());
+			for (long i = 0; i < n; ++i) { so[i].a = (int64_t)pairs[i].x; so[i].b = (int32_t)(pairs[i].y >> 32); so[i].c = (int32_t)(uint32_t)pairs[i].y; pm[i] = -1; }
+		} else {
+			regs.resize(n);
+			for (long i = 0; i < n; ++i) {
+				bwagpu_alnreg_t g; memset(&g, 0, sizeof g);
+				g.seedlen0 = (int)i; g.score = kk[i].b;
+				if (kind <= 1) { g.is_alt = kk[i].c & 1; g.hash = (uint64_t)kk[i].a; }
+				else { g.rb = g.re = kk[i].a; g.qb = kk[i].c; }
+				regs[i] = g;
+			}
+			if (kind == 0) introsort(regs.data(), n, HashLess());
+			else if (kind == 1) introsort(regs.data(), n, HashLess2());
+			else if (kind == 4) introsort(regs.data(), n, RegEndLess());
+			else introsort(regs.data(), n, RegBestLess());
+			for (long i = 0; i < n; ++i) { pm[i] = regs[i].seedlen0; so[i] = kk[pm[i]]; }
+		}
+	}
+	return 0;
 }
 
 }  // extern "C"

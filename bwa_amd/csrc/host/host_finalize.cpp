@@ -67,17 +67,6 @@ static void mark_core(const bwagpu_opt_t &opt, int n, bwagpu_alnreg_t *a, std::v
 	}
 }
 
-struct HashLess {    // alnreg_hlt (bwamem.c:423)
-	bool operator()(const bwagpu_alnreg_t &a, const bwagpu_alnreg_t &b) const {
-		return a.score > b.score || (a.score == b.score && (a.is_alt < b.is_alt || (a.is_alt == b.is_alt && a.hash < b.hash)));
-	}
-};
-struct HashLess2 {   // alnreg_hlt2 (bwamem.c:426)
-	bool operator()(const bwagpu_alnreg_t &a, const bwagpu_alnreg_t &b) const {
-		return a.is_alt < b.is_alt || (a.is_alt == b.is_alt && (a.score > b.score || (a.score == b.score && a.hash < b.hash)));
-	}
-};
-
 int mark_primary_se(const bwagpu_opt_t &opt, Regs &av, int64_t id)
 {
 	int n = (int)av.size(), n_pri = 0;

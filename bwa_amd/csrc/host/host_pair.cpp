@@ -41,8 +41,6 @@ template <class R> static int cal_sub(const bwagpu_opt_t &opt, const R &r)
 	return j < r.size() ? r[j].score : opt.min_seed_len * opt.a;
 }
 
-struct U64Less { bool operator()(uint64_t a, uint64_t b) const { return a < b; } };
-
 // The insert sizes of a batch's uniquely placed pairs, per orientation (the filter of bwamem_pair.c:79-91).  The pairs are independent,
 // so the batch is cut into one contiguous range per thread and the ranges' lists are concatenated; everything downstream sorts the
 // lists first, so their order is immaterial.
@@ -124,13 +122,6 @@ void pestat_flat(const bwagpu_opt_t &opt, int64_t l_pac, int n, const bwagpu_aln
 }
 
 // ---- mem_sort_dedup_patch with bns == 0: no patching, only redundancy removal and the final sort (bwamem.c:463-515) ----
-struct RegEndLess { bool operator()(const bwagpu_alnreg_t &a, const bwagpu_alnreg_t &b) const { return a.re < b.re; } };
-struct RegBestLess {
-	bool operator()(const bwagpu_alnreg_t &a, const bwagpu_alnreg_t &b) const {
-		return a.score > b.score || (a.score == b.score && (a.rb < b.rb || (a.rb == b.rb && a.qb < b.qb)));
-	}
-};
-
 int sort_dedup_nopatch(const bwagpu_opt_t &opt, Regs &av)
 {
 	int n = (int)av.size(), m;
@@ -277,9 +268,6 @@ int64_t host_matesw_records(const bwagpu_opt_t &opt, const RefSeqs &ref, int n, 
 }
 
 // ---- pairing (mem_pair, bwamem_pair.c:208-274) --------------------------------------------------------------------------------
-struct Pair64 { uint64_t x, y; };
-struct Pair64Less { bool operator()(const Pair64 &a, const Pair64 &b) const { return a.x < b.x || (a.x == b.x && a.y < b.y); } };   // utils.c:44
-
 static int pair_ends(const bwagpu_opt_t &opt, const RefSeqs &ref, const Pestat pes[4], const Regs a[2], int id, int *sub, int *n_sub, int z[2], const int n_pri[2])
 {
 	thread_local std::vector<Pair64> v, u;      // (scratch kept from pair to pair)

@@ -241,6 +241,25 @@ typedef struct {
  * in an LDS ring, direction bytes in HBM, tiled traceback) -> {score, n_ops, up to 70 ops...} (n_ops may exceed 70: the first 70 are returned).  opt supplies the scoring (mat, gap costs, zdrop). */
 int bwagpu_debug_dp(bwagpu_t *h, const bwagpu_opt_t *opt, int kind, int n_cases, const bwagpu_dp_case_t *cases, const uint8_t *seqs, int64_t n_seq_bytes, int32_t *out);
 
+/* ---- differential tests of the device sorts ------------------------------------------------------------------------------ */
+/* One element of a bwagpu_debug_sort case: a = the 64-bit part of the key (a region's end or start, an interval's info), b = score or weight,
+ * c = query start.  A kind reads the fields its order is made of. */
+typedef struct { int64_t a; int32_t b, c; } bwagpu_sort_key_t;
+/* Runs one of the device's restatements of klib's ks_introsort (ksort.h:176-226) on n_cases cases -- case k is keys[off[k] .. off[k + 1]), off[0] = 0 --
+ * where and as the product runs it, and returns per case the permutation it produced (perm[off[k] + place] = index of the element within its case;
+ * -1 where nothing was written) and status[k]: 0 sorted, 1 the routine declined the case (dedup_read_par: a coordinate outside its packed keys),
+ * -2 outside the entry's limits (kinds 7, 8: more than par_cap elements).
+ * kind 0: one lane's introsort of b << 32 | index (mem_chain2aln's seed order, bwamem.c:684); 1: the same order by the wave-per-read kernel's routine (one
+ * lane up to 32 seeds, a wave-wide network above); 2: k_publish's sort of intervals by a (bwamem.c:187); 3: k_publish_blk's (workgroup network up to 4096
+ * intervals, one lane above); 4: chains by weight b, heaviest first (bwamem.c:367), pairs in LDS or HBM by size and chain_flt_lds; 5 / 6: regions by end a
+ * (bwamem.c:467) / by (b descending, a, c) (bwamem.c:504) as the lane-per-read kernel sorts them; 7 / 8: the same two orders as dedup_read_par sorts them,
+ * with its switches: dd_net (elements from which a network finishes the sort; 0: never) and par_cap (2 .. 1100: the elements its LDS arrays hold). */
+/* The sizes at which the forms above change their method, as compiled: out[0] intervals up to which k_publish_blk sorts by its network, [1] chains whose
+ * weight pairs fit the LDS area, [2] the largest chain_flt_lds, [3] regions from which the lane-per-read kernel sorts key records, [4] the largest par_cap,
+ * [5] seeds up to which chain_sort_wave sorts on one lane, [6] the default of option dedup_net (dd_net), [7] 0. */
+void bwagpu_debug_sort_limits(int32_t out[8]);
+int bwagpu_debug_sort(bwagpu_t *h, int kind, int n_cases, const bwagpu_sort_key_t *keys, const int64_t *off, int dd_net, int par_cap, int chain_flt_lds, int32_t *perm, int32_t *status);
+
 /* ---- optional widening past mem_process_seqs' first loop ---- */
 /* After bwagpu_batch_download: one bwagpu_cigar_t per downloaded region, in the same order, computed on the device.  They
  * are what worker2's mem_reg2aln (bwamem.c:1119-1152) would compute on the host for that region; a finalize stage can use

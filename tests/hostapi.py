@@ -37,8 +37,18 @@ def lib():
         L.bwamem_host_free.argtypes = [C.c_void_p]
         L.bwamem_host_region_cigars.restype = C.c_int64
         L.bwamem_host_region_cigars.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
+        L.bwamem_host_debug_sort.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         _lib = L
     return _lib
+
+
+def debug_sort(kind, keys, off):
+    """bwamem_host_debug_sort: hostmem::introsort with the kind's comparator on every case -> (sorted keys, perm; perm is -1 for the kinds that sort bare numbers)."""
+    keys = np.ascontiguousarray(keys); off = np.ascontiguousarray(off, dtype=np.int64)
+    assert keys.dtype.itemsize == 16 and int(off[-1]) == keys.shape[0]
+    out = np.zeros_like(keys); perm = np.full(keys.shape[0], -2, dtype=np.int32)
+    assert lib().bwamem_host_debug_sort(kind, off.shape[0] - 1, keys.ctypes.data, off.ctypes.data, out.ctypes.data, perm.ctypes.data) == 0
+    return out, perm
 
 
 class HostFinalize:

@@ -46,8 +46,33 @@ def lib():
         L.refshim_sizes(sz)
         assert sz[0] == C.sizeof(MemOpt) and sz[1] == ALNREG_DTYPE.itemsize and sz[2] == INTV_DTYPE.itemsize
         assert sz[3] == SEED_DTYPE.itemsize and sz[11] == CHAIN_HDR_DTYPE.itemsize and sz[6] == C.sizeof(MemPestat)
+        # KSORT_INIT's functions are not static: the reference's own instances of ks_introsort (ksort.h:176-226), each (n, array)
+        for f in ("ks_introsort_64", "ks_introsort_128", "ks_introsort_mem_intv", "ks_introsort_mem_flt", "ks_introsort_mem_ars2", "ks_introsort_mem_ars",
+                  "ks_introsort_mem_ars_hash", "ks_introsort_mem_ars_hash2"):
+            getattr(L, f).restype = None
+            getattr(L, f).argtypes = [C.c_size_t, C.c_void_p]
+        assert sz[4] == C.sizeof(RefChain) and sz[2] == C.sizeof(RefIntv)      # (pair64_t is two uint64_t, utils.h:50-52: no padding to get wrong)
         _lib = L
     return _lib
+
+
+class RefChain(C.Structure):      # mem_chain_t (bwamem.c:200-206)
+    _fields_ = [("n", C.c_int), ("m", C.c_int), ("first", C.c_int), ("rid", C.c_int), ("w", C.c_uint32, 29), ("kept", C.c_uint32, 2), ("is_alt", C.c_uint32, 1),
+                ("frac_rep", C.c_float), ("pos", C.c_int64), ("seeds", C.c_void_p)]
+
+
+class RefIntv(C.Structure):       # bwtintv_t (bwt.h:48-51)
+    _fields_ = [("x", C.c_uint64 * 3), ("info", C.c_uint64)]
+
+
+class RefPair64(C.Structure):     # pair64_t (utils.h:50-52)
+    _fields_ = [("x", C.c_uint64), ("y", C.c_uint64)]
+
+
+# the same layouts for numpy (wbits: w in bits 0..28, kept 29..30, is_alt 31 -- checked against the ctypes bit-fields in test_sort_fuzz.py)
+REF_CHAIN_DTYPE = np.dtype([("n", "<i4"), ("m", "<i4"), ("first", "<i4"), ("rid", "<i4"), ("wbits", "<u4"), ("frac_rep", "<f4"), ("pos", "<i8"), ("seeds", "<u8")])
+REF_PAIR64_DTYPE = np.dtype([("x", "<u8"), ("y", "<u8")])
+assert REF_CHAIN_DTYPE.itemsize == C.sizeof(RefChain) == 40 and REF_PAIR64_DTYPE.itemsize == C.sizeof(RefPair64) == 16 and C.sizeof(RefIntv) == INTV_DTYPE.itemsize
 
 
 def build_index(fasta: str) -> str:

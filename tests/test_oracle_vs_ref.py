@@ -131,3 +131,36 @@ def test_ksw_global2_fuzz():
         b = O.orc_ksw_global2(*base, C.byref(no), C.byref(co))
         assert a == b and nr.value == no.value and [cr[i] for i in range(nr.value)] == [co[i] for i in range(no.value)], f"case {it}"
         assert a == R.ksw_global2(*base, None, None) == O.orc_ksw_global2(*base, None, None)
+
+
+def test_introsort_fuzz():
+    """orc_introsort (orc_sort.c), the sort every parity test's expected values go through, against the reference's own ks_introsort (the instance for regions
+    by end, bwamem.c:417-418): exact equality of the permutations, ties included -- over the cases of tests/sortcases.py, whose depth-limit family runs
+    the quicksort out of its budget so that the comb sort is entered (uniformly random keys never do that)."""
+    import orcapi
+    import sortcases as sc
+    from bwa_amd.structs import ALNREG_DTYPE
+    R, O = refapi.lib(), orcapi.lib()
+    LT = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p)
+    i64 = C.c_int64.from_address
+    lt = LT(lambda a, b: i64(a).value < i64(b).value)
+    O.orc_introsort.restype = None
+    O.orc_introsort.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, LT]
+    recs = sc.build("end", 400, extra_sizes=(4097,), extra_depth=(4096,))
+    fams, comb, rule11, ties = {}, 0, 0, 0
+    for i, (case, k) in enumerate(recs):
+        n = k.shape[0]
+        a = np.zeros(n, dtype=ALNREG_DTYPE)
+        a["re"] = k["a"]; a["seedlen0"] = np.arange(n)
+        R.ks_introsort_mem_ars2(n, a.ctypes.data)
+        b = np.zeros((n, 2), dtype=np.int64)
+        b[:, 0] = k["a"]; b[:, 1] = np.arange(n)
+        O.orc_introsort(b.ctypes.data, n, 16, lt)
+        assert np.array_equal(b[:, 1], a["seedlen0"]), f"case {i} ({case.family}, n = {n}): oracle {b[:, 1].tolist()} reference {a['seedlen0'].tolist()} keys {k['a'].tolist()}"
+        fams[case.family] = fams.get(case.family, 0) + 1
+        if case.stat:
+            assert case.stat["comb"] > 0
+            comb += 1; rule11 += case.stat["rule11"] > 0; ties += case.stat["ties_in_comb"] > 0
+    assert sum(fams.values()) == len(recs)
+    assert not [f for f in sc.FAMILIES + ("end_edges",) if not fams.get(f)], fams
+    assert comb == fams["depth"] + fams["depth_tied"] and rule11 > 0 and ties > 0
