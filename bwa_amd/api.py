@@ -16,7 +16,7 @@ try:   # torch bundles its own HIP runtime (libamdhip64); loading it first keeps
 except Exception:  # pragma: no cover
     torch = None
 
-from .structs import ALNREG_DTYPE, MemOpt
+from .structs import ALNREG_DTYPE, PRIMARY_DTYPE, MemOpt
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 DEFAULT_LIB = os.path.join(HERE, "csrc", "libbwagpu.so")
@@ -60,6 +60,7 @@ EXPORTS = [
     "bwagpu_free", "bwagpu_batch_upload", "bwagpu_batch_run", "bwagpu_batch_download", "bwagpu_set_taps", "bwagpu_tap_intervals",
     "bwagpu_tap_chains", "bwagpu_tap_regs_raw", "bwagpu_index_buffers", "bwagpu_index_export", "bwagpu_clone", "bwagpu_index_ready",
     "bwagpu_batch_cigars", "bwagpu_batch_cigar_ops", "bwagpu_debug_phase", "bwagpu_batch_matesw", "bwagpu_clone_to_device", "bwagpu_index_build", "bwagpu_built_free", "bwagpu_abi_sizes", "bwagpu_debug_prof", "bwagpu_debug_hist", "bwagpu_debug_seed_x2", "bwagpu_debug_chain_hist", "bwagpu_debug_dp", "bwagpu_debug_sort", "bwagpu_debug_sort_limits", "bwagpu_set_cigar_filter", "bwagpu_batch_reserve", "bwagpu_batch_footprint", "bwagpu_mem_info",
+    "bwagpu_batch_primary", "bwagpu_primary_flat", "bwagpu_primary_limits",
     "bwagpu_trim", "bwagpu_set_option", "bwagpu_get_option", "bwagpu_set_default_option", "bwagpu_clear_default_options", "bwagpu_option_name",
 ]
 
@@ -108,6 +109,9 @@ def load_library(path: str | None = None) -> C.CDLL:
     L.bwagpu_index_export.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.bwagpu_debug_dp.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
     L.bwagpu_debug_sort.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    L.bwagpu_batch_primary.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.bwagpu_primary_flat.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.bwagpu_primary_limits.restype = None
     L.bwagpu_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_longlong]
     L.bwagpu_get_option.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p]
     L.bwagpu_set_default_option.argtypes = [C.c_char_p, C.c_longlong]
@@ -268,6 +272,31 @@ class BwaGpu:
         p, n = C.c_void_p(), C.c_int64()
         self._chk(self.L.bwagpu_batch_matesw(self.h, C.byref(opt), pes.ctypes.data, C.byref(p), C.byref(n)))
         return self._take(p, n.value, MATESW_DTYPE)
+
+    def primary(self, opt: MemOpt, id0: int = 0):
+        """bwagpu_batch_primary: mem_mark_primary_se + mem_approx_mapq_se of every read of the last download() on the device; read i has id id0 + i.
+        -> (PRIMARY_DTYPE records, concatenated per read with the download's counts; n_pri int32[n reads]; device time of the kernels in ms)"""
+        p, n, ms = C.c_void_p(), C.c_int64(), C.c_float()
+        n_pri = np.zeros(self._n, dtype=np.int32)
+        self._chk(self.L.bwagpu_batch_primary(self.h, C.byref(opt), int(id0), C.byref(p), C.byref(n), n_pri.ctypes.data, C.byref(ms)))
+        return self._take(p, n.value, PRIMARY_DTYPE), n_pri, ms.value
+
+    def primary_flat(self, opt: MemOpt, counts: np.ndarray, regs: np.ndarray, ids: np.ndarray):
+        """bwagpu_primary_flat: the same kernels on region lists of the caller (read i: counts[i] records of regs, id ids[i]) -> (records, n_pri, ms)."""
+        counts = np.ascontiguousarray(counts, dtype=np.int32)
+        regs = np.ascontiguousarray(regs, dtype=ALNREG_DTYPE)
+        ids = np.ascontiguousarray(ids, dtype=np.int64)
+        assert counts.shape == ids.shape and int(counts.sum()) == regs.shape[0]
+        p, ms = C.c_void_p(), C.c_float()
+        n_pri = np.zeros(counts.shape[0], dtype=np.int32)
+        self._chk(self.L.bwagpu_primary_flat(self.h, C.byref(opt), counts.shape[0], counts.ctypes.data, regs.ctypes.data, ids.ctypes.data, C.byref(p), n_pri.ctypes.data, C.byref(ms)))
+        return self._take(p, regs.shape[0], PRIMARY_DTYPE), n_pri, ms.value
+
+    def primary_limits(self) -> dict:
+        """bwagpu_primary_limits: the region counts at which the marking kernels change their form, as compiled."""
+        out = (C.c_int32 * 4)()
+        self.L.bwagpu_primary_limits(out)
+        return dict(zip(("lane_max", "lds_small", "lds_big", "scan"), list(out)))
 
     def debug_dp(self, opt: MemOpt, kind: int, cases: np.ndarray, seqs: np.ndarray) -> np.ndarray:
         """bwagpu_debug_dp: one wavefront of a device DP routine per case (DP_CASE_DTYPE) -> int32[n_cases, 72]."""

@@ -37,6 +37,7 @@
 #include "dev_cigar.h"
 #include "dev_dedupw.h"
 #include "dev_matesw.h"
+#include "dev_primary.h"
 #include "dev_debug.h"
 
 #define BWAGPU_VERSION "bwagpu 0.1 (gfx950)"
@@ -89,6 +90,10 @@ struct bwagpu_s {
 	bwagpu_stats_t stats = {};
 	volatile int phase = 0;       // progress marker for bwagpu_debug_phase (diagnostics of a stuck call)
 	i64 packed_tot = -1;          // regions packed by the last bwagpu_batch_download (-1: none)
+	int packed_max = 0; bool downloaded = false;   // ... the largest count of a read among them; a download has happened for this run (a batch without reads packs nothing)
+	DevBuf d_pri_out, d_pri_npri, d_pri_lists, d_pri_ctr, d_pri_scratch, d_pri_log;      // bwagpu_batch_primary / bwagpu_primary_flat: records, return values, the wavefront forms' read lists and their lengths, HBM working arrays, the table of logarithms
+	DevBuf d_pf_regs, d_pf_cnt, d_pf_off, d_pf_ids;                                       // ... and the uploaded lists of bwagpu_primary_flat
+	std::vector<double> pri_log; i64 pri_log_dev = 0;                                      // log((double)k) by the host's libm for k < size; entries resident in d_pri_log
 	DevBuf d_msw_tasks, d_msw_out, d_msw_pes, d_msw_scratch;
 	i64 cigl_z_cap = 0;                          // bytes per direction matrix of the long CIGAR tier's scratch (grows with the batches)
 	DevBuf d_cigl_z, d_cigl_ops, d_cigl_md, d_cigl_list;      // scratch of the long-segment CIGAR tier (k_cigar_long): direction matrices, operations, MD strings per workgroup
@@ -230,7 +235,7 @@ static bool option_in_range(const BwagpuConfig &c, const long long *f, long long
 	if (f == &c.ext_occ) return value == 4 || value == 6;
 	if (f == &c.seed_mrg) return value == -1 || value == 0 || value == 2;
 	if (f == &c.share) return in(-1, 100);
-	if (f == &c.seed_task_stack || f == &c.seed_p2_cap || f == &c.mem_cap || f == &c.seed_grid || f == &c.cig_ops_cap || f == &c.idx_desc_max_mb) return in(0, 0x3fffffff);
+	if (f == &c.seed_task_stack || f == &c.seed_p2_cap || f == &c.mem_cap || f == &c.seed_grid || f == &c.cig_ops_cap || f == &c.idx_desc_max_mb || f == &c.pri_log_cap) return in(0, 0x3fffffff);
 	if (f == &c.seed_budget || f == &c.dedup_heavy) return in(-1, 0x3fffffff);
 	if (f == &c.dedup_stage || f == &c.dedup_big || f == &c.dedup_net) return in(-1, 1024);
 	if (f == &c.seed_lds_ent) return in(-1, 16);
@@ -493,7 +498,7 @@ extern "C" void bwagpu_destroy(bwagpu_t *h)
 		for (DevBuf *b : ib) b->release();
 		delete h->ibuf;
 	}
-	DevBuf *all[] = { &h->d_heavy, &h->d_dd_tmp, &h->d_p2_tasks, &h->d_vr_tab, &h->d_vr_ovf, &h->d_intv_n3, &h->d_cigl_list, &h->d_cigl_z, &h->d_cigl_ops, &h->d_cigl_md, &h->d_seq_2b, &h->d_seq_flags, &h->d_cig_ext, &h->d_msw_tasks, &h->d_msw_out, &h->d_msw_pes, &h->d_msw_scratch, &h->d_pack_off, &h->d_regs_packed, &h->d_pack_read, &h->d_cigs, &h->d_seq, &h->d_seq_nib, &h->d_off, &h->d_ctr, &h->d_tmp_intv,
+	DevBuf *all[] = { &h->d_pri_out, &h->d_pri_npri, &h->d_pri_lists, &h->d_pri_ctr, &h->d_pri_scratch, &h->d_pri_log, &h->d_pf_regs, &h->d_pf_cnt, &h->d_pf_off, &h->d_pf_ids, &h->d_heavy, &h->d_dd_tmp, &h->d_p2_tasks, &h->d_vr_tab, &h->d_vr_ovf, &h->d_intv_n3, &h->d_cigl_list, &h->d_cigl_z, &h->d_cigl_ops, &h->d_cigl_md, &h->d_seq_2b, &h->d_seq_flags, &h->d_cig_ext, &h->d_msw_tasks, &h->d_msw_out, &h->d_msw_pes, &h->d_msw_scratch, &h->d_pack_off, &h->d_regs_packed, &h->d_pack_read, &h->d_cigs, &h->d_seq, &h->d_seq_nib, &h->d_off, &h->d_ctr, &h->d_tmp_intv,
 		&h->d_intv_n, &h->d_intv_off, &h->d_intv, &h->d_seed_n, &h->d_seed_off, &h->d_slot_pos, &h->d_slot_qbeg, &h->d_slot_len, &h->d_slot_rid, &h->d_slot_blob, &h->d_chain_n, &h->d_node_off,
 		&h->d_order, &h->d_bin_cnt, &h->d_seed_w, &h->d_seed_order, &h->d_nodes, &h->d_reg_off, &h->d_reg_cap_r, &h->d_reg_n_raw, &h->d_reg_n, &h->d_regs, &h->d_regs_raw, &h->d_dp_h, &h->d_dp_e, &h->d_minhsp };
 	for (DevBuf *b : all) b->release();
@@ -825,7 +830,7 @@ extern "C" int bwagpu_batch_upload(bwagpu_t *h, int n, const uint8_t *seqs, cons
 {
 	if (!h || n < 0 || (n > 0 && (!seqs || !off))) return BWAGPU_EINVAL;
 	HIPCHK(h, hipSetDevice(h->device));
-	h->have_batch = false; h->ran = false; h->packed_tot = -1; h->cig_ext_n = -1; h->phase = 10;
+	h->have_batch = false; h->ran = false; h->packed_tot = -1; h->downloaded = false; h->cig_ext_n = -1; h->phase = 10;
 	h->n_reads = n; h->max_len = 0; h->n_bases = n ? off[n] - off[0] : 0;
 	if (n && off[0] != 0) return BWAGPU_EINVAL;
 	for (int i = 0; i < n; ++i) {
@@ -973,7 +978,7 @@ extern "C" int bwagpu_batch_run(bwagpu_t *h, const bwagpu_opt_t *opt)
 	HIPCHK(h, hipSetDevice(h->device));
 	memset(&h->stats, 0, sizeof h->stats);
 	h->stats.n_reads = h->n_reads; h->stats.n_bases = h->n_bases;
-	h->ran = false; h->packed_tot = -1; h->cig_ext_n = -1;      // regions packed by an earlier download (and their CIGAR operations) belong to the previous run
+	h->ran = false; h->packed_tot = -1; h->downloaded = false; h->cig_ext_n = -1;      // regions packed by an earlier download (and their CIGAR operations) belong to the previous run
 	if (h->n_reads == 0) { h->ran = true; return BWAGPU_OK; }
 	int n = h->n_reads;
 	// resident lanes: enough to fill the chip, bounded by the seeding scratch budget (2 interval stacks per lane)
@@ -1373,13 +1378,13 @@ extern "C" int bwagpu_batch_download(bwagpu_t *h, int32_t *counts, bwagpu_alnreg
 	HIPCHK(h, hipSetDevice(h->device));
 	const int n = h->n_reads;
 	h->cig_ext_n = -1;
-	if (n == 0) { *regs_out = (bwagpu_alnreg_t*)malloc(sizeof(bwagpu_alnreg_t)); *n_regs_out = 0; return BWAGPU_OK; }
+	if (n == 0) { *regs_out = (bwagpu_alnreg_t*)malloc(sizeof(bwagpu_alnreg_t)); *n_regs_out = 0; h->downloaded = true; h->packed_max = 0; return BWAGPU_OK; }
 	h->phase = 30;
 	std::vector<i32> cnt((size_t)n); std::vector<i64> dst((size_t)n);
 	HIPCHK(h, hipMemcpyAsync(cnt.data(), h->d_reg_n.p, (size_t)n * 4, hipMemcpyDeviceToHost, h->stream));
 	HIPCHK(h, wait_stream(h));
-	i64 tot = 0;
-	for (int i = 0; i < n; ++i) { dst[i] = tot; tot += cnt[i]; if (counts) counts[i] = cnt[i]; }
+	i64 tot = 0; int cnt_max = 0;
+	for (int i = 0; i < n; ++i) { dst[i] = tot; tot += cnt[i]; if (cnt[i] > cnt_max) cnt_max = cnt[i]; if (counts) counts[i] = cnt[i]; }
 	release_reserved(h);      // (the blocks bwagpu_batch_reserve page-locked for this handle go back to the pool, where the next lines find them)
 	bwagpu_alnreg_t *res = (bwagpu_alnreg_t*)result_alloc((size_t)(tot ? tot : 1) * sizeof(bwagpu_alnreg_t));
 	if (!res) return BWAGPU_ENOMEM;
@@ -1402,7 +1407,7 @@ extern "C" int bwagpu_batch_download(bwagpu_t *h, int32_t *counts, bwagpu_alnreg
 		if (e != hipSuccess) { bwagpu_free(res); HIPCHK(h, e); }
 		(void)hipEventElapsedTime(&h->stats.ms_pack, h->ev[0], h->ev[1]); (void)hipEventElapsedTime(&h->stats.ms_download_copy, h->ev[1], h->ev[2]);
 	}
-	h->packed_tot = tot; h->phase = 39;
+	h->packed_tot = tot; h->packed_max = cnt_max; h->downloaded = true; h->phase = 39;
 	*regs_out = res; *n_regs_out = tot;
 	return BWAGPU_OK;
 }
@@ -1589,6 +1594,158 @@ extern "C" int bwagpu_batch_matesw(bwagpu_t *h, const bwagpu_opt_t *opt, const b
 	}
 	*out = res; *n_out = (int64_t)nt;
 	return BWAGPU_OK;
+}
+
+// ---- primary/secondary marking + mapQ on the device (dev_primary.h) ---------------------------------------------------------------------------
+extern "C" void bwagpu_primary_limits(int32_t out[4]) { out[0] = PRI_LANE_MAX; out[1] = PRI_LDS_SMALL; out[2] = PRI_LDS_BIG; out[3] = PRI_SCAN; }
+
+static const i64 PRI_LOG_MAX = (i64)1 << 22;      // entries the table of logarithms is grown to at most (32 MB); arguments beyond it are the host's
+// The kernels of both entry points on n_reads lists (counts d_cnt, offsets d_off into d_regs; ids d_ids, or id0 + i): records to a result block (*out), return
+// values to n_pri.  max_cnt = the largest count (sizes the HBM form), log_need = the largest argument of a logarithm to expect; host_cnt / host_regs:
+// the lists on the host, or null -- they are then fetched from the device if a record comes back flagged.
+static int primary_run(bwagpu_t *h, const bwagpu_opt_t *opt, int n_reads, i64 tot, int max_cnt, i64 log_need, const i32 *d_cnt, const i64 *d_off, const bwagpu_alnreg_t *d_regs,
+					   const i64 *d_ids, i64 id0, const i32 *host_cnt, const bwagpu_alnreg_t *host_regs, bwagpu_primary_t **out, int32_t *n_pri, float *kernel_ms)
+{
+	if (kernel_ms) *kernel_ms = 0.f;
+	bwagpu_primary_t *res = (bwagpu_primary_t*)result_alloc((size_t)(tot ? tot : 1) * sizeof(bwagpu_primary_t));
+	if (!res) return BWAGPU_ENOMEM;
+	if (n_reads == 0) { *out = res; return BWAGPU_OK; }
+	// the table of logarithms: the host's log() of every integer a mapQ of this batch can ask for (option pri_log_cap: a table of exactly that many entries, for tests)
+	i64 log_n = log_need + 1 < 4096 ? 4096 : log_need + 1;
+	if (log_n > PRI_LOG_MAX) log_n = PRI_LOG_MAX;
+	if (h->cfg.pri_log_cap > 0) log_n = h->cfg.pri_log_cap < PRI_LOG_MAX ? h->cfg.pri_log_cap : PRI_LOG_MAX;
+	if ((i64)h->pri_log.size() < log_n) { const size_t was = h->pri_log.size(); h->pri_log.resize((size_t)log_n); for (size_t k = was; k < (size_t)log_n; ++k) h->pri_log[k] = log((double)k); }
+	const int n_hbm = max_cnt > PRI_LDS_BIG ? (n_reads < 64 ? n_reads : 64) : 0;      // workgroups of the HBM form
+	const void *log_was = h->d_pri_log.p;
+	if (h->d_pri_out.ensure((size_t)(tot ? tot : 1) * sizeof(bwagpu_primary_t)) || h->d_pri_npri.ensure((size_t)n_reads * 4) || h->d_pri_lists.ensure((size_t)n_reads * 3 * 4) ||
+		h->d_pri_ctr.ensure(4 * sizeof(unsigned int)) || h->d_pri_log.ensure((size_t)log_n * 8) || (n_hbm && h->d_pri_scratch.ensure((size_t)n_hbm * max_cnt * PRI_WORDS * 4))) {
+		bwagpu_free(res); h->err = "hipMalloc failed (primary)"; return BWAGPU_ENOMEM;
+	}
+	hipError_t e = hipSuccess;
+	if (h->pri_log_dev < log_n || h->d_pri_log.p != log_was) { /* (a buffer that had to grow is a new one) */ e = hipMemcpyAsync(h->d_pri_log.p, h->pri_log.data(), (size_t)log_n * 8, hipMemcpyHostToDevice, h->stream); h->pri_log_dev = log_n; }
+	if (e == hipSuccess) e = hipMemsetAsync(h->d_pri_ctr.p, 0, 4 * sizeof(unsigned int), h->stream);
+	const PriLogTab lg = { h->d_pri_log.as<double>(), (int)log_n };
+	bwagpu_primary_t *d_out = h->d_pri_out.as<bwagpu_primary_t>();
+	i32 *d_npri = h->d_pri_npri.as<i32>(), *lists = h->d_pri_lists.as<i32>();
+	unsigned int *list_n = h->d_pri_ctr.as<unsigned int>();
+	(void)hipEventRecord(h->ev[0], h->stream);
+	if (e == hipSuccess) {
+		int nb = (n_reads + PRI_LANE_BLOCK - 1) / PRI_LANE_BLOCK; if (nb > 256 * 12) nb = 256 * 12;
+		hipLaunchKernelGGL(k_primary_lane, dim3(nb), dim3(PRI_LANE_BLOCK), 0, h->stream, *opt, n_reads, d_cnt, d_off, d_regs, d_ids, id0, lg, d_out, d_npri, lists, list_n);
+		e = hipGetLastError();
+	}
+	// the wavefront forms draw their reads from the lists the first kernel left (their lengths stay on the device); a form no read of the batch can need is not launched
+	if (e == hipSuccess && max_cnt > PRI_LANE_MAX) {
+		const int nb = n_reads < 256 * 16 ? n_reads : 256 * 16;
+		hipLaunchKernelGGL(k_primary_wave<PRI_LDS_SMALL>, dim3(nb), dim3(64), 0, h->stream, *opt, d_cnt, d_off, d_regs, d_ids, id0, lg, d_out, d_npri, lists, list_n, (u64*)nullptr, 0);
+		e = hipGetLastError();
+	}
+	if (e == hipSuccess && max_cnt > PRI_LDS_SMALL) {
+		const int nb = n_reads < 256 * 3 ? n_reads : 256 * 3;
+		hipLaunchKernelGGL(k_primary_wave<PRI_LDS_BIG>, dim3(nb), dim3(64), 0, h->stream, *opt, d_cnt, d_off, d_regs, d_ids, id0, lg, d_out, d_npri, lists + n_reads, list_n + 1, (u64*)nullptr, 0);
+		e = hipGetLastError();
+	}
+	if (e == hipSuccess && n_hbm) {
+		hipLaunchKernelGGL(k_primary_wave<0>, dim3(n_hbm), dim3(64), 0, h->stream, *opt, d_cnt, d_off, d_regs, d_ids, id0, lg, d_out, d_npri, lists + (size_t)2 * n_reads, list_n + 2, h->d_pri_scratch.as<u64>(), max_cnt);
+		e = hipGetLastError();
+	}
+	(void)hipEventRecord(h->ev[1], h->stream);
+	std::vector<i32> np((size_t)n_reads);
+	if (e == hipSuccess && tot) e = hipMemcpyAsync(res, d_out, (size_t)tot * sizeof(bwagpu_primary_t), hipMemcpyDeviceToHost, h->stream);
+	if (e == hipSuccess) e = hipMemcpyAsync(np.data(), d_npri, (size_t)n_reads * 4, hipMemcpyDeviceToHost, h->stream);
+	if (e == hipSuccess) e = wait_stream(h);
+	if (e != hipSuccess) { bwagpu_free(res); HIPCHK(h, e); }
+	if (kernel_ms) (void)hipEventElapsedTime(kernel_ms, h->ev[0], h->ev[1]);
+	for (int i = 0; i < n_reads; ++i) if (np[i] < 0) { bwagpu_free(res); h->err = "internal: a read outgrew the marking kernel's working arrays"; return BWAGPU_EHIP; }
+	if (n_pri) memcpy(n_pri, np.data(), (size_t)n_reads * 4);
+	// records whose mapQ needed a logarithm outside the table: the same function with the host's log()
+	bool any = false;
+	for (i64 k = 0; k < tot && !any; ++k) any = (res[k].flags & 1) != 0;
+	if (any) {
+		std::vector<i32> cnt_; std::vector<bwagpu_alnreg_t> regs_;
+		if (!host_cnt) {
+			cnt_.resize((size_t)n_reads); regs_.resize((size_t)tot);
+			e = hipMemcpyAsync(cnt_.data(), d_cnt, (size_t)n_reads * 4, hipMemcpyDeviceToHost, h->stream);
+			if (e == hipSuccess) e = hipMemcpyAsync(regs_.data(), d_regs, (size_t)tot * sizeof(bwagpu_alnreg_t), hipMemcpyDeviceToHost, h->stream);
+			if (e == hipSuccess) e = wait_stream(h);
+			if (e != hipSuccess) { bwagpu_free(res); HIPCHK(h, e); }
+			host_cnt = cnt_.data(); host_regs = regs_.data();
+		}
+		i64 base = 0;
+		for (int i = 0; i < n_reads; ++i) {
+			for (int k = 0; k < host_cnt[i]; ++k) {
+				bwagpu_primary_t &r = res[base + k];
+				int miss = 0;
+				if (r.flags & 1) r.mapq = pri_mapq(*opt, host_regs[base + r.src], r.sub, r.sub_n, PriLogLibm(), miss);
+			}
+			base += host_cnt[i];
+		}
+	}
+	*out = res;
+	return BWAGPU_OK;
+}
+
+extern "C" int bwagpu_batch_primary(bwagpu_t *h, const bwagpu_opt_t *opt, int64_t id0, bwagpu_primary_t **out, int64_t *n_out, int32_t *n_pri, float *kernel_ms)
+{
+	if (!h || !opt || !h->ran || !h->downloaded || !out || !n_out) return BWAGPU_EINVAL;
+	const BusyGuard busy(h->ibuf->busy);
+	HIPCHK(h, hipSetDevice(h->device));
+	const i64 tot = h->packed_tot < 0 ? 0 : h->packed_tot;
+	// a logarithm's argument is at most the longer side of a region (the read, or the read and the gaps its band allows), its seed coverage (at most the read),
+	// or the read's number of regions plus one
+	i64 log_need = 2 * (i64)h->max_len + 4 * (i64)(opt->w > 0 ? opt->w : 0) + 64;
+	if (h->packed_max + 2 > log_need) log_need = h->packed_max + 2;
+	*out = nullptr; *n_out = 0;
+	if (tot == 0) {      // no region in the whole batch: nothing to run (and the packed arrays may not exist)
+		bwagpu_primary_t *res = (bwagpu_primary_t*)result_alloc(sizeof(bwagpu_primary_t));
+		if (!res) return BWAGPU_ENOMEM;
+		if (n_pri) for (int i = 0; i < h->n_reads; ++i) n_pri[i] = 0;
+		if (kernel_ms) *kernel_ms = 0.f;
+		*out = res;
+		return BWAGPU_OK;
+	}
+	const int rc = primary_run(h, opt, h->n_reads, tot, h->packed_max, log_need, h->d_reg_n.as<i32>(), h->d_pack_off.as<i64>(), h->d_regs_packed.as<bwagpu_alnreg_t>(), nullptr, id0,
+							   nullptr, nullptr, out, n_pri, kernel_ms);
+	if (rc == BWAGPU_OK) *n_out = tot;
+	return rc;
+}
+
+extern "C" int bwagpu_primary_flat(bwagpu_t *h, const bwagpu_opt_t *opt, int n_reads, const int32_t *counts, const bwagpu_alnreg_t *regs, const int64_t *ids,
+								   bwagpu_primary_t **out, int32_t *n_pri, float *kernel_ms)
+{
+	if (!h || !opt || n_reads < 0 || !out || (n_reads > 0 && (!counts || !ids))) return BWAGPU_EINVAL;
+	i64 tot = 0; int max_cnt = 0;
+	for (int i = 0; i < n_reads; ++i) { if (counts[i] < 0 || counts[i] > 0x3fffffff) return BWAGPU_EINVAL; tot += counts[i]; if (counts[i] > max_cnt) max_cnt = counts[i]; }
+	if (tot > 0 && !regs) return BWAGPU_EINVAL;
+	const BusyGuard busy(h->ibuf->busy);
+	HIPCHK(h, hipSetDevice(h->device));
+	*out = nullptr;
+	// the largest argument a logarithm can get: a region's longer side, its seed coverage, its incoming sub_n plus the increments of both rounds plus one
+	std::vector<i64> off((size_t)n_reads);
+	i64 log_need = 0, k = 0;
+	for (int i = 0; i < n_reads; ++i) {
+		off[i] = k;
+		for (int j = 0; j < counts[i]; ++j, ++k) {
+			const bwagpu_alnreg_t &a = regs[k];
+			const i64 lq = (i64)a.qe - a.qb, lr = a.re - a.rb, sn = (i64)a.sub_n + 2 * (i64)counts[i] + 1;
+			if (lq > log_need) log_need = lq;
+			if (lr > log_need) log_need = lr;
+			if (a.seedcov > log_need) log_need = a.seedcov;
+			if (sn > log_need) log_need = sn;
+		}
+	}
+	if (n_reads && (h->d_pf_cnt.ensure((size_t)n_reads * 4) || h->d_pf_off.ensure((size_t)n_reads * 8) || h->d_pf_ids.ensure((size_t)n_reads * 8) || h->d_pf_regs.ensure((size_t)(tot ? tot : 1) * sizeof(bwagpu_alnreg_t)))) {
+		h->err = "hipMalloc failed (primary)"; return BWAGPU_ENOMEM;
+	}
+	if (n_reads) {
+		HIPCHK(h, hipMemcpyAsync(h->d_pf_cnt.p, counts, (size_t)n_reads * 4, hipMemcpyHostToDevice, h->stream));
+		HIPCHK(h, hipMemcpyAsync(h->d_pf_off.p, off.data(), (size_t)n_reads * 8, hipMemcpyHostToDevice, h->stream));
+		HIPCHK(h, hipMemcpyAsync(h->d_pf_ids.p, ids, (size_t)n_reads * 8, hipMemcpyHostToDevice, h->stream));
+		if (tot) HIPCHK(h, hipMemcpyAsync(h->d_pf_regs.p, regs, (size_t)tot * sizeof(bwagpu_alnreg_t), hipMemcpyHostToDevice, h->stream));
+		HIPCHK(h, wait_stream(h));      // (`off` is a local array)
+	}
+	return primary_run(h, opt, n_reads, tot, max_cnt, log_need, h->d_pf_cnt.as<i32>(), h->d_pf_off.as<i64>(), h->d_pf_regs.as<bwagpu_alnreg_t>(), h->d_pf_ids.as<i64>(), 0,
+					   counts, regs, out, n_pri, kernel_ms);
 }
 
 extern "C" int bwagpu_align_flat(bwagpu_t *h, const bwagpu_opt_t *opt, int n, const uint8_t *seqs, const int64_t *off,

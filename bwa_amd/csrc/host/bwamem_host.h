@@ -77,6 +77,7 @@ struct Read {   // == bseq1_t as the finalize code needs it
 	const char *name; const char *comment; const uint8_t *seq /* nt4 codes */; const char *qual; int l_seq;
 	const CigHints *hints = nullptr;
 	const bwagpu_matesw_t *msw = nullptr; int n_msw = 0;   // device-computed mate-rescue alignments of this read (bwagpu_batch_matesw)
+	const bwagpu_primary_t *pri = nullptr;                 // device-computed marking and mapQ of this read's regions (bwagpu_batch_primary): one record per region
 };
 
 typedef std::vector<bwagpu_alnreg_t> Regs;
@@ -94,12 +95,13 @@ template <class F> static inline void parallel_for(int n_threads, long n, F f)
 
 uint64_t hash_64(uint64_t key);                                     // utils.h:98-109
 int mark_primary_se(const bwagpu_opt_t &opt, Regs &a, int64_t id);  // bwamem.c:547-584
-void reorder_primary5(int T, Regs &a);                              // bwamem.c:1008-1030
+int reorder_primary5(int T, Regs &a);                               // bwamem.c:1008-1030; returns the place a[0] was exchanged with (0: the list is as it was)
+void apply_primary(Regs &a, const bwagpu_primary_t *pri, int64_t id, std::vector<int32_t> &mapq);   // the list as mark_primary_se(opt, a, id) leaves it, from a read's bwagpu_batch_primary records; mapq[k] = approx_mapq_se of a[k]
 int approx_mapq_se(const bwagpu_opt_t &opt, const bwagpu_alnreg_t &a);   // bwamem.c:982-1006
 void host_region_cigar(const bwagpu_opt_t &opt, const RefSeqs &ref, const uint8_t *query, const bwagpu_alnreg_t &ar, bwagpu_cigar_t *out, std::vector<uint32_t> *ext);   // == one bwagpu_batch_cigars record (+ its entries of the operation array)
-Aln reg2aln(const bwagpu_opt_t &opt, const RefSeqs &ref, int l_query, const uint8_t *query, const bwagpu_alnreg_t *ar, const CigHints *hints = nullptr);   // bwamem.c:1119-1189
+Aln reg2aln(const bwagpu_opt_t &opt, const RefSeqs &ref, int l_query, const uint8_t *query, const bwagpu_alnreg_t *ar, const CigHints *hints = nullptr, int mapq_given = -1 /* >= 0: approx_mapq_se of *ar, computed elsewhere */);   // bwamem.c:1119-1189
 void aln2sam(const bwagpu_opt_t &opt, const RefSeqs &ref, SamText &out, const Read &s, const std::vector<Aln> &list, int which, const Aln *mate, const char *rg_id);   // bwamem.c:851-976
-void reg2sam(const bwagpu_opt_t &opt, const RefSeqs &ref, SamText &out, const Read &s, Regs &a, int extra_flag, const Aln *mate, const char *rg_id);   // bwamem.c:1033-1079
+void reg2sam(const bwagpu_opt_t &opt, const RefSeqs &ref, SamText &out, const Read &s, Regs &a, int extra_flag, const Aln *mate, const char *rg_id, const int32_t *dev_mapq = nullptr /* parallel to a: apply_primary's */);   // bwamem.c:1033-1079
 void pestat_flat(const bwagpu_opt_t &opt, int64_t l_pac, int n, const bwagpu_alnreg_t *all, const int64_t *roff, Pestat pes[4], bool verbose, int n_threads = 1);
 void attach_matesw(int n, Read *reads, const bwagpu_matesw_t *recs, int64_t n_recs, std::vector<bwagpu_matesw_t> &sorted);
 int64_t host_matesw_records(const bwagpu_opt_t &opt, const RefSeqs &ref, int n, const uint8_t *seqs, const int64_t *off, const bwagpu_alnreg_t *all, const int64_t *roff,

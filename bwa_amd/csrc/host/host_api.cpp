@@ -11,6 +11,16 @@
 
 namespace hostmem {
 
+// mark_primary_se (+ mem_reorder_primary5) of one single-end read: on the host, or -- when the device stage left records for the read (bwagpu_batch_primary) --
+// by applying them.  Returns the regions' mapQs in the second case (in `mq`), null in the first.
+static inline const int32_t *mark_se(const bwagpu_opt_t &opt, Regs &a, const Read &s, int64_t id, std::vector<int32_t> &mq)
+{
+	if (!s.pri) { mark_primary_se(opt, a, id); if (opt.flag & F_PRIMARY5) reorder_primary5(opt.T, a); return nullptr; }
+	apply_primary(a, s.pri, id, mq);
+	if (opt.flag & F_PRIMARY5) { const int k = reorder_primary5(opt.T, a); if (k > 0) std::swap(mq[0], mq[(size_t)k]); }
+	return mq.data();
+}
+
 // the regions of all reads of a batch (flat, read i's at all[roff[i] .. roff[i+1])) -> SAM text per read (sam[i]); PE when opt.flag & F_PE (mates
 // interleaved).  A worker copies a read's regions into a list of its own that it keeps from read to read (the stage's functions reorder, flag
 // and extend that list): per-read lists built by one thread and released by another cost two allocator round trips per read, and
@@ -35,11 +45,11 @@ void finalize_batch(const bwagpu_opt_t &opt, const RefSeqs &ref, int64_t n_proce
 		parallel_for(n_threads, n, [&](long i) {
 			thread_local Regs a;
 			a.assign(all + roff[i], all + roff[i + 1]);
-			mark_primary_se(opt, a, n_processed + i);
-			if (opt.flag & F_PRIMARY5) reorder_primary5(opt.T, a);
+			thread_local std::vector<int32_t> mq;
+			const int32_t *dq = mark_se(opt, a, reads[i], n_processed + i, mq);
 			thread_local SamText out;
 			out.clear();
-			reg2sam(opt, ref, out, reads[i], a, 0, 0, rg_id);
+			reg2sam(opt, ref, out, reads[i], a, 0, 0, rg_id, dq);
 			sam[i].assign(out.data(), out.size());
 		});
 	}
@@ -61,7 +71,7 @@ void finalize_batch_chunks(const bwagpu_opt_t &opt, const RefSeqs &ref, int64_t 
 	auto put = [](std::string &dst, const SamText &s) { dst.append(s.data(), strnlen(s.data(), s.size())); };
 	std::atomic<long> next(0);
 	auto work = [&]() {
-		Regs a[2]; SamText out[2], buf;
+		Regs a[2]; SamText out[2], buf; std::vector<int32_t> mq;
 		for (;;) {
 			const long c = next.fetch_add(1);
 			if (c >= n_chunks) break;
@@ -79,9 +89,8 @@ void finalize_batch_chunks(const bwagpu_opt_t &opt, const RefSeqs &ref, int64_t 
 			} else {
 				for (int i = lo; i < hi; ++i) {
 					a[0].assign(all + roff[i], all + roff[i + 1]);
-					mark_primary_se(opt, a[0], n_processed + i);
-					if (opt.flag & F_PRIMARY5) reorder_primary5(opt.T, a[0]);
-					reg2sam(opt, ref, buf, reads[i], a[0], 0, 0, rg_id);
+					const int32_t *dq = mark_se(opt, a[0], reads[i], n_processed + i, mq);
+					reg2sam(opt, ref, buf, reads[i], a[0], 0, 0, rg_id, dq);
 				}
 			}
 			if (!memchr(buf.data(), 0, buf.size())) { dst.assign(buf.data(), buf.size()); continue; }
@@ -98,10 +107,9 @@ void finalize_batch_chunks(const bwagpu_opt_t &opt, const RefSeqs &ref, int64_t 
 			} else {
 				for (int i = lo; i < hi; ++i) {
 					a[0].assign(all + roff[i], all + roff[i + 1]);
-					mark_primary_se(opt, a[0], n_processed + i);
-					if (opt.flag & F_PRIMARY5) reorder_primary5(opt.T, a[0]);
+					const int32_t *dq = mark_se(opt, a[0], reads[i], n_processed + i, mq);
 					out[0].clear();
-					reg2sam(opt, ref, out[0], reads[i], a[0], 0, 0, rg_id);
+					reg2sam(opt, ref, out[0], reads[i], a[0], 0, 0, rg_id, dq);
 					put(dst, out[0]);
 				}
 			}

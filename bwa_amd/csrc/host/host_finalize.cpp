@@ -99,21 +99,38 @@ int mark_primary_se(const bwagpu_opt_t &opt, Regs &av, int64_t id)
 	return n_pri;
 }
 
-void reorder_primary5(int T, Regs &av)
+int reorder_primary5(int T, Regs &av)
 {
 	int n = (int)av.size(), n_pri = 0, left_st = INT_MAX, left_k = -1;
 	bwagpu_alnreg_t *a = av.data();
 	for (int k = 0; k < n; ++k) if (a[k].secondary < 0 && !a[k].is_alt && a[k].score >= T) ++n_pri;
-	if (n_pri <= 1) return;
+	if (n_pri <= 1) return 0;
 	for (int k = 0; k < n; ++k) {
 		if (a[k].secondary >= 0 || a[k].is_alt || a[k].score < T) continue;
 		if (a[k].qb < left_st) { left_st = a[k].qb; left_k = k; }
 	}
-	if (left_k == 0) return;
+	if (left_k == 0) return 0;
 	std::swap(a[0], a[left_k]);
 	for (int k = 1; k < n; ++k) {
 		if (a[k].secondary == 0) a[k].secondary = left_k; else if (a[k].secondary == left_k) a[k].secondary = 0;
 		if (a[k].secondary_all == 0) a[k].secondary_all = left_k; else if (a[k].secondary_all == left_k) a[k].secondary_all = 0;
+	}
+	return left_k;
+}
+
+// What mark_primary_se leaves, taken from the device's records (bwagpu_batch_primary): the regions in the records' order with the marked fields set,
+// and every region's mapQ beside them.
+void apply_primary(Regs &av, const bwagpu_primary_t *pri, int64_t id, std::vector<int32_t> &mapq)
+{
+	const int n = (int)av.size();
+	thread_local Regs src;
+	src = av; mapq.resize((size_t)n);
+	for (int i = 0; i < n; ++i) {
+		const bwagpu_primary_t &r = pri[i];
+		bwagpu_alnreg_t &a = av[i];
+		a = src[r.src];
+		a.secondary = r.secondary; a.secondary_all = r.secondary_all; a.sub = r.sub; a.alt_sc = r.alt_sc; a.sub_n = r.sub_n; a.hash = hash_64((uint64_t)(id + r.src));
+		mapq[i] = r.mapq;
 	}
 }
 
@@ -260,13 +277,13 @@ void host_region_cigar(const bwagpu_opt_t &opt, const RefSeqs &ref, const uint8_
 	} else out->md = (uint64_t)md4(1) << 32 | md4(0);
 }
 
-Aln reg2aln(const bwagpu_opt_t &opt, const RefSeqs &ref, int l_query, const uint8_t *query, const bwagpu_alnreg_t *ar, const CigHints *hints)
+Aln reg2aln(const bwagpu_opt_t &opt, const RefSeqs &ref, int l_query, const uint8_t *query, const bwagpu_alnreg_t *ar, const CigHints *hints, int mapq_given)
 {
 	Aln a;
 	if (ar == 0 || ar->rb < 0 || ar->re < 0) { a.rid = -1; a.pos = -1; a.flag |= 0x4; return a; }
 	int qb = ar->qb, qe = ar->qe, score = 0, last_sc = -(1 << 30), NM = -1, i = 0;
 	int64_t rb = ar->rb, re = ar->re;
-	a.mapq = ar->secondary < 0 ? approx_mapq_se(opt, *ar) : 0;
+	a.mapq = ar->secondary < 0 ? (mapq_given >= 0 ? mapq_given : approx_mapq_se(opt, *ar)) : 0;
 	if (ar->secondary >= 0) a.flag |= 0x100;
 	int tmp = infer_bw(qe - qb, (int)(re - rb), ar->truesc, opt.a, opt.o_del, opt.e_del);
 	int w2 = infer_bw(qe - qb, (int)(re - rb), ar->truesc, opt.a, opt.o_ins, opt.e_ins);
@@ -315,7 +332,7 @@ static inline int pri_idx(double ratio, const bwagpu_alnreg_t *a, int i)
 }
 
 // returns false when no XA exists for any region (the reference's NULL)
-static bool gen_alt(const bwagpu_opt_t &opt, const RefSeqs &ref, const Regs &av, int l_query, const uint8_t *query, std::vector<std::string> &xa, std::vector<char> &has, const CigHints *hints)
+static bool gen_alt(const bwagpu_opt_t &opt, const RefSeqs &ref, const Regs &av, int l_query, const uint8_t *query, std::vector<std::string> &xa, std::vector<char> &has, const CigHints *hints, const int32_t *dev_mapq = nullptr)
 {
 	int n = (int)av.size(), tot = 0;
 	const bwagpu_alnreg_t *a = av.data();
@@ -331,7 +348,7 @@ static bool gen_alt(const bwagpu_opt_t &opt, const RefSeqs &ref, const Regs &av,
 		int r = pri_idx(opt.XA_drop_ratio, a, i);
 		if (r < 0) continue;
 		if (cnt[r] > opt.max_XA_hits_alt || (!has_alt[r] && cnt[r] > opt.max_XA_hits)) continue;
-		Aln t = reg2aln(opt, ref, l_query, query, &a[i], hints);
+		Aln t = reg2aln(opt, ref, l_query, query, &a[i], hints, dev_mapq ? dev_mapq[i] : -1);
 		std::string &s = xa[r];
 		s += ref.ctg[t.rid].name; s += ','; s += "+-"[t.is_rev]; put_int(s, t.pos + 1); s += ',';
 		for (uint32_t c : t.cigar) { put_int(s, c >> 4); s += "MIDSHN"[c & 0xf]; }
@@ -497,12 +514,12 @@ void aln2sam(const bwagpu_opt_t &opt, const RefSeqs &ref, SamText &str, const Re
 }
 
 // ---- all records of one read (mem_reg2sam, bwamem.c:1033-1079) -----------------------------------------------------------
-void reg2sam(const bwagpu_opt_t &opt, const RefSeqs &ref, SamText &out, const Read &s, Regs &av, int extra_flag, const Aln *m, const char *rg_id)
+void reg2sam(const bwagpu_opt_t &opt, const RefSeqs &ref, SamText &out, const Read &s, Regs &av, int extra_flag, const Aln *m, const char *rg_id, const int32_t *dev_mapq)
 {
 	std::vector<std::string> xa; std::vector<char> has;
 	bool have_xa = false;
 	out.reserve(out.size() + 2 * (size_t)s.l_seq + 320);
-	if (!(opt.flag & F_ALL)) have_xa = gen_alt(opt, ref, av, s.l_seq, s.seq, xa, has, s.hints);
+	if (!(opt.flag & F_ALL)) have_xa = gen_alt(opt, ref, av, s.l_seq, s.seq, xa, has, s.hints, dev_mapq);
 	std::vector<Aln> aa;
 	int l = 0;
 	const int n = (int)av.size();
@@ -511,7 +528,7 @@ void reg2sam(const bwagpu_opt_t &opt, const RefSeqs &ref, SamText &out, const Re
 		if (p.score < opt.T) continue;
 		if (p.secondary >= 0 && (p.is_alt || !(opt.flag & F_ALL))) continue;
 		if (p.secondary >= 0 && p.secondary < INT_MAX && p.score < av[p.secondary].score * opt.drop_ratio) continue;
-		Aln q = reg2aln(opt, ref, s.l_seq, s.seq, &p, s.hints);
+		Aln q = reg2aln(opt, ref, s.l_seq, s.seq, &p, s.hints, dev_mapq ? dev_mapq[k] : -1);
 		if (have_xa && has[k]) { q.has_xa = true; q.xa = xa[k]; }
 		q.flag |= extra_flag;
 		if (p.secondary >= 0) q.sub = -1;

@@ -38,6 +38,11 @@ ALNREG_DTYPE = np.dtype([
 ])
 assert ALNREG_DTYPE.itemsize == 88
 
+# bwagpu_primary_t: one region as mem_mark_primary_se + mem_approx_mapq_se leave it (bwagpu_batch_primary / bwagpu_primary_flat)
+PRIMARY_DTYPE = np.dtype([("src", "<i4"), ("secondary", "<i4"), ("secondary_all", "<i4"), ("sub", "<i4"), ("alt_sc", "<i4"), ("sub_n", "<i4"),
+                          ("mapq", "<i4"), ("flags", "<i4")])
+assert PRIMARY_DTYPE.itemsize == 32
+
 INTV_DTYPE = np.dtype([("x0", "<u8"), ("x1", "<u8"), ("x2", "<u8"), ("info", "<u8")])
 SEED_DTYPE = np.dtype([("rbeg", "<i8"), ("qbeg", "<i4"), ("len", "<i4"), ("score", "<i4"), ("_pad", "<i4")])
 CHAIN_HDR_DTYPE = np.dtype([("n", "<i4"), ("rid", "<i4"), ("w", "<i4"), ("kept", "<i4"), ("is_alt", "<i4"),

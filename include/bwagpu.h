@@ -279,6 +279,29 @@ int bwagpu_batch_cigar_ops(bwagpu_t *h, uint32_t **ops, int64_t *n_ops);
  * and runs ksw_align2 itself where there is none.  Free with bwagpu_free. */
 int bwagpu_batch_matesw(bwagpu_t *h, const bwagpu_opt_t *opt, const bwagpu_pes_t pes[4], bwagpu_matesw_t **out, int64_t *n_out);
 
+/* Primary/secondary marking and mapping quality on the device: what worker2 does first with a read's regions,
+ * mem_mark_primary_se (bwamem.c:519-584) followed by mem_approx_mapq_se (bwamem.c:982-1006).  One record per region, in the order
+ * mem_mark_primary_se leaves the read's list; `hash` is not stored (it is hash_64(id + src), utils.h:98-109). */
+typedef struct {
+	int32_t src;            /* index of this region in the read's list as given / as downloaded */
+	int32_t secondary, secondary_all, sub, alt_sc, sub_n;   /* as the reference leaves them (INT_MAX for an ALT hit's `secondary`, bwamem.c:571) */
+	int32_t mapq;           /* mem_approx_mapq_se of the marked region, for every region (callers apply `secondary < 0 ? mapq : 0` themselves, bwamem.c:1061) */
+	int32_t flags;          /* bit 0: a logarithm's argument was outside the handle's table; mapq was then computed by the host side of the call (it is right either way) */
+} bwagpu_primary_t;
+/* After bwagpu_batch_download: the records of every read of the batch, concatenated in read order with the download's counts.  Read i of the
+ * batch has id id0 + i -- what mem_reg2sam (n_processed + i, bwamem.c:1227) and mem_sam_pe (id << 1 | r, bwamem_pair.c:349-350) pass for an even
+ * n_processed.  n_pri[i] (may be NULL) = mem_mark_primary_se's return value for read i; *kernel_ms (may be NULL) = device time of the kernels
+ * (HIP events).  Free *out with bwagpu_free.  BWAGPU_EINVAL before a download. */
+int bwagpu_batch_primary(bwagpu_t *h, const bwagpu_opt_t *opt, int64_t id0, bwagpu_primary_t **out, int64_t *n_out, int32_t *n_pri, float *kernel_ms);
+/* The same kernels on region lists the caller supplies (read i: counts[i] regions, concatenated in regs; ids[i] its id) -- for a finalize stage
+ * that marks after it has merged mate-rescue hits on the host (bwamem_pair.c -> mem_sam_pe).  The regions' sub_n, csub, seedcov, frac_rep and
+ * is_alt are read as given (the reference does not reset sub_n either).  *out: sum of counts records, free with bwagpu_free. */
+int bwagpu_primary_flat(bwagpu_t *h, const bwagpu_opt_t *opt, int n_reads, const int32_t *counts, const bwagpu_alnreg_t *regs, const int64_t *ids,
+						bwagpu_primary_t **out, int32_t *n_pri, float *kernel_ms);
+/* The sizes at which the kernels change their method, as compiled: out[0] regions up to which one lane marks a read, [1] up to which a wavefront
+ * does with its small LDS area, [2] with its large one (reads with more work in HBM scratch), [3] entries of the kept list compared per step. */
+void bwagpu_primary_limits(int32_t out[4]);
+
 /* ---- index construction on the device -------------------------------------------------------- */
 /* The arrays `bwa index` leaves in bwt_t after bwt_bwtgen2/bwt_pac2bwt + bwt_bwtupdate_core + bwt_cal_sa
  * (bwtindex.c:64-120, 150-172; bwt.c:62-84), built from the 2-bit packed forward strand by a suffix sort in HBM
