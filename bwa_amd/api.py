@@ -16,7 +16,7 @@ try:   # torch bundles its own HIP runtime (libamdhip64); loading it first keeps
 except Exception:  # pragma: no cover
     torch = None
 
-from .structs import ALNREG_DTYPE, PRIMARY_DTYPE, MemOpt
+from .structs import ALNREG_DTYPE, PAIR_DTYPE, PESTAT_DTYPE, PRIMARY_DTYPE, MemOpt
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 DEFAULT_LIB = os.path.join(HERE, "csrc", "libbwagpu.so")
@@ -60,7 +60,7 @@ EXPORTS = [
     "bwagpu_free", "bwagpu_batch_upload", "bwagpu_batch_run", "bwagpu_batch_download", "bwagpu_set_taps", "bwagpu_tap_intervals",
     "bwagpu_tap_chains", "bwagpu_tap_regs_raw", "bwagpu_index_buffers", "bwagpu_index_export", "bwagpu_clone", "bwagpu_index_ready",
     "bwagpu_batch_cigars", "bwagpu_batch_cigar_ops", "bwagpu_debug_phase", "bwagpu_batch_matesw", "bwagpu_clone_to_device", "bwagpu_index_build", "bwagpu_built_free", "bwagpu_abi_sizes", "bwagpu_debug_prof", "bwagpu_debug_hist", "bwagpu_debug_seed_x2", "bwagpu_debug_chain_hist", "bwagpu_debug_dp", "bwagpu_debug_sort", "bwagpu_debug_sort_limits", "bwagpu_set_cigar_filter", "bwagpu_batch_reserve", "bwagpu_batch_footprint", "bwagpu_mem_info",
-    "bwagpu_batch_primary", "bwagpu_primary_flat", "bwagpu_primary_limits",
+    "bwagpu_batch_primary", "bwagpu_primary_flat", "bwagpu_primary_limits", "bwagpu_batch_pair", "bwagpu_pair_flat", "bwagpu_pair_limits",
     "bwagpu_trim", "bwagpu_set_option", "bwagpu_get_option", "bwagpu_set_default_option", "bwagpu_clear_default_options", "bwagpu_option_name",
 ]
 
@@ -112,6 +112,9 @@ def load_library(path: str | None = None) -> C.CDLL:
     L.bwagpu_batch_primary.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.bwagpu_primary_flat.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.bwagpu_primary_limits.restype = None
+    L.bwagpu_batch_pair.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.bwagpu_pair_flat.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.bwagpu_pair_limits.restype = None
     L.bwagpu_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_longlong]
     L.bwagpu_get_option.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p]
     L.bwagpu_set_default_option.argtypes = [C.c_char_p, C.c_longlong]
@@ -297,6 +300,35 @@ class BwaGpu:
         out = (C.c_int32 * 4)()
         self.L.bwagpu_primary_limits(out)
         return dict(zip(("lane_max", "lds_small", "lds_big", "scan"), list(out)))
+
+    def pair(self, opt: MemOpt, pes: np.ndarray, id0: int = 0):
+        """bwagpu_batch_pair: marking, then mem_pair of every pair (reads 2p, 2p + 1) of the last download() on the device; pes = PESTAT_DTYPE[4], read i has
+        id id0 + i (id0 even).  -> (PAIR_DTYPE[n pairs], PRIMARY_DTYPE records as primary() returns them, n_pri int32[n reads], device time of the kernels in ms)"""
+        pes = np.ascontiguousarray(pes, dtype=PESTAT_DTYPE)
+        assert pes.shape == (4,)
+        pp, npairs, pr, nr, ms = C.c_void_p(), C.c_int64(), C.c_void_p(), C.c_int64(), C.c_float()
+        n_pri = np.zeros(self._n, dtype=np.int32)
+        self._chk(self.L.bwagpu_batch_pair(self.h, C.byref(opt), pes.ctypes.data, int(id0), C.byref(pp), C.byref(npairs), C.byref(pr), C.byref(nr), n_pri.ctypes.data, C.byref(ms)))
+        return self._take(pp, npairs.value, PAIR_DTYPE), self._take(pr, nr.value, PRIMARY_DTYPE), n_pri, ms.value
+
+    def pair_flat(self, opt: MemOpt, pes: np.ndarray, counts: np.ndarray, n_pri: np.ndarray, regs: np.ndarray, ids: np.ndarray):
+        """bwagpu_pair_flat: the pairing kernels on marked lists of the caller (reads 2p, 2p + 1: counts[] records of regs each, of which the first n_pri[]
+        take part; pair p has id ids[p]) -> (PAIR_DTYPE[n pairs], ms)."""
+        pes = np.ascontiguousarray(pes, dtype=PESTAT_DTYPE)
+        counts = np.ascontiguousarray(counts, dtype=np.int32)
+        n_pri = np.ascontiguousarray(n_pri, dtype=np.int32)
+        regs = np.ascontiguousarray(regs, dtype=ALNREG_DTYPE)
+        ids = np.ascontiguousarray(ids, dtype=np.int64)
+        assert pes.shape == (4,) and counts.shape == n_pri.shape == (2 * ids.shape[0],) and int(counts.sum()) == regs.shape[0]
+        p, ms = C.c_void_p(), C.c_float()
+        self._chk(self.L.bwagpu_pair_flat(self.h, C.byref(opt), pes.ctypes.data, ids.shape[0], counts.ctypes.data, n_pri.ctypes.data, regs.ctypes.data, ids.ctypes.data, C.byref(p), C.byref(ms)))
+        return self._take(p, ids.shape[0], PAIR_DTYPE), ms.value
+
+    def pair_limits(self) -> dict:
+        """bwagpu_pair_limits: the numbers of hits at which the pairing kernels change their form, as compiled."""
+        out = (C.c_int32 * 3)()
+        self.L.bwagpu_pair_limits(out)
+        return dict(zip(("lane_max", "lds_small", "lds_big"), list(out)))
 
     def debug_dp(self, opt: MemOpt, kind: int, cases: np.ndarray, seqs: np.ndarray) -> np.ndarray:
         """bwagpu_debug_dp: one wavefront of a device DP routine per case (DP_CASE_DTYPE) -> int32[n_cases, 72]."""

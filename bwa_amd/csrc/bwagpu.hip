@@ -15,6 +15,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include <math.h>
+#include <algorithm>
 #include <atomic>
 #include <map>
 #include <mutex>
@@ -38,6 +39,7 @@
 #include "dev_dedupw.h"
 #include "dev_matesw.h"
 #include "dev_primary.h"
+#include "dev_pair.h"
 #include "dev_debug.h"
 
 #define BWAGPU_VERSION "bwagpu 0.1 (gfx950)"
@@ -92,6 +94,8 @@ struct bwagpu_s {
 	i64 packed_tot = -1;          // regions packed by the last bwagpu_batch_download (-1: none)
 	int packed_max = 0; bool downloaded = false;   // ... the largest count of a read among them; a download has happened for this run (a batch without reads packs nothing)
 	DevBuf d_pri_out, d_pri_npri, d_pri_lists, d_pri_ctr, d_pri_scratch, d_pri_log;      // bwagpu_batch_primary / bwagpu_primary_flat: records, return values, the wavefront forms' read lists and their lengths, HBM working arrays, the table of logarithms
+	DevBuf d_pair_out, d_pair_lists, d_pair_ctr, d_pair_scratch, d_pair_tab, d_pair_npri;      // bwagpu_batch_pair / bwagpu_pair_flat: records, the wavefront forms' pair lists and their lengths, HBM working arrays, the table of log(2 erfc) values, bwagpu_pair_flat's n_pri
+	std::vector<double> pair_tab; bwagpu_pestat_t pair_tab_pes[4] = {}; i64 pair_tab_cap = -1; i32 pair_toff[4] = {}, pair_tlen[4] = {}; bool pair_tab_dev = false;   // the table as last filled: for these windows and this capacity; resident in d_pair_tab
 	DevBuf d_pf_regs, d_pf_cnt, d_pf_off, d_pf_ids;                                       // ... and the uploaded lists of bwagpu_primary_flat
 	std::vector<double> pri_log; i64 pri_log_dev = 0;                                      // log((double)k) by the host's libm for k < size; entries resident in d_pri_log
 	DevBuf d_msw_tasks, d_msw_out, d_msw_pes, d_msw_scratch;
@@ -235,7 +239,7 @@ static bool option_in_range(const BwagpuConfig &c, const long long *f, long long
 	if (f == &c.ext_occ) return value == 4 || value == 6;
 	if (f == &c.seed_mrg) return value == -1 || value == 0 || value == 2;
 	if (f == &c.share) return in(-1, 100);
-	if (f == &c.seed_task_stack || f == &c.seed_p2_cap || f == &c.mem_cap || f == &c.seed_grid || f == &c.cig_ops_cap || f == &c.idx_desc_max_mb || f == &c.pri_log_cap) return in(0, 0x3fffffff);
+	if (f == &c.seed_task_stack || f == &c.seed_p2_cap || f == &c.mem_cap || f == &c.seed_grid || f == &c.cig_ops_cap || f == &c.idx_desc_max_mb || f == &c.pri_log_cap || f == &c.pair_tab_cap) return in(0, 0x3fffffff);
 	if (f == &c.seed_budget || f == &c.dedup_heavy) return in(-1, 0x3fffffff);
 	if (f == &c.dedup_stage || f == &c.dedup_big || f == &c.dedup_net) return in(-1, 1024);
 	if (f == &c.seed_lds_ent) return in(-1, 16);
@@ -498,7 +502,7 @@ extern "C" void bwagpu_destroy(bwagpu_t *h)
 		for (DevBuf *b : ib) b->release();
 		delete h->ibuf;
 	}
-	DevBuf *all[] = { &h->d_pri_out, &h->d_pri_npri, &h->d_pri_lists, &h->d_pri_ctr, &h->d_pri_scratch, &h->d_pri_log, &h->d_pf_regs, &h->d_pf_cnt, &h->d_pf_off, &h->d_pf_ids, &h->d_heavy, &h->d_dd_tmp, &h->d_p2_tasks, &h->d_vr_tab, &h->d_vr_ovf, &h->d_intv_n3, &h->d_cigl_list, &h->d_cigl_z, &h->d_cigl_ops, &h->d_cigl_md, &h->d_seq_2b, &h->d_seq_flags, &h->d_cig_ext, &h->d_msw_tasks, &h->d_msw_out, &h->d_msw_pes, &h->d_msw_scratch, &h->d_pack_off, &h->d_regs_packed, &h->d_pack_read, &h->d_cigs, &h->d_seq, &h->d_seq_nib, &h->d_off, &h->d_ctr, &h->d_tmp_intv,
+	DevBuf *all[] = { &h->d_pair_out, &h->d_pair_lists, &h->d_pair_ctr, &h->d_pair_scratch, &h->d_pair_tab, &h->d_pair_npri, &h->d_pri_out, &h->d_pri_npri, &h->d_pri_lists, &h->d_pri_ctr, &h->d_pri_scratch, &h->d_pri_log, &h->d_pf_regs, &h->d_pf_cnt, &h->d_pf_off, &h->d_pf_ids, &h->d_heavy, &h->d_dd_tmp, &h->d_p2_tasks, &h->d_vr_tab, &h->d_vr_ovf, &h->d_intv_n3, &h->d_cigl_list, &h->d_cigl_z, &h->d_cigl_ops, &h->d_cigl_md, &h->d_seq_2b, &h->d_seq_flags, &h->d_cig_ext, &h->d_msw_tasks, &h->d_msw_out, &h->d_msw_pes, &h->d_msw_scratch, &h->d_pack_off, &h->d_regs_packed, &h->d_pack_read, &h->d_cigs, &h->d_seq, &h->d_seq_nib, &h->d_off, &h->d_ctr, &h->d_tmp_intv,
 		&h->d_intv_n, &h->d_intv_off, &h->d_intv, &h->d_seed_n, &h->d_seed_off, &h->d_slot_pos, &h->d_slot_qbeg, &h->d_slot_len, &h->d_slot_rid, &h->d_slot_blob, &h->d_chain_n, &h->d_node_off,
 		&h->d_order, &h->d_bin_cnt, &h->d_seed_w, &h->d_seed_order, &h->d_nodes, &h->d_reg_off, &h->d_reg_cap_r, &h->d_reg_n_raw, &h->d_reg_n, &h->d_regs, &h->d_regs_raw, &h->d_dp_h, &h->d_dp_e, &h->d_minhsp };
 	for (DevBuf *b : all) b->release();
@@ -1746,6 +1750,215 @@ extern "C" int bwagpu_primary_flat(bwagpu_t *h, const bwagpu_opt_t *opt, int n_r
 	}
 	return primary_run(h, opt, n_reads, tot, max_cnt, log_need, h->d_pf_cnt.as<i32>(), h->d_pf_off.as<i64>(), h->d_pf_regs.as<bwagpu_alnreg_t>(), h->d_pf_ids.as<i64>(), 0,
 					   counts, regs, out, n_pri, kernel_ms);
+}
+
+// ---- pairing on the device (dev_pair.h) ------------------------------------------------------------------------------------------------------------
+extern "C" void bwagpu_pair_limits(int32_t out[3]) { out[0] = PAIR_LANE_MAX; out[1] = PAIR_LDS_SMALL; out[2] = PAIR_LDS_BIG; }
+
+static const i64 PAIR_TAB_DEFAULT = (i64)1 << 18;      // entries of the table of log(2 erfc) values unless option pair_tab_cap says otherwise (2 MB)
+// bwamem_pair.c:243-244: the term of q that depends on the distance alone, by the host's libm
+static double pair_tab_value(i64 dist, const bwagpu_pestat_t &pe)
+{
+	const double ns = (dist - pe.avg) / pe.std;
+	return log(2. * erfc(fabs(ns) * M_SQRT1_2));
+}
+
+// mem_pair of one pair on the host, with the host's erfc / log: the records of pairs that met a distance outside the table.  The same statement of the
+// function as pair_read (dev_pair.h): sort by (x, y), the candidate set of every i, the two largest candidates, the count.
+static bwagpu_pair_t pair_host(const bwagpu_opt_t &opt, const bwagpu_pestat_t pes[4], i64 l_pac, const std::vector<i64> &ctg_off, const bwagpu_alnreg_t *a0, const bwagpu_primary_t *s0, int n0,
+							   const bwagpu_alnreg_t *a1, const bwagpu_primary_t *s1, int n1, int id)
+{
+	bwagpu_pair_t rec; rec.score = rec.sub = rec.n_sub = 0; rec.z[0] = rec.z[1] = -1; rec.flags = 1; rec.n_cand = 0;
+	std::vector<std::pair<u64, u64>> v;
+	for (int r = 0; r < 2; ++r)
+		for (int i = 0; i < (r ? n1 : n0); ++i) {
+			const bwagpu_alnreg_t &g = r ? a1[s1 ? s1[i].src : i] : a0[s0 ? s0[i].src : i];
+			u64 x, y;
+			pair_key(g, i, r, l_pac, g.rid >= 0 && (size_t)g.rid < ctg_off.size() ? ctg_off[(size_t)g.rid] : 0, x, y);
+			v.emplace_back(x, y);
+		}
+	std::sort(v.begin(), v.end());      // (a total order: the (i, r) are distinct)
+	u64 bx = 0, by = 0, cx = 0, cy = 0;      // the largest and the second largest candidate
+	std::vector<int> qs; std::vector<u64> ys;
+	for (int i = 0; i < (int)v.size(); ++i)
+		for (int k = i - 1; k >= 0; --k) {
+			const i64 dist = (i64)v[i].first - (i64)v[k].first;
+			if (((v[k].second ^ v[i].second) & 1) == 0) continue;
+			const int dir = (int)(v[k].second & 2) | (int)(v[i].second >> 1 & 1);
+			if (pes[dir].failed || dist < pes[dir].low || dist > pes[dir].high) continue;
+			const int q = pair_q(v[i].second >> 32, v[k].second >> 32, pair_tab_value(dist, pes[dir]), opt.a);
+			const u64 py = (u64)k << 32 | (u64)i, px = pair_cand_x(q, py, id);
+			if (pair_lt(bx, by, px, py)) { cx = bx; cy = by; bx = px; by = py; }
+			else if (pair_lt(cx, cy, px, py)) { cx = px; cy = py; }
+			qs.push_back(q); ys.push_back(py);
+		}
+	rec.n_cand = (i64)qs.size();
+	if (qs.empty()) return rec;
+	const u64 yk = v[(size_t)(by >> 32)].second, yi = v[(size_t)(by & 0xffffffffu)].second;
+	rec.z[yk & 1] = (int)((yk & 0xffffffffu) >> 2); rec.z[yi & 1] = (int)((yi & 0xffffffffu) >> 2);
+	rec.score = (int)(bx >> 32);
+	if (qs.size() > 1) {
+		const int tmp = pair_tmp(opt);
+		rec.sub = (int)(cx >> 32);
+		for (size_t j = 0; j < qs.size(); ++j) if (ys[j] != by && rec.sub - qs[j] <= tmp) ++rec.n_sub;
+	}
+	return rec;
+}
+
+// The kernels of both entry points on n_pairs pairs (reads 2p, 2p + 1: lists at d_off[] of d_regs, the first d_npri[] places of each; d_src: the marking records
+// at the same offsets, or null; ids d_ids, or id0 + p): records to a result block (*out).  max_sum = the largest n_pri[2p] + n_pri[2p + 1] to expect (sizes the HBM
+// form).  The same lists on the host, for the pairs that come back flagged: host_npri, and host_off / host_regs (tot regions) / host_ids or null -- they are then
+// fetched from the device --, host_src (null with d_src).
+static int pair_run(bwagpu_t *h, const bwagpu_opt_t *opt, const bwagpu_pestat_t pes[4], int n_pairs, i64 tot, i64 max_sum, const i32 *d_npri, const i64 *d_off, const bwagpu_alnreg_t *d_regs,
+					const bwagpu_primary_t *d_src, const i64 *d_ids, i64 id0, const i32 *host_npri, const i64 *host_off, const bwagpu_alnreg_t *host_regs, const bwagpu_primary_t *host_src,
+					const i64 *host_ids, bwagpu_pair_t **out, float *kernel_ms)
+{
+	if (kernel_ms) *kernel_ms = 0.f;
+	bwagpu_pair_t *res = (bwagpu_pair_t*)result_alloc((size_t)(n_pairs ? n_pairs : 1) * sizeof(bwagpu_pair_t));
+	if (!res) return BWAGPU_ENOMEM;
+	if (n_pairs == 0) { *out = res; return BWAGPU_OK; }
+	// the table: for every orientation that has not failed, the distances low .. high as far as the capacity goes, in the order of the orientations
+	const i64 cap = h->cfg.pair_tab_cap > 0 ? h->cfg.pair_tab_cap : PAIR_TAB_DEFAULT;
+	if (!h->pair_tab_dev || h->pair_tab_cap != cap || memcmp(h->pair_tab_pes, pes, sizeof h->pair_tab_pes) != 0) {
+		i64 used = 0;
+		for (int d = 0; d < 4; ++d) {
+			i64 len = pes[d].failed || pes[d].high < pes[d].low ? 0 : (i64)pes[d].high - pes[d].low + 1;
+			if (len > cap - used) len = cap - used;
+			h->pair_toff[d] = (i32)used; h->pair_tlen[d] = (i32)len; used += len;
+		}
+		h->pair_tab.resize((size_t)(used ? used : 1));
+		for (int d = 0; d < 4; ++d)
+			for (i64 k = 0; k < h->pair_tlen[d]; ++k) h->pair_tab[(size_t)(h->pair_toff[d] + k)] = pair_tab_value((i64)pes[d].low + k, pes[d]);
+		memcpy(h->pair_tab_pes, pes, sizeof h->pair_tab_pes); h->pair_tab_cap = cap; h->pair_tab_dev = false;
+	}
+	const int n_hbm = max_sum > PAIR_LDS_BIG ? (n_pairs < 64 ? n_pairs : 64) : 0;      // workgroups of the HBM form
+	if (max_sum > 0x3fffffff) { bwagpu_free(res); return BWAGPU_EINVAL; }
+	const void *tab_was = h->d_pair_tab.p;
+	if (h->d_pair_out.ensure((size_t)n_pairs * sizeof(bwagpu_pair_t)) || h->d_pair_lists.ensure((size_t)n_pairs * 3 * 4) || h->d_pair_ctr.ensure(4 * sizeof(unsigned int)) ||
+		h->d_pair_tab.ensure(h->pair_tab.size() * 8) || (n_hbm && h->d_pair_scratch.ensure((size_t)n_hbm * (size_t)max_sum * PAIR_WORDS * 4))) {
+		bwagpu_free(res); h->err = "hipMalloc failed (pair)"; return BWAGPU_ENOMEM;
+	}
+	hipError_t e = hipSuccess;
+	if (!h->pair_tab_dev || h->d_pair_tab.p != tab_was) { e = hipMemcpyAsync(h->d_pair_tab.p, h->pair_tab.data(), h->pair_tab.size() * 8, hipMemcpyHostToDevice, h->stream); h->pair_tab_dev = true; }
+	if (e == hipSuccess) e = hipMemsetAsync(h->d_pair_ctr.p, 0, 4 * sizeof(unsigned int), h->stream);
+	PairWin P; P.t = h->d_pair_tab.as<double>();
+	for (int d = 0; d < 4; ++d) { P.low[d] = pes[d].low; P.high[d] = pes[d].high; P.failed[d] = pes[d].failed || pes[d].high < pes[d].low; P.toff[d] = h->pair_toff[d]; P.tlen[d] = h->pair_tlen[d]; }
+	bwagpu_pair_t *d_out = h->d_pair_out.as<bwagpu_pair_t>();
+	i32 *lists = h->d_pair_lists.as<i32>();
+	unsigned int *list_n = h->d_pair_ctr.as<unsigned int>();
+	const i64 *ctg = h->ix.ctg_off;
+	(void)hipEventRecord(h->ev[0], h->stream);
+	if (e == hipSuccess) {
+		int nb = (n_pairs + PAIR_LANE_BLOCK - 1) / PAIR_LANE_BLOCK; if (nb > 256 * 12) nb = 256 * 12;
+		hipLaunchKernelGGL(k_pair_lane, dim3(nb), dim3(PAIR_LANE_BLOCK), 0, h->stream, *opt, P, h->l_pac, h->n_seqs, ctg, n_pairs, d_npri, d_off, d_regs, d_src, d_ids, id0, d_out, lists, list_n);
+		e = hipGetLastError();
+	}
+	// the wavefront forms draw their pairs from the lists the first kernel left; a form no pair of the batch can need is not launched
+	if (e == hipSuccess && max_sum > PAIR_LANE_MAX) {
+		const int nb = n_pairs < 256 * 16 ? n_pairs : 256 * 16;
+		hipLaunchKernelGGL(k_pair_wave<PAIR_LDS_SMALL>, dim3(nb), dim3(64), 0, h->stream, *opt, P, h->l_pac, h->n_seqs, ctg, d_npri, d_off, d_regs, d_src, d_ids, id0, d_out, lists, list_n, (u64*)nullptr, 0);
+		e = hipGetLastError();
+	}
+	if (e == hipSuccess && max_sum > PAIR_LDS_SMALL) {
+		const int nb = n_pairs < 256 * 4 ? n_pairs : 256 * 4;
+		hipLaunchKernelGGL(k_pair_wave<PAIR_LDS_BIG>, dim3(nb), dim3(64), 0, h->stream, *opt, P, h->l_pac, h->n_seqs, ctg, d_npri, d_off, d_regs, d_src, d_ids, id0, d_out, lists + n_pairs, list_n + 1, (u64*)nullptr, 0);
+		e = hipGetLastError();
+	}
+	if (e == hipSuccess && n_hbm) {
+		hipLaunchKernelGGL(k_pair_wave<0>, dim3(n_hbm), dim3(64), 0, h->stream, *opt, P, h->l_pac, h->n_seqs, ctg, d_npri, d_off, d_regs, d_src, d_ids, id0, d_out, lists + (size_t)2 * n_pairs, list_n + 2,
+						   h->d_pair_scratch.as<u64>(), (int)max_sum);
+		e = hipGetLastError();
+	}
+	(void)hipEventRecord(h->ev[1], h->stream);
+	if (e == hipSuccess) e = hipMemcpyAsync(res, d_out, (size_t)n_pairs * sizeof(bwagpu_pair_t), hipMemcpyDeviceToHost, h->stream);
+	if (e == hipSuccess) e = wait_stream(h);
+	if (e != hipSuccess) { bwagpu_free(res); HIPCHK(h, e); }
+	if (kernel_ms) (void)hipEventElapsedTime(kernel_ms, h->ev[0], h->ev[1]);
+	bool any = false;
+	for (int p = 0; p < n_pairs; ++p) {
+		if (res[p].flags & 2) { bwagpu_free(res); h->err = "internal: a pair outgrew the pairing kernel's working arrays"; return BWAGPU_EHIP; }
+		any |= (res[p].flags & 1) != 0;
+	}
+	if (any) {      // pairs that met a distance outside the table: the same function with the host's erfc / log
+		std::vector<i64> off_, ids_; std::vector<bwagpu_alnreg_t> regs_;
+		if (!host_off) { off_.resize((size_t)n_pairs * 2); e = hipMemcpyAsync(off_.data(), d_off, (size_t)n_pairs * 2 * 8, hipMemcpyDeviceToHost, h->stream); host_off = off_.data(); }
+		if (e == hipSuccess && !host_regs) { regs_.resize((size_t)(tot ? tot : 1)); if (tot) e = hipMemcpyAsync(regs_.data(), d_regs, (size_t)tot * sizeof(bwagpu_alnreg_t), hipMemcpyDeviceToHost, h->stream); host_regs = regs_.data(); }
+		if (e == hipSuccess) e = wait_stream(h);
+		if (e != hipSuccess) { bwagpu_free(res); HIPCHK(h, e); }
+		for (int p = 0; p < n_pairs; ++p) {
+			if (!(res[p].flags & 1)) continue;
+			const i64 o0 = host_off[2 * (size_t)p], o1 = host_off[2 * (size_t)p + 1];
+			res[p] = pair_host(*opt, pes, h->l_pac, h->h_ctg_off, host_regs + o0, host_src ? host_src + o0 : nullptr, host_npri[2 * (size_t)p], host_regs + o1, host_src ? host_src + o1 : nullptr,
+							   host_npri[2 * (size_t)p + 1], (int)(host_ids ? host_ids[p] : id0 + p));
+		}
+	}
+	*out = res;
+	return BWAGPU_OK;
+}
+
+extern "C" int bwagpu_batch_pair(bwagpu_t *h, const bwagpu_opt_t *opt, const bwagpu_pestat_t pes[4], int64_t id0, bwagpu_pair_t **pairs, int64_t *n_pairs,
+								 bwagpu_primary_t **pri, int64_t *n_pri_recs, int32_t *n_pri, float *kernel_ms)
+{
+	if (!h || !opt || !pes || !h->ran || !h->downloaded || !pairs || !n_pairs) return BWAGPU_EINVAL;
+	if ((h->n_reads & 1) || (id0 & 1) || (opt->flag & 0x800 /* MEM_F_PRIMARY5 */)) return BWAGPU_EINVAL;
+	*pairs = nullptr; *n_pairs = 0;
+	if (pri) *pri = nullptr;
+	if (n_pri_recs) *n_pri_recs = 0;
+	const int np = h->n_reads / 2;
+	bwagpu_primary_t *recs = nullptr; int64_t n_recs = 0; float ms_pri = 0.f, ms_pair = 0.f;
+	std::vector<i32> npri((size_t)h->n_reads);
+	int rc = bwagpu_batch_primary(h, opt, id0, &recs, &n_recs, npri.data(), &ms_pri);
+	if (rc != BWAGPU_OK) return rc;
+	const BusyGuard busy(h->ibuf->busy);
+	if (hipSetDevice(h->device) != hipSuccess) { bwagpu_free(recs); h->err = "hipSetDevice failed"; return BWAGPU_EHIP; }
+	bwagpu_pair_t *res = nullptr;
+	if (n_recs == 0) {      // no region in the whole batch: every pair is without a candidate (and the packed arrays may not exist)
+		res = (bwagpu_pair_t*)result_alloc((size_t)(np ? np : 1) * sizeof(bwagpu_pair_t));
+		if (!res) { bwagpu_free(recs); return BWAGPU_ENOMEM; }
+		for (int p = 0; p < np; ++p) { res[p].score = res[p].sub = res[p].n_sub = 0; res[p].z[0] = res[p].z[1] = -1; res[p].flags = 0; res[p].n_cand = 0; }
+	} else {
+		i64 max_sum = 0;
+		for (int p = 0; p < np; ++p) { const i64 s = (i64)npri[2 * (size_t)p] + npri[2 * (size_t)p + 1]; if (s > max_sum) max_sum = s; }
+		rc = pair_run(h, opt, pes, np, n_recs, max_sum, h->d_pri_npri.as<i32>(), h->d_pack_off.as<i64>(), h->d_regs_packed.as<bwagpu_alnreg_t>(), h->d_pri_out.as<bwagpu_primary_t>(), nullptr, id0 >> 1,
+					  npri.data(), nullptr, nullptr, recs, nullptr, &res, &ms_pair);
+		if (rc != BWAGPU_OK) { bwagpu_free(recs); return rc; }
+	}
+	*pairs = res; *n_pairs = np;
+	if (n_pri) memcpy(n_pri, npri.data(), (size_t)h->n_reads * 4);
+	if (kernel_ms) *kernel_ms = ms_pri + ms_pair;
+	if (pri) { *pri = recs; if (n_pri_recs) *n_pri_recs = n_recs; } else bwagpu_free(recs);
+	return BWAGPU_OK;
+}
+
+extern "C" int bwagpu_pair_flat(bwagpu_t *h, const bwagpu_opt_t *opt, const bwagpu_pestat_t pes[4], int n_pairs, const int32_t *counts, const int32_t *n_pri,
+								const bwagpu_alnreg_t *regs, const int64_t *ids, bwagpu_pair_t **pairs, float *kernel_ms)
+{
+	if (!h || !opt || !pes || n_pairs < 0 || n_pairs > 0x3fffffff || !pairs || (n_pairs > 0 && (!counts || !n_pri || !ids))) return BWAGPU_EINVAL;
+	const size_t n_reads = (size_t)n_pairs * 2;
+	std::vector<i64> off(n_reads ? n_reads : 1);
+	i64 tot = 0, max_sum = 0;
+	for (size_t i = 0; i < n_reads; ++i) {
+		if (counts[i] < 0 || counts[i] > 0x3fffffff || n_pri[i] < 0 || n_pri[i] > counts[i] || (counts[i] > 0 && !regs)) return BWAGPU_EINVAL;
+		off[i] = tot;
+		for (int k = 0; k < n_pri[i]; ++k) if (regs[tot + k].rid < 0 || regs[tot + k].rid >= h->n_seqs) return BWAGPU_EINVAL;
+		tot += counts[i];
+		if (i & 1) { const i64 s = (i64)n_pri[i - 1] + n_pri[i]; if (s > max_sum) max_sum = s; }
+	}
+	const BusyGuard busy(h->ibuf->busy);
+	HIPCHK(h, hipSetDevice(h->device));
+	*pairs = nullptr;
+	if (n_pairs && (h->d_pair_npri.ensure(n_reads * 4) || h->d_pf_off.ensure(n_reads * 8) || h->d_pf_ids.ensure((size_t)n_pairs * 8) || h->d_pf_regs.ensure((size_t)(tot ? tot : 1) * sizeof(bwagpu_alnreg_t)))) {
+		h->err = "hipMalloc failed (pair)"; return BWAGPU_ENOMEM;
+	}
+	if (n_pairs) {
+		HIPCHK(h, hipMemcpyAsync(h->d_pair_npri.p, n_pri, n_reads * 4, hipMemcpyHostToDevice, h->stream));
+		HIPCHK(h, hipMemcpyAsync(h->d_pf_off.p, off.data(), n_reads * 8, hipMemcpyHostToDevice, h->stream));
+		HIPCHK(h, hipMemcpyAsync(h->d_pf_ids.p, ids, (size_t)n_pairs * 8, hipMemcpyHostToDevice, h->stream));
+		if (tot) HIPCHK(h, hipMemcpyAsync(h->d_pf_regs.p, regs, (size_t)tot * sizeof(bwagpu_alnreg_t), hipMemcpyHostToDevice, h->stream));
+		HIPCHK(h, wait_stream(h));      // (`off` is a local array)
+	}
+	return pair_run(h, opt, pes, n_pairs, tot, max_sum, h->d_pair_npri.as<i32>(), h->d_pf_off.as<i64>(), h->d_pf_regs.as<bwagpu_alnreg_t>(), nullptr, h->d_pf_ids.as<i64>(), 0,
+					n_pri, off.data(), regs, nullptr, ids, pairs, kernel_ms);
 }
 
 extern "C" int bwagpu_align_flat(bwagpu_t *h, const bwagpu_opt_t *opt, int n, const uint8_t *seqs, const int64_t *off,

@@ -56,6 +56,7 @@
 	X(cig_long,          1)    /* CIGAR stage: the long-segment tier (k_cigar_long)                                                                     */ \
 	X(cigl_mib,          32768)/* CIGAR stage: scratch budget of that tier in MiB (32 GiB: 1024 direction matrices of a 10 kb read's widest band)                                                                      */ \
 	X(pri_log_cap,       0)    /* marking + mapQ stage: entries of the table of logarithms (0: from the batch; test hook: a tiny table sends the mapQs to the host side of the call) */ \
+	X(pair_tab_cap,      0)    /* pairing stage: entries of the table of log(2 erfc) values over the insert-size windows (0: 262144, enough for four windows of max_ins = 10000; test hook: a tiny table sends the pairs to the host side of the call) */ \
 	X(cig_trace,         0)    /* CIGAR stage: print the launches' times (waits for the stream after each)                                              */ \
 	X(debug_sync,        0)    /* wait and report after every stage of bwagpu_batch_run                                                                 */ \
 	X(reserve_results,   1)    /* bwagpu_batch_reserve also page-locks the result blocks of a batch of that shape (0: the first download does; A/B)      */ \

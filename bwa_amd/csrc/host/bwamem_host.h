@@ -78,7 +78,9 @@ struct Read {   // == bseq1_t as the finalize code needs it
 	const CigHints *hints = nullptr;
 	const bwagpu_matesw_t *msw = nullptr; int n_msw = 0;   // device-computed mate-rescue alignments of this read (bwagpu_batch_matesw)
 	const bwagpu_primary_t *pri = nullptr;                 // device-computed marking and mapQ of this read's regions (bwagpu_batch_primary): one record per region
+	const bwagpu_pair_t *pair = nullptr;                   // first read of a pair: the device's mem_pair record of the pair as downloaded (bwagpu_batch_pair); both reads then have `pri`
 };
+extern std::atomic<long> g_pairs_from_device;             // pairs whose marking and mem_pair result sam_pe took from the device's records
 
 typedef std::vector<bwagpu_alnreg_t> Regs;
 

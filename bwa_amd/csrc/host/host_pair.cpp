@@ -267,6 +267,8 @@ int64_t host_matesw_records(const bwagpu_opt_t &opt, const RefSeqs &ref, int n, 
 	return nout;
 }
 
+std::atomic<long> g_pairs_from_device(0);
+
 // ---- pairing (mem_pair, bwamem_pair.c:208-274) --------------------------------------------------------------------------------
 static int pair_ends(const bwagpu_opt_t &opt, const RefSeqs &ref, const Pestat pes[4], const Regs a[2], int id, int *sub, int *n_sub, int z[2], const int n_pri[2])
 {
@@ -332,7 +334,7 @@ static inline int raw_mapq(int diff, int a) { return (int)(6.02 * diff / a + .49
 // ---- mem_sam_pe (bwamem_pair.c:276-419) ------------------------------------------------------------------------------------
 int sam_pe(const bwagpu_opt_t &opt, const RefSeqs &ref, const Pestat pes[4], uint64_t id, const Read s[2], Regs a[2], SamText *const outp[2], const char *rg_id)
 {
-	int n = 0, z[2] = {0, 0}, o, subo, n_sub, extra_flag = 1, n_pri[2];
+	int n = 0, z[2] = {0, 0}, o = 0, subo = 0, n_sub = 0, extra_flag = 1, n_pri[2];
 	Aln h[2];
 	SamText &out0 = *outp[0], &out1 = *outp[1];
 	out0.reserve(out0.size() + 2 * (size_t)s[0].l_seq + 320); out1.reserve(out1.size() + 2 * (size_t)s[1].l_seq + 320);      // one allocation instead of the five a growing string makes
@@ -346,12 +348,29 @@ int sam_pe(const bwagpu_opt_t &opt, const RefSeqs &ref, const Pestat pes[4], uin
 			for (int j = 0; j < (int)b[i].size() && j < opt.max_matesw; ++j)
 				n += matesw(opt, ref, pes, b[i][j], s[!i].l_seq, s[!i].seq, a[!i], s[!i].msw, s[!i].n_msw);
 	}
-	n_pri[0] = mark_primary_se(opt, a[0], (int64_t)(id << 1 | 0));
-	n_pri[1] = mark_primary_se(opt, a[1], (int64_t)(id << 1 | 1));
+	// The device's records of the pair (bwagpu_batch_pair) describe the lists as downloaded: they stand for the marking and for pair_ends when the rescue loop
+	// has aligned nothing (no hit was added), no reordering comes between the two (F_PRIMARY5) and the record is the device's own (unflagged).
+	const bwagpu_pair_t *dev = n == 0 && s[0].pair && s[0].pri && s[1].pri && !(opt.flag & F_PRIMARY5) && !(s[0].pair->flags & 1) ? s[0].pair : nullptr;
+	if (dev) {
+		thread_local std::vector<int32_t> mq;
+		for (int i = 0; i < 2; ++i) {
+			apply_primary(a[i], s[i].pri, (int64_t)(id << 1 | (uint64_t)i), mq);
+			n_pri[i] = 0;
+			for (size_t j = 0; j < a[i].size(); ++j) n_pri[i] += a[i][j].is_alt == 0;
+		}
+		++g_pairs_from_device;
+	} else {
+		n_pri[0] = mark_primary_se(opt, a[0], (int64_t)(id << 1 | 0));
+		n_pri[1] = mark_primary_se(opt, a[1], (int64_t)(id << 1 | 1));
+	}
 	if (opt.flag & F_PRIMARY5) { reorder_primary5(opt.T, a[0]); reorder_primary5(opt.T, a[1]); }
 	bool no_pairing = (opt.flag & F_NOPAIRING) != 0;
 	if (!no_pairing) {
-		if (n_pri[0] && n_pri[1] && (o = pair_ends(opt, ref, pes, a, (int)id, &subo, &n_sub, z, n_pri)) > 0) {
+		if (n_pri[0] && n_pri[1] && dev) {
+			o = dev->score; subo = dev->sub; n_sub = dev->n_sub;
+			if (dev->n_cand > 0) { z[0] = dev->z[0]; z[1] = dev->z[1]; }
+		}
+		if (n_pri[0] && n_pri[1] && (dev ? o : (o = pair_ends(opt, ref, pes, a, (int)id, &subo, &n_sub, z, n_pri))) > 0) {
 			int is_multi[2], q_pe, score_un, q_se[2];
 			for (int i = 0; i < 2; ++i) {
 				int j;

@@ -39,6 +39,7 @@ using namespace hostmem;
 static int g_verbose = 3;
 static int g_device_matesw = 1;   // BWAGPU_CLI_MATESW=0: the host runs every mate-rescue alignment itself (same output)
 static int g_device_cigars = 1;   // BWAGPU_CLI_CIGARS=0: the host computes every CIGAR itself (same output)
+static int g_device_pair = 0;     // BWAGPU_CLI_PAIR=1: paired-end batches take the marking and mem_pair of the pairs the rescue loop leaves alone from the device (bwagpu_batch_pair; same output)
 static int g_device_primary = 0;  // BWAGPU_CLI_PRIMARY=1: single-end batches take primary/secondary marking and mapQ from the device (bwagpu_batch_primary; same output)
 static std::atomic<long> g_n_primary_reads(0);   // ... reads finalized from such records (the BWAGPU_CLI_TRACE line at the end of the run)
 
@@ -342,7 +343,8 @@ struct Sub {      // one mem_process_seqs call (bwamem.c:1235-1264) on the reads
 	bwagpu_cigar_t *cigs = nullptr;           // device-side global alignments of the regions (bwagpu_batch_cigars)
 	uint32_t *cig_ops = nullptr;              // ... and the operation array its records with more than 6 operations point into
 	bwagpu_matesw_t *msw = nullptr; int64_t n_msw = 0;   // device-side mate-rescue alignments (bwagpu_batch_matesw)
-	bwagpu_primary_t *pri = nullptr;          // device-side marking + mapQ records of the regions, in each read's marked order (bwagpu_batch_primary; single-end)
+	bwagpu_primary_t *pri = nullptr;          // device-side marking + mapQ records of the regions, in each read's marked order (bwagpu_batch_primary; single-end, or paired-end with bwagpu_batch_pair)
+	bwagpu_pair_t *pairs = nullptr;           // device-side mem_pair records of the pairs as downloaded (bwagpu_batch_pair)
 	Pestat pes[4]; bool have_pes = false;     // insert-size windows, when they had to be computed before the finalize stage
 	double t_dev = 0;
 };
@@ -404,7 +406,7 @@ static void device_sub(const std::vector<bwagpu_t*> &gpus, Sub &u, const RefSeqs
 	int D = (int)gpus.size();
 	const int units = pe ? n / 2 : n, per = pe ? 2 : 1;
 	if (D > units) D = units > 0 ? units : 1;
-	struct Shard { int lo = 0, hi = 0; std::vector<int64_t> off; bwagpu_alnreg_t *all = nullptr; int64_t tot = 0; bwagpu_cigar_t *cigs = nullptr; uint32_t *ops = nullptr; int64_t n_ops = 0; bwagpu_matesw_t *msw = nullptr; int64_t n_msw = 0; bwagpu_primary_t *pri = nullptr; };
+	struct Shard { int lo = 0, hi = 0; std::vector<int64_t> off; bwagpu_alnreg_t *all = nullptr; int64_t tot = 0; bwagpu_cigar_t *cigs = nullptr; uint32_t *ops = nullptr; int64_t n_ops = 0; bwagpu_matesw_t *msw = nullptr; int64_t n_msw = 0; bwagpu_primary_t *pri = nullptr; bwagpu_pair_t *pairs = nullptr; };
 	std::vector<Shard> sh((size_t)D);
 	for (int d = 0; d < D; ++d) {
 		sh[d].lo = (int)((int64_t)units * d / D) * per; sh[d].hi = d + 1 == D ? n : (int)((int64_t)units * (d + 1) / D) * per;
@@ -514,6 +516,28 @@ static void device_sub(const std::vector<bwagpu_t*> &gpus, Sub &u, const RefSeqs
 	}
 	t4 = now_s();
 	if (pes_thread.joinable()) pes_thread.join();
+	// mem_pair of the pairs as downloaded, and the marking of their ends, on the device too: the windows are known here.  Read i of the batch has id
+	// n_processed + i (mem_sam_pe: id << 1 | r with id = (n_processed + i) >> 1); a shard starts at an even read.
+	if (g_device_pair && pe && u.have_pes && !(u.opt.flag & (F_PRIMARY5 | F_NOPAIRING)) && !(u.n_processed & 1) && u.tot > 0) {
+		bwagpu_pestat_t dp[4];
+		for (int d = 0; d < 4; ++d) { memset(&dp[d], 0, sizeof dp[d]); dp[d].low = u.pes[d].low; dp[d].high = u.pes[d].high; dp[d].failed = u.pes[d].failed; dp[d].avg = u.pes[d].avg; dp[d].std = u.pes[d].std; }
+		on_devices([&](int d) {
+			Shard &s = sh[d];
+			if (s.tot == 0) return;
+			int64_t np = 0, nr = 0;
+			int rc = bwagpu_batch_pair(gpus[d], &u.opt, dp, u.n_processed + s.lo, &s.pairs, &np, &s.pri, &nr, nullptr, nullptr);
+			if (rc != BWAGPU_OK || nr != s.tot || np != (s.hi - s.lo) / 2) device_fail(gpus[d], rc, "bwagpu_batch_pair returned another number of records than bwagpu_batch_download");
+		});
+		u.pri = (bwagpu_primary_t*)malloc((size_t)u.tot * sizeof(bwagpu_primary_t));
+		u.pairs = (bwagpu_pair_t*)malloc((size_t)(n / 2 + 1) * sizeof(bwagpu_pair_t));
+		if (!u.pri || !u.pairs) { fprintf(stderr, "[E::%s] out of memory\n", "mem_process_seqs"); exit(EXIT_FAILURE); }
+		int64_t k = 0;
+		for (auto &s : sh) {      // (a record names its region by the index within its read: nothing moves with the shard; a shard without regions has only pairs without a candidate)
+			if (s.tot) { memcpy(u.pri + k, s.pri, (size_t)s.tot * sizeof(bwagpu_primary_t)); memcpy(u.pairs + s.lo / 2, s.pairs, (size_t)((s.hi - s.lo) / 2) * sizeof(bwagpu_pair_t)); }
+			else for (int p = s.lo / 2; p < s.hi / 2; ++p) { bwagpu_pair_t &r = u.pairs[p]; memset(&r, 0, sizeof r); r.z[0] = r.z[1] = -1; }
+			k += s.tot; bwagpu_free(s.pri); s.pri = nullptr; bwagpu_free(s.pairs); s.pairs = nullptr;
+		}
+	}
 	if (want_matesw) {
 		bwagpu_pes_t dp[4];
 		for (int d = 0; d < 4; ++d) { dp[d].low = u.pes[d].low; dp[d].high = u.pes[d].high; dp[d].failed = u.pes[d].failed; dp[d].pad_ = 0; }
@@ -561,6 +585,7 @@ static void finalize_sub(const RefSeqs &ref, Work &w, Sub &u, const Pestat *pes0
 		reads[i].comment = copy_comment && q.has_comment ? T + q.comment : nullptr;
 		reads[i].seq = u.flat.data() + u.off[i]; reads[i].qual = q.has_qual ? T + q.qual : nullptr; reads[i].l_seq = q.l_seq;
 		if (u.pri) reads[i].pri = u.pri + roff[i];
+		if (u.pairs && !(i & 1)) reads[i].pair = u.pairs + (i >> 1);
 	});
 	if (u.opt.flag & F_PE) for (int i = 0; i + 1 < n; i += 2) if (strcmp(reads[i].name, reads[i + 1].name) != 0) { fprintf(stderr, "[mem_sam_pe] paired reads have different names: \"%s\", \"%s\"\n", reads[i].name, reads[i + 1].name); exit(EXIT_FAILURE); }
 	std::vector<bwagpu_matesw_t> msw_sorted;
@@ -573,6 +598,7 @@ static void finalize_sub(const RefSeqs &ref, Work &w, Sub &u, const Pestat *pes0
 		finalize_batch(u.opt, ref, u.n_processed, n, reads.data(), u.all, roff.data(), pes, u.opt.n_threads, rg_id, sam, g_verbose >= 3);
 		for (int i = 0; i < n; ++i) w.out[u.idx[i]].swap(sam[i]);
 	}
+	if (u.pairs) { free(u.pairs); u.pairs = nullptr; free(u.pri); u.pri = nullptr; }
 	if (u.pri) { g_n_primary_reads += n; bwagpu_free(u.pri); u.pri = nullptr; }
 	bwagpu_free(u.all); u.all = nullptr; bwagpu_free(u.cigs); u.cigs = nullptr; bwagpu_free(u.cig_ops); u.cig_ops = nullptr; bwagpu_free(u.msw); u.msw = nullptr;
 	if (g_verbose >= 3) fprintf(stderr, "[M::%s] Processed %d reads in %.3f real sec\n", "mem_process_seqs", n, u.t_dev + (now_s() - t0));
@@ -838,6 +864,7 @@ int main(int argc, char *argv[])
 	if (getenv("BWAGPU_CLI_MATESW")) g_device_matesw = atoi(getenv("BWAGPU_CLI_MATESW"));
 	if (getenv("BWAGPU_CLI_CIGARS")) g_device_cigars = atoi(getenv("BWAGPU_CLI_CIGARS"));
 	if (getenv("BWAGPU_CLI_PRIMARY")) g_device_primary = atoi(getenv("BWAGPU_CLI_PRIMARY"));
+	if (getenv("BWAGPU_CLI_PAIR")) g_device_pair = atoi(getenv("BWAGPU_CLI_PAIR"));
 	int n_dev = getenv("BWAGPU_CLI_STREAMS") ? atoi(getenv("BWAGPU_CLI_STREAMS")) : 3;      // batches in flight on the device
 	if (n_dev < 1) n_dev = 1;
 	// devices: BWAGPU_DEVICES=0,1,... (default: the one of BWAGPU_DEVICE).  The index reaches the other devices by device-to-device copies over
@@ -1038,6 +1065,7 @@ int main(int argc, char *argv[])
 	to_out.close();
 	writer.join();
 	all_done = true; watchdog.join();
+	if (g_device_pair && tl_trace) fprintf(stderr, "[D::main_mem] %ld pairs paired from device records (BWAGPU_CLI_PAIR)\n", hostmem::g_pairs_from_device.load());
 	if (g_device_primary && tl_trace) fprintf(stderr, "[D::main_mem] %ld reads finalized from device primary/mapQ records (BWAGPU_CLI_PRIMARY)\n", g_n_primary_reads.load());
 	if (g_verbose >= 3) { const double dt = now_s() - t_start; fprintf(stderr, "[M::%s] %ld reads in %.3f sec after the index was loaded: %.0f reads/s\n", "main_mem", n_reads_total.load(), dt, dt > 0 ? n_reads_total.load() / dt : 0.);
 		fprintf(stderr, "[M::%s] stage busy time: read %.3f s, encode %.3f s, device %.3f s (over %d handles), finalize %.3f s, write %.3f s\n", "main_mem", busy_read, busy_enc, busy_dev_us.load() * 1e-6, n_work, busy_fin, busy_write);

@@ -43,6 +43,11 @@ PRIMARY_DTYPE = np.dtype([("src", "<i4"), ("secondary", "<i4"), ("secondary_all"
                           ("mapq", "<i4"), ("flags", "<i4")])
 assert PRIMARY_DTYPE.itemsize == 32
 
+# bwagpu_pestat_t == mem_pestat_t (4 bytes of padding before the doubles), bwagpu_pair_t: mem_pair's results for one pair (bwagpu_batch_pair / bwagpu_pair_flat)
+PESTAT_DTYPE = np.dtype({"names": ["low", "high", "failed", "avg", "std"], "formats": ["<i4", "<i4", "<i4", "<f8", "<f8"], "offsets": [0, 4, 8, 16, 24], "itemsize": 32})
+PAIR_DTYPE = np.dtype([("score", "<i4"), ("sub", "<i4"), ("n_sub", "<i4"), ("z", "<i4", (2,)), ("flags", "<i4"), ("n_cand", "<i8")])
+assert PESTAT_DTYPE.itemsize == 32 and PAIR_DTYPE.itemsize == 32
+
 INTV_DTYPE = np.dtype([("x0", "<u8"), ("x1", "<u8"), ("x2", "<u8"), ("info", "<u8")])
 SEED_DTYPE = np.dtype([("rbeg", "<i8"), ("qbeg", "<i4"), ("len", "<i4"), ("score", "<i4"), ("_pad", "<i4")])
 CHAIN_HDR_DTYPE = np.dtype([("n", "<i4"), ("rid", "<i4"), ("w", "<i4"), ("kept", "<i4"), ("is_alt", "<i4"),
@@ -54,7 +59,7 @@ class MemPestat(C.Structure):
     _fields_ = [("low", C.c_int), ("high", C.c_int), ("failed", C.c_int), ("avg", C.c_double), ("std", C.c_double)]
 
 
-assert C.sizeof(MemPestat) == 32
+assert C.sizeof(MemPestat) == 32 == PESTAT_DTYPE.itemsize and MemPestat.avg.offset == 16
 
 
 def default_opt() -> MemOpt:

@@ -302,6 +302,32 @@ int bwagpu_primary_flat(bwagpu_t *h, const bwagpu_opt_t *opt, int n_reads, const
  * does with its small LDS area, [2] with its large one (reads with more work in HBM scratch), [3] entries of the kept list compared per step. */
 void bwagpu_primary_limits(int32_t out[4]);
 
+/* Pairing of the two ends' hits on the device: mem_pair (bwamem_pair.c:208-269), the next thing worker2 does with a pair once both ends are marked. */
+typedef struct { int32_t low, high, failed; double avg, std; } bwagpu_pestat_t;   /* == mem_pestat_t (bwamem.h:108-112), 32 bytes */
+typedef struct {
+	int32_t score, sub, n_sub;  /* mem_pair's return value, *sub and *n_sub */
+	int32_t z[2];               /* places of the best pair's hits in the two ends' marked lists; {-1, -1} when there is no candidate (the reference leaves z untouched) */
+	int32_t flags;              /* bit 0: a distance was outside the handle's table of log(2 erfc) values (option pair_tab_cap); the host side of the call then computed the record (it is right either way) */
+	int64_t n_cand;             /* number of candidate pairs (u.n) */
+} bwagpu_pair_t;
+/* After bwagpu_batch_download of a batch whose reads 2p and 2p + 1 are mates: the marking kernels of bwagpu_batch_primary on the downloaded lists (read i
+ * has id id0 + i; id0 must be even), then mem_pair of every pair on the device-resident records: place i of a read is region `src` of its i-th record, the
+ * first n_pri places of each end take part, and pair p has id (id0 >> 1) + p truncated to int, as mem_sam_pe passes it (bwamem_pair.c:349-354).
+ * *pairs: *n_pairs records, free with bwagpu_free.  pri / n_pri_recs (may be NULL) receive bwagpu_batch_primary's records (free with bwagpu_free), n_pri
+ * (may be NULL) its return values, *kernel_ms (may be NULL) the device time of all kernels.  A pair one of whose ends has no primary-assembly hit gets the
+ * no-candidate record (mem_sam_pe does not call mem_pair then).  BWAGPU_EINVAL: before a download, an odd number of reads, an odd id0, MEM_F_PRIMARY5 in
+ * opt->flag (mem_reorder_primary5 between marking and pairing is not on the device), NULL h / opt / pes / pairs / n_pairs. */
+int bwagpu_batch_pair(bwagpu_t *h, const bwagpu_opt_t *opt, const bwagpu_pestat_t pes[4], int64_t id0, bwagpu_pair_t **pairs, int64_t *n_pairs,
+					  bwagpu_primary_t **pri, int64_t *n_pri_recs, int32_t *n_pri, float *kernel_ms);
+/* The same kernels on lists the caller has already marked (reads 2p, 2p + 1: counts[] regions each, concatenated in regs; the first n_pri[] of each take
+ * part, the rest are ignored; ids[p] the pair's id) -- for a finalize stage that pairs after it has merged rescued hits.  Of a region rb, rid and score are
+ * read.  *pairs: n_pairs records, free with bwagpu_free.  BWAGPU_EINVAL also for n_pri outside [0, counts] and a rid outside the index. */
+int bwagpu_pair_flat(bwagpu_t *h, const bwagpu_opt_t *opt, const bwagpu_pestat_t pes[4], int n_pairs, const int32_t *counts, const int32_t *n_pri,
+					 const bwagpu_alnreg_t *regs, const int64_t *ids, bwagpu_pair_t **pairs, float *kernel_ms);
+/* The numbers of hits of both ends at which the pairing kernels change their form, as compiled: out[0] up to which one lane does a pair, [1] up to which a
+ * wavefront does with its small LDS area, [2] with its large one (pairs with more work in HBM scratch). */
+void bwagpu_pair_limits(int32_t out[3]);
+
 /* ---- index construction on the device -------------------------------------------------------- */
 /* The arrays `bwa index` leaves in bwt_t after bwt_bwtgen2/bwt_pac2bwt + bwt_bwtupdate_core + bwt_cal_sa
  * (bwtindex.c:64-120, 150-172; bwt.c:62-84), built from the 2-bit packed forward strand by a suffix sort in HBM
