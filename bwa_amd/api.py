@@ -16,7 +16,7 @@ try:   # torch bundles its own HIP runtime (libamdhip64); loading it first keeps
 except Exception:  # pragma: no cover
     torch = None
 
-from .structs import ALNREG_DTYPE, PAIR_DTYPE, PESTAT_DTYPE, PRIMARY_DTYPE, MemOpt
+from .structs import ALNREG_DTYPE, PAIR_DTYPE, PESTAT_DTYPE, PRIMARY_DTYPE, RESCUE_DTYPE, MemOpt
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 DEFAULT_LIB = os.path.join(HERE, "csrc", "libbwagpu.so")
@@ -60,7 +60,7 @@ EXPORTS = [
     "bwagpu_free", "bwagpu_batch_upload", "bwagpu_batch_run", "bwagpu_batch_download", "bwagpu_set_taps", "bwagpu_tap_intervals",
     "bwagpu_tap_chains", "bwagpu_tap_regs_raw", "bwagpu_index_buffers", "bwagpu_index_export", "bwagpu_clone", "bwagpu_index_ready",
     "bwagpu_batch_cigars", "bwagpu_batch_cigar_ops", "bwagpu_debug_phase", "bwagpu_batch_matesw", "bwagpu_clone_to_device", "bwagpu_index_build", "bwagpu_built_free", "bwagpu_abi_sizes", "bwagpu_debug_prof", "bwagpu_debug_hist", "bwagpu_debug_seed_x2", "bwagpu_debug_chain_hist", "bwagpu_debug_dp", "bwagpu_debug_sort", "bwagpu_debug_sort_limits", "bwagpu_set_cigar_filter", "bwagpu_batch_reserve", "bwagpu_batch_footprint", "bwagpu_mem_info",
-    "bwagpu_batch_primary", "bwagpu_primary_flat", "bwagpu_primary_limits", "bwagpu_batch_pair", "bwagpu_pair_flat", "bwagpu_pair_limits",
+    "bwagpu_batch_primary", "bwagpu_primary_flat", "bwagpu_primary_limits", "bwagpu_batch_pair", "bwagpu_pair_flat", "bwagpu_pair_limits", "bwagpu_batch_rescue", "bwagpu_rescue_flat", "bwagpu_rescue_limits",
     "bwagpu_trim", "bwagpu_set_option", "bwagpu_get_option", "bwagpu_set_default_option", "bwagpu_clear_default_options", "bwagpu_option_name",
 ]
 
@@ -115,6 +115,9 @@ def load_library(path: str | None = None) -> C.CDLL:
     L.bwagpu_batch_pair.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.bwagpu_pair_flat.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.bwagpu_pair_limits.restype = None
+    L.bwagpu_batch_rescue.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 9
+    L.bwagpu_rescue_flat.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 14
+    L.bwagpu_rescue_limits.restype = None
     L.bwagpu_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_longlong]
     L.bwagpu_get_option.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p]
     L.bwagpu_set_default_option.argtypes = [C.c_char_p, C.c_longlong]
@@ -329,6 +332,51 @@ class BwaGpu:
         out = (C.c_int32 * 3)()
         self.L.bwagpu_pair_limits(out)
         return dict(zip(("lane_max", "lds_small", "lds_big"), list(out)))
+
+    def _rescue_out(self, n, counts, pr, ps, nr, prec, ppri, n_pri, ppair, ms, want_pri, want_pairs):
+        out = dict(counts=counts, regs=self._take(pr, nr.value, ALNREG_DTYPE), src=self._take(ps, nr.value, np.dtype("<i4")), rescue=self._take(prec, n // 2, RESCUE_DTYPE), ms=ms.value)
+        if want_pri:
+            out["pri"] = self._take(ppri, nr.value, PRIMARY_DTYPE); out["n_pri"] = n_pri
+        if want_pairs:
+            out["pairs"] = self._take(ppair, n // 2, PAIR_DTYPE)
+        return out
+
+    def rescue(self, opt: MemOpt, pes: np.ndarray, id0: int = 0, pri: bool = True, pairs: bool = True) -> dict:
+        """bwagpu_batch_rescue: mem_matesw's decision loop and merge for every pair (reads 2p, 2p + 1) of the last download() on the device, then (pri) the marking of the
+        merged lists and (pairs) mem_pair on those records; pes = PESTAT_DTYPE[4], read i has id id0 + i (id0 even).  -> dict: counts int32[n reads], regs (the merged lists),
+        src int32 per merged region (index in the downloaded list, or -1 - (j << 2 | r) for a rescued hit), rescue RESCUE_DTYPE[n pairs], ms; pri, n_pri; pairs."""
+        pes = np.ascontiguousarray(pes, dtype=PESTAT_DTYPE)
+        assert pes.shape == (4,)
+        counts, n_pri = np.zeros(self._n, dtype=np.int32), np.zeros(self._n, dtype=np.int32)
+        pr, ps, nr, prec, ppri, ppair, ms = C.c_void_p(), C.c_void_p(), C.c_int64(), C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_float()
+        self._chk(self.L.bwagpu_batch_rescue(self.h, C.byref(opt), pes.ctypes.data, int(id0), counts.ctypes.data, C.byref(pr), C.byref(ps), C.byref(nr), C.byref(prec),
+                                             C.byref(ppri) if pri else None, n_pri.ctypes.data if pri else None, C.byref(ppair) if pairs else None, C.byref(ms)))
+        return self._rescue_out(self._n, counts, pr, ps, nr, prec, ppri, n_pri, ppair, ms, pri, pairs)
+
+    def rescue_flat(self, opt: MemOpt, pes: np.ndarray, seqs: np.ndarray, off: np.ndarray, counts_in: np.ndarray, regs_in: np.ndarray, ids=None, pri: bool = True, pairs: bool = True) -> dict:
+        """bwagpu_rescue_flat: the same kernels on reads (nt4, read i at seqs[off[i]:off[i + 1]]) and region lists of the caller; ids: one per read (needed for pri / pairs)."""
+        pes = np.ascontiguousarray(pes, dtype=PESTAT_DTYPE)
+        seqs = np.ascontiguousarray(seqs, dtype=np.uint8); off = np.ascontiguousarray(off, dtype=np.int64)
+        counts_in = np.ascontiguousarray(counts_in, dtype=np.int32); regs_in = np.ascontiguousarray(regs_in, dtype=ALNREG_DTYPE)
+        n = counts_in.shape[0]
+        assert pes.shape == (4,) and n % 2 == 0 and off.shape == (n + 1,) and int(counts_in.sum()) == regs_in.shape[0]
+        if ids is None:
+            pri = pairs = False
+        else:
+            ids = np.ascontiguousarray(ids, dtype=np.int64)
+            assert ids.shape == (n,)
+        counts, n_pri = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
+        pr, ps, nr, prec, ppri, ppair, ms = C.c_void_p(), C.c_void_p(), C.c_int64(), C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_float()
+        self._chk(self.L.bwagpu_rescue_flat(self.h, C.byref(opt), pes.ctypes.data, n // 2, seqs.ctypes.data, off.ctypes.data, counts_in.ctypes.data, regs_in.ctypes.data,
+                                            ids.ctypes.data if ids is not None else None, counts.ctypes.data, C.byref(pr), C.byref(ps), C.byref(nr), C.byref(prec),
+                                            C.byref(ppri) if pri else None, n_pri.ctypes.data if pri else None, C.byref(ppair) if pairs else None, C.byref(ms)))
+        return self._rescue_out(n, counts, pr, ps, nr, prec, ppri, n_pri, ppair, ms, pri, pairs)
+
+    def rescue_limits(self) -> dict:
+        """bwagpu_rescue_limits: the capacities of a pair's larger end at which the rescue kernels change their form, as compiled."""
+        out = (C.c_int32 * 4)()
+        self.L.bwagpu_rescue_limits(out)
+        return dict(zip(("lane_max", "lds_max"), list(out)[:2]))
 
     def debug_dp(self, opt: MemOpt, kind: int, cases: np.ndarray, seqs: np.ndarray) -> np.ndarray:
         """bwagpu_debug_dp: one wavefront of a device DP routine per case (DP_CASE_DTYPE) -> int32[n_cases, 72]."""

@@ -40,6 +40,7 @@
 #include "dev_matesw.h"
 #include "dev_primary.h"
 #include "dev_pair.h"
+#include "dev_rescue.h"
 #include "dev_debug.h"
 
 #define BWAGPU_VERSION "bwagpu 0.1 (gfx950)"
@@ -99,6 +100,8 @@ struct bwagpu_s {
 	DevBuf d_pf_regs, d_pf_cnt, d_pf_off, d_pf_ids;                                       // ... and the uploaded lists of bwagpu_primary_flat
 	std::vector<double> pri_log; i64 pri_log_dev = 0;                                      // log((double)k) by the host's libm for k < size; entries resident in d_pri_log
 	DevBuf d_msw_tasks, d_msw_out, d_msw_pes, d_msw_scratch;
+	enum { RS_X, RS_TOFF, RS_TIX, RS_ARENA, RS_ASRC, RS_ACNT, RS_POFF, RS_REGS, RS_SRC, RS_OUT, RS_LISTS, RS_CTR, RS_KEYS, RS_STAGE, RS_SEQ, RS_SEQOFF, RS_IDS, RS_PAIRIDS, RS_CNT_IN, RS_OFF_IN, RS_REGS_IN, RS_N };
+	DevBuf d_rs[RS_N];      // bwagpu_batch_rescue / bwagpu_rescue_flat (dev_rescue.h): anchors x 4 per read and their prefix sums, the task table, the arena of working lists (regions, src, lengths), the packed merged lists (offsets, regions, src), records, the wavefront forms' pair lists and their lengths, HBM sort keys; bwagpu_rescue_flat's uploads
 	i64 cigl_z_cap = 0;                          // bytes per direction matrix of the long CIGAR tier's scratch (grows with the batches)
 	DevBuf d_cigl_z, d_cigl_ops, d_cigl_md, d_cigl_list;      // scratch of the long-segment CIGAR tier (k_cigar_long): direction matrices, operations, MD strings per workgroup
 	DevBuf d_cig_ext; i64 cig_ext_n = -1;   // operation array of the last bwagpu_batch_cigars (records with 7..64 operations point into it)
@@ -506,6 +509,7 @@ extern "C" void bwagpu_destroy(bwagpu_t *h)
 		&h->d_intv_n, &h->d_intv_off, &h->d_intv, &h->d_seed_n, &h->d_seed_off, &h->d_slot_pos, &h->d_slot_qbeg, &h->d_slot_len, &h->d_slot_rid, &h->d_slot_blob, &h->d_chain_n, &h->d_node_off,
 		&h->d_order, &h->d_bin_cnt, &h->d_seed_w, &h->d_seed_order, &h->d_nodes, &h->d_reg_off, &h->d_reg_cap_r, &h->d_reg_n_raw, &h->d_reg_n, &h->d_regs, &h->d_regs_raw, &h->d_dp_h, &h->d_dp_e, &h->d_minhsp };
 	for (DevBuf *b : all) b->release();
+	for (DevBuf &b : h->d_rs) b.release();
 	for (int i = 0; i < 8; ++i) if (h->ev[i]) (void)hipEventDestroy(h->ev[i]);
 	if (h->ev_wait) (void)hipEventDestroy(h->ev_wait);
 	if (h->stream) (void)hipStreamDestroy(h->stream);
@@ -1556,17 +1560,11 @@ extern "C" int bwagpu_batch_cigar_ops(bwagpu_t *h, uint32_t **ops, int64_t *n_op
 	return BWAGPU_OK;
 }
 
-extern "C" int bwagpu_batch_matesw(bwagpu_t *h, const bwagpu_opt_t *opt, const bwagpu_pes_t pes[4], bwagpu_matesw_t **out, int64_t *n_out)
+// The task kernels of mate rescue on n reads (reads 2p, 2p + 1 mates; sequences d_seq / d_seqoff, lists d_cnt / d_off / d_regs): k_matesw_tasks, then k_matesw_sw
+// on the *nt tasks it found, results in d_msw_out.  d_toff / d_tix: the table of dev_rescue.h, or null.  Returns with the alignment kernel in the stream.
+static int matesw_launch(bwagpu_t *h, const bwagpu_opt_t *opt, const bwagpu_pes_t pes[4], int n, const u8 *d_seq, const i64 *d_seqoff, const i32 *d_cnt, const i64 *d_off,
+						 const bwagpu_alnreg_t *d_regs, const i64 *d_toff, i32 *d_tix, i64 task_cap, unsigned long long *n_tasks_out)
 {
-	if (!h || !opt || !pes || !h->ran || h->packed_tot < 0 || !out || !n_out) return BWAGPU_EINVAL;
-	if (opt->e_del <= 0 || opt->e_ins <= 0 || (h->n_reads & 1)) return BWAGPU_EINVAL;
-	const BusyGuard busy(h->ibuf->busy);
-	static_assert(sizeof(bwagpu_matesw_t) == 56 && sizeof(MateTask) == 24 && sizeof(bwagpu_pes_t) == 16, "layout");
-	HIPCHK(h, hipSetDevice(h->device));
-	const int n = h->n_reads;
-	*out = nullptr; *n_out = 0;
-	if (n == 0 || h->packed_tot == 0) { *out = (bwagpu_matesw_t*)malloc(sizeof(bwagpu_matesw_t)); return *out ? BWAGPU_OK : BWAGPU_ENOMEM; }
-	const i64 task_cap = (i64)n * 2 + 1024;          // more candidates than this are simply left to the host
 	const int waves = 1024;
 	if (h->d_msw_tasks.ensure((size_t)task_cap * sizeof(MateTask)) || h->d_msw_out.ensure((size_t)task_cap * sizeof(bwagpu_matesw_t)) ||
 		h->d_msw_pes.ensure(4 * sizeof(bwagpu_pes_t)) || h->d_ctr.ensure(sizeof(Counters))) {
@@ -1577,22 +1575,45 @@ extern "C" int bwagpu_batch_matesw(bwagpu_t *h, const bwagpu_opt_t *opt, const b
 	HIPCHK(h, hipMemsetAsync(next, 0, 8, h->stream));
 	HIPCHK(h, hipMemcpyAsync(h->d_msw_pes.p, pes, 4 * sizeof(bwagpu_pes_t), hipMemcpyHostToDevice, h->stream));
 	int nb = (n / 2 + BLOCK - 1) / BLOCK; if (nb > 8192) nb = 8192; if (nb < 1) nb = 1;
-	hipLaunchKernelGGL(k_matesw_tasks, dim3(nb), dim3(BLOCK), 0, h->stream, h->ix, *opt, n, h->d_reg_n.as<i32>(), h->d_pack_off.as<i64>(), h->d_regs_packed.as<bwagpu_alnreg_t>(),
-					   h->d_msw_pes.as<bwagpu_pes_t>(), h->d_msw_tasks.as<MateTask>(), n_tasks, task_cap);
+	(void)hipEventRecord(h->ev[4], h->stream);      // (ev[4] .. ev[5]: the task kernel; ev[6]: ahead of the alignment kernel -- rescue_run's kernel time is the sum of its segments, not a span over its host waits)
+	hipLaunchKernelGGL(k_matesw_tasks, dim3(nb), dim3(BLOCK), 0, h->stream, h->ix, *opt, n, d_cnt, d_off, d_regs,
+					   h->d_msw_pes.as<bwagpu_pes_t>(), h->d_msw_tasks.as<MateTask>(), n_tasks, task_cap, d_toff, d_tix);
 	HIPCHK(h, hipGetLastError());
+	(void)hipEventRecord(h->ev[5], h->stream);
 	unsigned long long nt = 0;
 	HIPCHK(h, hipMemcpyAsync(&nt, n_tasks, 8, hipMemcpyDeviceToHost, h->stream));
 	HIPCHK(h, wait_stream(h));
 	if ((i64)nt > task_cap) nt = (unsigned long long)task_cap;
-	bwagpu_matesw_t *res = (bwagpu_matesw_t*)result_alloc((size_t)(nt ? nt : 1) * sizeof(bwagpu_matesw_t));
-	if (!res) return BWAGPU_ENOMEM;
+	(void)hipEventRecord(h->ev[6], h->stream);
 	if (nt) {
-		Batch B = {}; B.seq = h->d_seq.as<u8>(); B.off = h->d_off.as<i64>(); B.n_reads = n; B.max_len = h->max_len;
+		Batch B = {}; B.seq = const_cast<u8*>(d_seq); B.off = const_cast<i64*>(d_seqoff); B.n_reads = n;      // (k_matesw_sw reads the sequences and their offsets, nothing else of the batch)
 		const i64 want = ((i64)nt + 3) / 4;           // one wavefront per alignment, four per workgroup
 		hipLaunchKernelGGL(k_matesw_sw, dim3((unsigned)(want < waves / 4 * 8 ? want : waves / 4 * 8)), dim3(BLOCK), 0, h->stream, h->ix, *opt, B, h->d_msw_pes.as<bwagpu_pes_t>(), h->d_msw_tasks.as<MateTask>(), (i64)nt,
 						   h->d_msw_out.as<bwagpu_matesw_t>(), next);
-		hipError_t e = hipGetLastError();
-		if (e == hipSuccess) e = hipMemcpyAsync(res, h->d_msw_out.p, (size_t)nt * sizeof(bwagpu_matesw_t), hipMemcpyDeviceToHost, h->stream);
+		HIPCHK(h, hipGetLastError());
+	}
+	*n_tasks_out = nt;
+	return BWAGPU_OK;
+}
+
+extern "C" int bwagpu_batch_matesw(bwagpu_t *h, const bwagpu_opt_t *opt, const bwagpu_pes_t pes[4], bwagpu_matesw_t **out, int64_t *n_out)
+{
+	if (!h || !opt || !pes || !h->ran || h->packed_tot < 0 || !out || !n_out) return BWAGPU_EINVAL;
+	if (opt->e_del <= 0 || opt->e_ins <= 0 || (h->n_reads & 1)) return BWAGPU_EINVAL;
+	const BusyGuard busy(h->ibuf->busy);
+	static_assert(sizeof(bwagpu_matesw_t) == 56 && sizeof(MateTask) == 24 && sizeof(bwagpu_pes_t) == 16, "layout");
+	HIPCHK(h, hipSetDevice(h->device));
+	const int n = h->n_reads;
+	*out = nullptr; *n_out = 0;
+	if (n == 0 || h->packed_tot == 0) { *out = (bwagpu_matesw_t*)malloc(sizeof(bwagpu_matesw_t)); return *out ? BWAGPU_OK : BWAGPU_ENOMEM; }
+	unsigned long long nt = 0;
+	const int rc = matesw_launch(h, opt, pes, n, h->d_seq.as<u8>(), h->d_off.as<i64>(), h->d_reg_n.as<i32>(), h->d_pack_off.as<i64>(), h->d_regs_packed.as<bwagpu_alnreg_t>(), nullptr, nullptr,
+								 (i64)n * 2 + 1024 /* more candidates than this are simply left to the host */, &nt);
+	if (rc != BWAGPU_OK) { (void)wait_stream(h); return rc; }
+	bwagpu_matesw_t *res = (bwagpu_matesw_t*)result_alloc((size_t)(nt ? nt : 1) * sizeof(bwagpu_matesw_t));
+	if (!res) { (void)wait_stream(h); return BWAGPU_ENOMEM; }
+	if (nt) {
+		hipError_t e = hipMemcpyAsync(res, h->d_msw_out.p, (size_t)nt * sizeof(bwagpu_matesw_t), hipMemcpyDeviceToHost, h->stream);
 		if (e == hipSuccess) e = wait_stream(h);
 		if (e != hipSuccess) { bwagpu_free(res); HIPCHK(h, e); }
 	}
@@ -1959,6 +1980,229 @@ extern "C" int bwagpu_pair_flat(bwagpu_t *h, const bwagpu_opt_t *opt, const bwag
 	}
 	return pair_run(h, opt, pes, n_pairs, tot, max_sum, h->d_pair_npri.as<i32>(), h->d_pf_off.as<i64>(), h->d_pf_regs.as<bwagpu_alnreg_t>(), nullptr, h->d_pf_ids.as<i64>(), 0,
 					n_pri, off.data(), regs, nullptr, ids, pairs, kernel_ms);
+}
+
+// ---- the merge of mate-rescue hits on the device (dev_rescue.h) -----------------------------------------------------------------------------------
+extern "C" void bwagpu_rescue_limits(int32_t out[4]) { out[0] = RESC_LANE_MAX; out[1] = RESC_LDS_MAX; out[2] = 0; out[3] = 0; }
+
+template <class T> static T *result_block(size_t n) { return (T*)result_alloc((n ? n : 1) * sizeof(T)); }
+
+// The kernels of both entry points on n_reads = 2 n_pairs reads (sequences d_seq / d_seqoff; lists d_cnt / d_off / d_regs, tot regions; read i has id d_ids[i], or
+// id0 + i): the task kernels, the replay, the packing, then -- for pri / pairs -- the marking and pairing kernels on the packed merged lists.
+static int rescue_run(bwagpu_t *h, const bwagpu_opt_t *opt, const bwagpu_pestat_t pes[4], int n_reads, i64 tot, const u8 *d_seq, const i64 *d_seqoff, const i32 *d_cnt, const i64 *d_off,
+					  const bwagpu_alnreg_t *d_regs, const i64 *d_ids, i64 id0, const i64 *host_ids, int32_t *counts, bwagpu_alnreg_t **regs, int32_t **src, int64_t *n_regs,
+					  bwagpu_rescue_t **rescue, bwagpu_primary_t **pri, int32_t *n_pri, bwagpu_pair_t **pairs, float *kernel_ms)
+{
+	const int np = n_reads / 2;
+	*regs = nullptr; *src = nullptr; *n_regs = 0; *rescue = nullptr;
+	if (pri) *pri = nullptr;
+	if (pairs) *pairs = nullptr;
+	if (kernel_ms) *kernel_ms = 0.f;
+	bwagpu_alnreg_t *res_regs = nullptr; int32_t *res_src = nullptr; bwagpu_rescue_t *res_rec = nullptr; bwagpu_primary_t *res_pri = nullptr; bwagpu_pair_t *res_pair = nullptr;
+	struct Undo { bwagpu_alnreg_t *&a; int32_t *&b; bwagpu_rescue_t *&c; bwagpu_primary_t *&d; bwagpu_pair_t *&e; bool keep = false;
+		~Undo() { if (!keep) { if (a) bwagpu_free(a); if (b) bwagpu_free(b); if (c) bwagpu_free(c); if (d) bwagpu_free(d); if (e) bwagpu_free(e); } } } undo{res_regs, res_src, res_rec, res_pri, res_pair};
+	res_rec = result_block<bwagpu_rescue_t>((size_t)np);
+	if (!res_rec) return BWAGPU_ENOMEM;
+	std::vector<i32> npri((size_t)n_reads, 0);
+	i64 mtot = 0;
+	float ms_resc = 0.f, ms_pri = 0.f, ms_pair = 0.f;
+	if (tot == 0) {      // no region in the whole batch: nothing to rescue from (and the packed arrays may not exist)
+		for (int i = 0; i < n_reads; ++i) counts[i] = 0;
+		for (int p = 0; p < np; ++p) { res_rec[p].n_aligned = res_rec[p].n_inline = res_rec[p].flags = res_rec[p].pad_ = 0; }
+		res_regs = result_block<bwagpu_alnreg_t>(0); res_src = result_block<int32_t>(0);
+		if (!res_regs || !res_src) return BWAGPU_ENOMEM;
+	} else {
+		bwagpu_pes_t pes4[4];
+		for (int d = 0; d < 4; ++d) { pes4[d].low = pes[d].low; pes4[d].high = pes[d].high; pes4[d].failed = pes[d].failed; pes4[d].pad_ = 0; }
+		DevBuf *D = h->d_rs;
+		if (D[bwagpu_s::RS_X].ensure((size_t)n_reads * 4) || D[bwagpu_s::RS_TOFF].ensure(((size_t)n_reads + 1) * 8) || D[bwagpu_s::RS_CTR].ensure(64) || D[bwagpu_s::RS_ACNT].ensure((size_t)n_reads * 4) ||
+			D[bwagpu_s::RS_POFF].ensure(((size_t)n_reads + 1) * 8) || D[bwagpu_s::RS_OUT].ensure((size_t)np * sizeof(bwagpu_rescue_t)) || D[bwagpu_s::RS_LISTS].ensure((size_t)np * 2 * 4)) {
+			h->err = "hipMalloc failed (rescue)"; return BWAGPU_ENOMEM;
+		}
+		i32 *d_x = D[bwagpu_s::RS_X].as<i32>(), *d_acnt = D[bwagpu_s::RS_ACNT].as<i32>();
+		i64 *d_toff = D[bwagpu_s::RS_TOFF].as<i64>(), *d_poff = D[bwagpu_s::RS_POFF].as<i64>();
+		unsigned int *list_n = D[bwagpu_s::RS_CTR].as<unsigned int>();
+		unsigned long long *d_maxcap = (unsigned long long*)(list_n + 2);
+		HIPCHK(h, hipMemsetAsync(D[bwagpu_s::RS_CTR].p, 0, 64, h->stream));
+		(void)hipEventRecord(h->ev[2], h->stream);
+		int nb = (np + BLOCK - 1) / BLOCK; if (nb > 8192) nb = 8192;
+		hipLaunchKernelGGL(k_rescue_count, dim3(nb), dim3(BLOCK), 0, h->stream, *opt, n_reads, d_cnt, d_off, d_regs, d_x, d_maxcap);
+		HIPCHK(h, hipGetLastError());
+		hipLaunchKernelGGL(k_rescue_scan, dim3(1), dim3(256), 0, h->stream, d_x, n_reads, d_toff);
+		HIPCHK(h, hipGetLastError());
+		(void)hipEventRecord(h->ev[3], h->stream);
+		i64 extra = 0; unsigned long long max_cap = 0;
+		HIPCHK(h, hipMemcpyAsync(&extra, d_toff + n_reads, 8, hipMemcpyDeviceToHost, h->stream));
+		HIPCHK(h, hipMemcpyAsync(&max_cap, d_maxcap, 8, hipMemcpyDeviceToHost, h->stream));
+		HIPCHK(h, wait_stream(h));
+		if (max_cap > 0x3fffffffull) return BWAGPU_EINVAL;
+		const int n_lds = np < 1024 ? np : 1024;      // workgroups of the form with its arrays in LDS (each has a staging area of RESC_LDS_MAX regions)
+		const int n_hbm = (i64)max_cap > RESC_LDS_MAX ? (np < 64 ? np : 64) : 0;      // workgroups of the form with its keys in HBM
+		if (D[bwagpu_s::RS_TIX].ensure((size_t)(extra ? extra : 1) * 4) || D[bwagpu_s::RS_ARENA].ensure((size_t)(tot + extra) * sizeof(bwagpu_alnreg_t)) || D[bwagpu_s::RS_ASRC].ensure((size_t)(tot + extra) * 4) ||
+			(n_hbm && D[bwagpu_s::RS_KEYS].ensure((size_t)n_hbm * resc_stride(RESC_WORK_BYTES, (int)max_cap))) ||
+			D[bwagpu_s::RS_STAGE].ensure(std::max((size_t)n_lds * resc_stride(RESC_STAGE_BYTES, RESC_LDS_MAX), (size_t)n_hbm * resc_stride(RESC_STAGE_BYTES, (int)max_cap)))) {
+			h->err = "hipMalloc failed (rescue)"; return BWAGPU_ENOMEM;
+		}
+		i32 *d_tix = D[bwagpu_s::RS_TIX].as<i32>();
+		HIPCHK(h, hipMemsetAsync(d_tix, 0xff, (size_t)(extra ? extra : 1) * 4, h->stream));
+		unsigned long long nt = 0;
+		if (extra) {
+			const int rc = matesw_launch(h, opt, pes4, n_reads, d_seq, d_seqoff, d_cnt, d_off, d_regs, d_toff, d_tix, extra /* four per anchor: every task has its record */, &nt);
+			if (rc != BWAGPU_OK) { (void)wait_stream(h); return rc; }
+		} else {      // (no anchor in the batch: the replay copies the lists and reads neither windows nor tasks)
+			if (h->d_msw_pes.ensure(4 * sizeof(bwagpu_pes_t)) || h->d_msw_out.ensure(sizeof(bwagpu_matesw_t))) { h->err = "hipMalloc failed (rescue)"; return BWAGPU_ENOMEM; }
+			HIPCHK(h, hipMemcpyAsync(h->d_msw_pes.p, pes4, sizeof pes4, hipMemcpyHostToDevice, h->stream));
+			(void)hipEventRecord(h->ev[6], h->stream);
+		}
+		RescIn R;
+		R.seq = d_seq; R.seq_off = d_seqoff; R.cnt = d_cnt; R.off = d_off; R.regs = d_regs; R.pes = h->d_msw_pes.as<bwagpu_pes_t>();
+		R.toff = d_toff; R.tix = d_tix; R.mres = h->d_msw_out.as<bwagpu_matesw_t>(); R.n_tasks = (i64)nt;
+		R.arena = D[bwagpu_s::RS_ARENA].as<bwagpu_alnreg_t>(); R.asrc = D[bwagpu_s::RS_ASRC].as<i32>(); R.acnt = d_acnt; R.out = D[bwagpu_s::RS_OUT].as<bwagpu_rescue_t>();
+		i32 *lists = D[bwagpu_s::RS_LISTS].as<i32>();
+		nb = (np + RESC_LANE_BLOCK - 1) / RESC_LANE_BLOCK; if (nb > 256 * 16) nb = 256 * 16;
+		hipLaunchKernelGGL(k_rescue_lane, dim3(nb), dim3(RESC_LANE_BLOCK), 0, h->stream, h->ix, *opt, R, np, lists, list_n);
+		HIPCHK(h, hipGetLastError());
+		// the wavefront forms draw their pairs from the lists the first kernel left; the first also takes what the lanes handed over, so it always runs
+		hipLaunchKernelGGL(k_rescue_wave<RESC_LDS_MAX>, dim3(n_lds), dim3(64), 0, h->stream, h->ix, *opt, R, lists, list_n, (u8*)nullptr, 0, D[bwagpu_s::RS_STAGE].as<u8>());
+		HIPCHK(h, hipGetLastError());
+		if (n_hbm) {
+			hipLaunchKernelGGL(k_rescue_wave<0>, dim3(n_hbm), dim3(64), 0, h->stream, h->ix, *opt, R, lists + np, list_n + 1, D[bwagpu_s::RS_KEYS].as<u8>(), (int)max_cap, D[bwagpu_s::RS_STAGE].as<u8>());
+			HIPCHK(h, hipGetLastError());
+		}
+		hipLaunchKernelGGL(k_rescue_scan, dim3(1), dim3(256), 0, h->stream, d_acnt, n_reads, d_poff);
+		HIPCHK(h, hipGetLastError());
+		(void)hipEventRecord(h->ev[7], h->stream);
+		HIPCHK(h, hipMemcpyAsync(&mtot, d_poff + n_reads, 8, hipMemcpyDeviceToHost, h->stream));
+		HIPCHK(h, hipMemcpyAsync(counts, d_acnt, (size_t)n_reads * 4, hipMemcpyDeviceToHost, h->stream));
+		HIPCHK(h, hipMemcpyAsync(res_rec, R.out, (size_t)np * sizeof(bwagpu_rescue_t), hipMemcpyDeviceToHost, h->stream));
+		HIPCHK(h, wait_stream(h));
+		if (mtot < 0 || mtot > tot + extra) { h->err = "internal: merged lists larger than their arena"; return BWAGPU_EHIP; }
+		for (int p = 0; p < np; ++p) if (res_rec[p].flags & 2) { h->err = "internal: a pair outgrew the rescue kernel's working lists"; return BWAGPU_EHIP; }
+		if (D[bwagpu_s::RS_REGS].ensure((size_t)(mtot ? mtot : 1) * sizeof(bwagpu_alnreg_t)) || D[bwagpu_s::RS_SRC].ensure((size_t)(mtot ? mtot : 1) * 4)) { h->err = "hipMalloc failed (rescue)"; return BWAGPU_ENOMEM; }
+		res_regs = result_block<bwagpu_alnreg_t>((size_t)mtot); res_src = result_block<int32_t>((size_t)mtot);
+		if (!res_regs || !res_src) return BWAGPU_ENOMEM;
+		nb = (n_reads + 3) / 4; if (nb > 8192) nb = 8192;
+		(void)hipEventRecord(h->ev[0], h->stream);
+		hipLaunchKernelGGL(k_rescue_pack, dim3(nb), dim3(BLOCK), 0, h->stream, R, n_reads, d_poff, D[bwagpu_s::RS_REGS].as<bwagpu_alnreg_t>(), D[bwagpu_s::RS_SRC].as<i32>());
+		HIPCHK(h, hipGetLastError());
+		(void)hipEventRecord(h->ev[1], h->stream);
+		if (mtot) {
+			HIPCHK(h, hipMemcpyAsync(res_regs, D[bwagpu_s::RS_REGS].p, (size_t)mtot * sizeof(bwagpu_alnreg_t), hipMemcpyDeviceToHost, h->stream));
+			HIPCHK(h, hipMemcpyAsync(res_src, D[bwagpu_s::RS_SRC].p, (size_t)mtot * 4, hipMemcpyDeviceToHost, h->stream));
+		}
+		HIPCHK(h, wait_stream(h));
+		{	// the kernels' segments between the call's host waits: count + scan, the task kernel, alignments + replay + scan, packing
+			float a = 0.f, b = 0.f, c = 0.f, d = 0.f;
+			(void)hipEventElapsedTime(&a, h->ev[2], h->ev[3]);
+			if (extra) (void)hipEventElapsedTime(&b, h->ev[4], h->ev[5]);
+			(void)hipEventElapsedTime(&c, h->ev[6], h->ev[7]);
+			(void)hipEventElapsedTime(&d, h->ev[0], h->ev[1]);
+			ms_resc = a + b + c + d;
+		}
+	}
+	// marking and pairing of the merged lists: the kernels of bwagpu_batch_primary / bwagpu_batch_pair, pointed at the packed merged lists
+	if (pri || pairs) {
+		if (mtot == 0) { res_pri = result_block<bwagpu_primary_t>(0); if (!res_pri) return BWAGPU_ENOMEM; }
+		else {
+			i64 log_need = 0, k = 0; int max_cnt = 0;
+			for (int i = 0; i < n_reads; ++i) {
+				if (counts[i] > max_cnt) max_cnt = counts[i];
+				for (int j = 0; j < counts[i]; ++j, ++k) {
+					const bwagpu_alnreg_t &a = res_regs[k];
+					const i64 lq = (i64)a.qe - a.qb, lr = a.re - a.rb, sn = (i64)a.sub_n + 2 * (i64)counts[i] + 1;
+					if (lq > log_need) log_need = lq;
+					if (lr > log_need) log_need = lr;
+					if (a.seedcov > log_need) log_need = a.seedcov;
+					if (sn > log_need) log_need = sn;
+				}
+			}
+			const int rc = primary_run(h, opt, n_reads, mtot, max_cnt, log_need, h->d_rs[bwagpu_s::RS_ACNT].as<i32>(), h->d_rs[bwagpu_s::RS_POFF].as<i64>(), h->d_rs[bwagpu_s::RS_REGS].as<bwagpu_alnreg_t>(),
+									   d_ids, id0, counts, res_regs, &res_pri, npri.data(), &ms_pri);
+			if (rc != BWAGPU_OK) return rc;
+		}
+	}
+	if (pairs) {
+		if (mtot == 0) {
+			res_pair = result_block<bwagpu_pair_t>((size_t)np);
+			if (!res_pair) return BWAGPU_ENOMEM;
+			for (int p = 0; p < np; ++p) { res_pair[p].score = res_pair[p].sub = res_pair[p].n_sub = 0; res_pair[p].z[0] = res_pair[p].z[1] = -1; res_pair[p].flags = 0; res_pair[p].n_cand = 0; }
+		} else {
+			i64 max_sum = 0;
+			for (int p = 0; p < np; ++p) { const i64 s2 = (i64)npri[2 * (size_t)p] + npri[2 * (size_t)p + 1]; if (s2 > max_sum) max_sum = s2; }
+			std::vector<i64> pid;
+			const i64 *d_pid = nullptr;
+			if (host_ids) {      // a pair's id is its first read's id >> 1 (bwamem_pair.c:349-354)
+				pid.resize((size_t)np);
+				for (int p = 0; p < np; ++p) pid[(size_t)p] = host_ids[2 * (size_t)p] >> 1;
+				if (h->d_rs[bwagpu_s::RS_PAIRIDS].ensure((size_t)np * 8)) { h->err = "hipMalloc failed (rescue)"; return BWAGPU_ENOMEM; }
+				HIPCHK(h, hipMemcpyAsync(h->d_rs[bwagpu_s::RS_PAIRIDS].p, pid.data(), (size_t)np * 8, hipMemcpyHostToDevice, h->stream));
+				HIPCHK(h, wait_stream(h));
+				d_pid = h->d_rs[bwagpu_s::RS_PAIRIDS].as<i64>();
+			}
+			std::vector<i64> poff((size_t)n_reads);
+			{ i64 run = 0; for (int i = 0; i < n_reads; ++i) { poff[(size_t)i] = run; run += counts[i]; } }
+			const int rc = pair_run(h, opt, pes, np, mtot, max_sum, h->d_pri_npri.as<i32>(), h->d_rs[bwagpu_s::RS_POFF].as<i64>(), h->d_rs[bwagpu_s::RS_REGS].as<bwagpu_alnreg_t>(), h->d_pri_out.as<bwagpu_primary_t>(),
+									d_pid, id0 >> 1, npri.data(), poff.data(), res_regs, res_pri, host_ids ? pid.data() : nullptr, &res_pair, &ms_pair);
+			if (rc != BWAGPU_OK) return rc;
+		}
+	}
+	undo.keep = true;
+	*regs = res_regs; *src = res_src; *n_regs = mtot; *rescue = res_rec;
+	if (pri) *pri = res_pri; else if (res_pri) bwagpu_free(res_pri);
+	if (pairs) *pairs = res_pair;
+	if (n_pri) memcpy(n_pri, npri.data(), (size_t)n_reads * 4);
+	if (kernel_ms) *kernel_ms = ms_resc + ms_pri + ms_pair;
+	return BWAGPU_OK;
+}
+
+extern "C" int bwagpu_batch_rescue(bwagpu_t *h, const bwagpu_opt_t *opt, const bwagpu_pestat_t pes[4], int64_t id0, int32_t *counts, bwagpu_alnreg_t **regs, int32_t **src, int64_t *n_regs,
+								   bwagpu_rescue_t **rescue, bwagpu_primary_t **pri, int32_t *n_pri, bwagpu_pair_t **pairs, float *kernel_ms)
+{
+	if (!h || !opt || !pes || !h->ran || !h->downloaded || !regs || !src || !n_regs || !rescue || (h->n_reads > 0 && !counts)) return BWAGPU_EINVAL;
+	if ((h->n_reads & 1) || (id0 & 1) || opt->e_del <= 0 || opt->e_ins <= 0 || (pairs && (opt->flag & 0x800 /* MEM_F_PRIMARY5 */))) return BWAGPU_EINVAL;
+	const BusyGuard busy(h->ibuf->busy);
+	HIPCHK(h, hipSetDevice(h->device));
+	const i64 tot = h->packed_tot < 0 ? 0 : h->packed_tot;
+	return rescue_run(h, opt, pes, h->n_reads, tot, h->d_seq.as<u8>(), h->d_off.as<i64>(), h->d_reg_n.as<i32>(), h->d_pack_off.as<i64>(), h->d_regs_packed.as<bwagpu_alnreg_t>(), nullptr, id0, nullptr,
+					  counts, regs, src, n_regs, rescue, pri, n_pri, pairs, kernel_ms);
+}
+
+extern "C" int bwagpu_rescue_flat(bwagpu_t *h, const bwagpu_opt_t *opt, const bwagpu_pestat_t pes[4], int n_pairs, const uint8_t *seqs, const int64_t *off, const int32_t *counts_in,
+								  const bwagpu_alnreg_t *regs_in, const int64_t *ids, int32_t *counts, bwagpu_alnreg_t **regs, int32_t **src, int64_t *n_regs, bwagpu_rescue_t **rescue,
+								  bwagpu_primary_t **pri, int32_t *n_pri, bwagpu_pair_t **pairs, float *kernel_ms)
+{
+	if (!h || !opt || !pes || n_pairs < 0 || n_pairs > 0x1fffffff || !regs || !src || !n_regs || !rescue) return BWAGPU_EINVAL;
+	if (n_pairs > 0 && (!seqs || !off || !counts_in || !counts || ((pri || pairs) && !ids))) return BWAGPU_EINVAL;
+	if (opt->e_del <= 0 || opt->e_ins <= 0 || (pairs && (opt->flag & 0x800 /* MEM_F_PRIMARY5 */))) return BWAGPU_EINVAL;
+	const int n_reads = 2 * n_pairs;
+	std::vector<i64> roff((size_t)n_reads + 1, 0);
+	i64 tot = 0;
+	for (int i = 0; i < n_reads; ++i) {
+		if (counts_in[i] < 0 || counts_in[i] > 0x3fffffff || off[i + 1] < off[i] || off[i] < 0 || off[i + 1] - off[i] > 0x3fffffff || (counts_in[i] > 0 && !regs_in)) return BWAGPU_EINVAL;
+		roff[(size_t)i] = tot;
+		for (int k = 0; k < counts_in[i]; ++k) if (regs_in[tot + k].rid < 0 || regs_in[tot + k].rid >= h->n_seqs) return BWAGPU_EINVAL;
+		tot += counts_in[i];
+	}
+	const i64 n_bases = n_reads ? off[n_reads] : 0;
+	for (i64 k = n_reads ? off[0] : 0; k < n_bases; ++k) if (seqs[k] > 4) return BWAGPU_EINVAL;
+	const BusyGuard busy(h->ibuf->busy);
+	HIPCHK(h, hipSetDevice(h->device));
+	DevBuf *D = h->d_rs;
+	if (n_reads) {
+		if (D[bwagpu_s::RS_SEQ].ensure((size_t)(n_bases ? n_bases : 1)) || D[bwagpu_s::RS_SEQOFF].ensure(((size_t)n_reads + 1) * 8) || D[bwagpu_s::RS_CNT_IN].ensure((size_t)n_reads * 4) ||
+			D[bwagpu_s::RS_OFF_IN].ensure(((size_t)n_reads + 1) * 8) || D[bwagpu_s::RS_REGS_IN].ensure((size_t)(tot ? tot : 1) * sizeof(bwagpu_alnreg_t)) || (ids && D[bwagpu_s::RS_IDS].ensure((size_t)n_reads * 8))) {
+			h->err = "hipMalloc failed (rescue)"; return BWAGPU_ENOMEM;
+		}
+		if (n_bases) HIPCHK(h, hipMemcpyAsync(D[bwagpu_s::RS_SEQ].p, seqs, (size_t)n_bases, hipMemcpyHostToDevice, h->stream));
+		HIPCHK(h, hipMemcpyAsync(D[bwagpu_s::RS_SEQOFF].p, off, ((size_t)n_reads + 1) * 8, hipMemcpyHostToDevice, h->stream));
+		HIPCHK(h, hipMemcpyAsync(D[bwagpu_s::RS_CNT_IN].p, counts_in, (size_t)n_reads * 4, hipMemcpyHostToDevice, h->stream));
+		HIPCHK(h, hipMemcpyAsync(D[bwagpu_s::RS_OFF_IN].p, roff.data(), ((size_t)n_reads + 1) * 8, hipMemcpyHostToDevice, h->stream));
+		if (tot) HIPCHK(h, hipMemcpyAsync(D[bwagpu_s::RS_REGS_IN].p, regs_in, (size_t)tot * sizeof(bwagpu_alnreg_t), hipMemcpyHostToDevice, h->stream));
+		if (ids) HIPCHK(h, hipMemcpyAsync(D[bwagpu_s::RS_IDS].p, ids, (size_t)n_reads * 8, hipMemcpyHostToDevice, h->stream));
+		HIPCHK(h, wait_stream(h));      // (`roff` is a local array)
+	}
+	return rescue_run(h, opt, pes, n_reads, tot, D[bwagpu_s::RS_SEQ].as<u8>(), D[bwagpu_s::RS_SEQOFF].as<i64>(), D[bwagpu_s::RS_CNT_IN].as<i32>(), D[bwagpu_s::RS_OFF_IN].as<i64>(),
+					  D[bwagpu_s::RS_REGS_IN].as<bwagpu_alnreg_t>(), ids ? D[bwagpu_s::RS_IDS].as<i64>() : nullptr, 0, ids, counts, regs, src, n_regs, rescue, pri, n_pri, pairs, kernel_ms);
 }
 
 extern "C" int bwagpu_align_flat(bwagpu_t *h, const bwagpu_opt_t *opt, int n, const uint8_t *seqs, const int64_t *off,

@@ -29,8 +29,8 @@ DEVFN int dev_infer_dir(i64 l_pac, i64 b1, i64 b2, i64 *dist)
 
 // One lane per pair: reads 2p and 2p+1 of the batch; regs/cnt/off are the packed regions of bwagpu_batch_download.
 __global__ void __launch_bounds__(256) k_matesw_tasks(DevIndex ix, bwagpu_opt_t opt, int n_reads, const i32 *cnt, const i64 *off, const bwagpu_alnreg_t *regs,
-													   const bwagpu_pes_t *pes, MateTask *tasks, unsigned long long *n_tasks, i64 task_cap)
-{
+													   const bwagpu_pes_t *pes, MateTask *tasks, unsigned long long *n_tasks, i64 task_cap, const i64 *toff, i32 *tix)
+{	// toff / tix (may be null; dev_rescue.h): the task of (anchor j of read ri, orientation r) goes to tix[toff[ri] + 4 j + r], which the caller has filled with -1
 	for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < n_reads / 2; p += gridDim.x * blockDim.x) {
 		for (int i = 0; i < 2; ++i) {
 			const int ri = 2 * p + i, rm = 2 * p + (1 - i);
@@ -53,12 +53,40 @@ __global__ void __launch_bounds__(256) k_matesw_tasks(DevIndex ix, bwagpu_opt_t 
 					if (skip[r]) continue;
 					const unsigned long long t = atomicAdd(n_tasks, 1ull);
 					if ((i64)t < task_cap) { MateTask m; m.read = rm; m.r = r; m.anchor_rb = a[j].rb; m.anchor_rid = a[j].rid; m.pad_ = 0; tasks[t] = m; }
+					if (tix && (i64)t < task_cap) tix[toff[ri] + 4 * (taken - 1) + r] = (i32)t;
 				}
 			}
 		}
 	}
 }
 
+enum { MSW_NOT_DUE = 0, MSW_DUE = 1, MSW_BEYOND = 2 };
+
+// The window of mem_matesw (bwamem_pair.c:156-166) for anchor position arb on contig arid, orientation r and a mate of l_ms bases, clamped as bns_fetch_seq
+// does (bntseq.c:426-443): MSW_DUE when the reference aligns (:167), MSW_BEYOND when it does but the mate or the window is beyond the alignment kernel.
+DEVFN int msw_window(const DevIndex &ix, const bwagpu_opt_t &opt, const bwagpu_pes_t *pes, int r, i64 arb, int arid, int l_ms, i64 &rb, i64 &re)
+{
+	const i64 l_pac = ix.l_pac;
+	const int is_rev = (r >> 1) != (r & 1), is_larger = !(r >> 1);
+	if (!is_rev) {
+		rb = is_larger ? arb + pes[r].low : arb - pes[r].high;
+		re = (is_larger ? arb + pes[r].high : arb - pes[r].low) + l_ms;
+	} else {
+		rb = (is_larger ? arb + pes[r].low : arb - pes[r].high) - l_ms;
+		re = is_larger ? arb + pes[r].high : arb - pes[r].low;
+	}
+	if (rb < 0) rb = 0;
+	if (re > l_pac << 1) re = l_pac << 1;
+	if (rb >= re) return MSW_NOT_DUE;
+	const i64 mid = (rb + re) >> 1;
+	int mrev; const int rid = dev_pos2rid(ix, dev_depos(ix, mid, &mrev));
+	i64 fb = ix.ctg_off[rid], fe = fb + ix.ctg_len[rid];
+	if (mrev) { const i64 t2 = fb; fb = (l_pac << 1) - fe; fe = (l_pac << 1) - t2; }
+	if (rb < fb) rb = fb;
+	if (re > fe) re = fe;
+	if (arid != rid || re - rb < opt.min_seed_len) return MSW_NOT_DUE;
+	return l_ms > MSW_MAX_Q || re - rb > MSW_MAX_T ? MSW_BEYOND : MSW_DUE;
+}
 struct MswRes { int score, te, qe, score2, te2; };
 enum { MSW_XBYTE = 0x10000, MSW_XSTOP = 0x20000, MSW_XSUBO = 0x40000, MSW_XSTART = 0x80000 };
 #define MSW_RUN_INTS (MSW_MAX_T + 4)     // LDS ints per wave: the (row maximum, row) runs of the score2 bookkeeping, at most one per two rows
@@ -156,7 +184,7 @@ __device__ MswRes wave_sw_core(int size, int qlen, QF Q, int tlen, TF T, const b
 // ksw_align2 (ksw.c:379-400): the forward pass and, with KSW_XSTART, the pass over the reversed prefixes that finds the start
 // positions.  res = {score, te, qe, score2, te2, tb, qb}.
 template <int NP, class QF, class TF>
-__device__ void wave_align2(const bwagpu_opt_t &opt, int qlen, QF Qf, int tlen, TF Tf, int xtra, i32 *runs, int res[7])
+DEVFN void wave_align2(const bwagpu_opt_t &opt, int qlen, QF Qf, int tlen, TF Tf, int xtra, i32 *runs, int res[7])
 {
 	const int size = (xtra & MSW_XBYTE) ? 1 : 2;
 	const MswRes a = wave_sw_core<NP>(size, qlen, Qf, tlen, Tf, opt, xtra, runs);
@@ -170,7 +198,7 @@ __device__ void wave_align2(const bwagpu_opt_t &opt, int qlen, QF Qf, int tlen, 
 }
 // (two instances: up to 192 padded query columns -- every 150 bp mate -- and up to MSW_QCOLS)
 template <class QF, class TF>
-__device__ void msw_align2(const bwagpu_opt_t &opt, int qlen, QF Qf, int tlen, TF Tf, int xtra, i32 *runs, int res[7])
+DEVFN void msw_align2(const bwagpu_opt_t &opt, int qlen, QF Qf, int tlen, TF Tf, int xtra, i32 *runs, int res[7])
 {
 	if (qlen <= 176) wave_align2<3>(opt, qlen, Qf, tlen, Tf, xtra, runs, res);
 	else wave_align2<(MSW_QCOLS + 63) / 64>(opt, qlen, Qf, tlen, Tf, xtra, runs, res);
@@ -183,7 +211,6 @@ __global__ void __launch_bounds__(256) k_matesw_sw(DevIndex ix, bwagpu_opt_t opt
 	__shared__ i32 msw_runs[4 * MSW_RUN_INTS];
 	const int lane = threadIdx.x & 63;
 	i32 *runs = msw_runs + (threadIdx.x >> 6) * MSW_RUN_INTS;
-	const i64 l_pac = ix.l_pac;
 	WaveQueue wq; wq_init(wq); wq.step = WQ_CHUNK;
 	for (;;) {
 		long long t;
@@ -194,29 +221,10 @@ __global__ void __launch_bounds__(256) k_matesw_sw(DevIndex ix, bwagpu_opt_t opt
 		o.score = 0; o.te = o.qe = o.score2 = o.te2 = o.tb = o.qb = -1; o.pad_ = 0; o.pad2_ = 0;
 		const u8 *ms = Bt.seq + Bt.off[k.read];
 		const int l_ms = uni((int)(Bt.off[k.read + 1] - Bt.off[k.read]));
-		const int r = uni(k.r), is_rev = (r >> 1) != (r & 1), is_larger = !(r >> 1);
+		const int r = uni(k.r), is_rev = (r >> 1) != (r & 1);
 		const i64 arb = uni64(k.anchor_rb);
 		i64 rb, re;
-		if (!is_rev) {
-			rb = is_larger ? arb + pes[r].low : arb - pes[r].high;
-			re = (is_larger ? arb + pes[r].high : arb - pes[r].low) + l_ms;
-		} else {
-			rb = (is_larger ? arb + pes[r].low : arb - pes[r].high) - l_ms;
-			re = is_larger ? arb + pes[r].high : arb - pes[r].low;
-		}
-		if (rb < 0) rb = 0;
-		if (re > l_pac << 1) re = l_pac << 1;
-		bool due = rb < re && l_ms <= MSW_MAX_Q;
-		int rid = -1;
-		if (due) {   // bns_fetch_seq: clamp to the contig of the window's midpoint (bntseq.c:426-443)
-			const i64 mid = (rb + re) >> 1;
-			int mrev; rid = dev_pos2rid(ix, dev_depos(ix, mid, &mrev));
-			i64 fb = ix.ctg_off[rid], fe = fb + ix.ctg_len[rid];
-			if (mrev) { const i64 t2 = fb; fb = (l_pac << 1) - fe; fe = (l_pac << 1) - t2; }
-			if (rb < fb) rb = fb;
-			if (re > fe) re = fe;
-			due = uni(k.anchor_rid) == rid && re - rb >= opt.min_seed_len && re - rb <= MSW_MAX_T;
-		}
+		const bool due = msw_window(ix, opt, pes, r, arb, uni(k.anchor_rid), l_ms, rb, re) == MSW_DUE;
 		rb = uni64(rb); re = uni64(re);
 		if (due) {
 			const int tlen = (int)(re - rb);

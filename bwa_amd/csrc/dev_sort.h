@@ -76,3 +76,46 @@ __device__ void dev_introsort(T *a, int n, LT lt)
 	}
 	if (FINISH) dev_insertion(a, 0, n, lt);
 }
+
+// The same routine with its stack in memory of the caller's (DEV_SORT_FRAMES frames): for kernels that keep no array in private memory (dev_rescue.h: LDS).
+// dev_introsort itself stays as it is -- the kernels that use it are held to their scratch sizes (tests/test_kernel_resources.py).
+struct SortFrame { int l, r, d; };
+#define DEV_SORT_FRAMES 40
+template <class T, class LT, bool FINISH = true>
+DEVFN void dev_introsort_stk(T *a, int n, LT lt, SortFrame *stack)
+{
+	int top = 0, d;
+	if (n < 1) return;
+	if (n == 2) { if (lt(a[1], a[0])) { T t = a[0]; a[0] = a[1]; a[1] = t; } return; }
+	for (d = 2; (1ul << d) < (unsigned long)n; ++d) {}
+	d <<= 1;
+	int s = 0, t = n - 1;
+	for (;;) {
+		if (s < t) {
+			if (--d == 0) { dev_combsort(a + s, t - s + 1, lt); t = s; continue; }
+			int i = s, j = t, k = i + ((j - i) >> 1) + 1;
+			if (lt(a[k], a[i])) { if (lt(a[k], a[j])) k = j; }
+			else k = lt(a[j], a[i]) ? i : j;
+			T piv = a[k];
+			if (k != t) { T x = a[k]; a[k] = a[t]; a[t] = x; }
+			for (;;) {
+				do ++i; while (lt(a[i], piv));
+				do --j; while (i <= j && lt(piv, a[j]));
+				if (j <= i) break;
+				T x = a[i]; a[i] = a[j]; a[j] = x;
+			}
+			{ T x = a[i]; a[i] = a[t]; a[t] = x; }
+			if (i - s > t - i) {
+				if (i - s > 16) { stack[top].l = s; stack[top].r = i - 1; stack[top].d = d; ++top; }
+				s = t - i > 16 ? i + 1 : t;
+			} else {
+				if (t - i > 16) { stack[top].l = i + 1; stack[top].r = t; stack[top].d = d; ++top; }
+				t = i - s > 16 ? i - 1 : s;
+			}
+		} else {
+			if (top == 0) break;
+			--top; s = stack[top].l; t = stack[top].r; d = stack[top].d;
+		}
+	}
+	if (FINISH) dev_insertion(a, 0, n, lt);
+}

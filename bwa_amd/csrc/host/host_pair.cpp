@@ -267,7 +267,7 @@ int64_t host_matesw_records(const bwagpu_opt_t &opt, const RefSeqs &ref, int n, 
 	return nout;
 }
 
-std::atomic<long> g_pairs_from_device(0);
+std::atomic<long> g_pairs_from_device(0), g_pairs_merged_on_device(0), g_pairs_merged_aligned(0);
 
 // ---- pairing (mem_pair, bwamem_pair.c:208-274) --------------------------------------------------------------------------------
 static int pair_ends(const bwagpu_opt_t &opt, const RefSeqs &ref, const Pestat pes[4], const Regs a[2], int id, int *sub, int *n_sub, int z[2], const int n_pri[2])
@@ -338,7 +338,15 @@ int sam_pe(const bwagpu_opt_t &opt, const RefSeqs &ref, const Pestat pes[4], uin
 	Aln h[2];
 	SamText &out0 = *outp[0], &out1 = *outp[1];
 	out0.reserve(out0.size() + 2 * (size_t)s[0].l_seq + 320); out1.reserve(out1.size() + 2 * (size_t)s[1].l_seq + 320);      // one allocation instead of the five a growing string makes
-	if (!(opt.flag & F_NO_RESCUE)) {   // mate rescue from the best hits of each end
+	// The device's merge (bwagpu_batch_rescue): the lists as the loop below would leave them, with the marking records and the pair record of those lists.  A pair
+	// the device flagged, or whose pair record is flagged, runs the host code unchanged.
+	const bool merged = s[0].rescue && !(s[0].rescue->flags & 1) && s[0].pair && !(s[0].pair->flags & 1) && s[0].pri && s[1].pri && !(opt.flag & F_PRIMARY5);
+	if (merged) {
+		for (int i = 0; i < 2; ++i) a[i].assign(s[i].merged, s[i].merged + s[i].n_merged);
+		n = s[0].rescue->n_aligned;
+		++g_pairs_merged_on_device;
+		if (n > 0) ++g_pairs_merged_aligned;
+	} else if (!(opt.flag & F_NO_RESCUE)) {   // mate rescue from the best hits of each end
 		thread_local Regs b[2];
 		b[0].clear(); b[1].clear();
 		for (int i = 0; i < 2; ++i)
@@ -350,7 +358,7 @@ int sam_pe(const bwagpu_opt_t &opt, const RefSeqs &ref, const Pestat pes[4], uin
 	}
 	// The device's records of the pair (bwagpu_batch_pair) describe the lists as downloaded: they stand for the marking and for pair_ends when the rescue loop
 	// has aligned nothing (no hit was added), no reordering comes between the two (F_PRIMARY5) and the record is the device's own (unflagged).
-	const bwagpu_pair_t *dev = n == 0 && s[0].pair && s[0].pri && s[1].pri && !(opt.flag & F_PRIMARY5) && !(s[0].pair->flags & 1) ? s[0].pair : nullptr;
+	const bwagpu_pair_t *dev = (merged || n == 0) && s[0].pair && s[0].pri && s[1].pri && !(opt.flag & F_PRIMARY5) && !(s[0].pair->flags & 1) ? s[0].pair : nullptr;
 	if (dev) {
 		thread_local std::vector<int32_t> mq;
 		for (int i = 0; i < 2; ++i) {
@@ -358,7 +366,7 @@ int sam_pe(const bwagpu_opt_t &opt, const RefSeqs &ref, const Pestat pes[4], uin
 			n_pri[i] = 0;
 			for (size_t j = 0; j < a[i].size(); ++j) n_pri[i] += a[i][j].is_alt == 0;
 		}
-		++g_pairs_from_device;
+		if (!merged) ++g_pairs_from_device;
 	} else {
 		n_pri[0] = mark_primary_se(opt, a[0], (int64_t)(id << 1 | 0));
 		n_pri[1] = mark_primary_se(opt, a[1], (int64_t)(id << 1 | 1));

@@ -39,6 +39,7 @@ using namespace hostmem;
 static int g_verbose = 3;
 static int g_device_matesw = 1;   // BWAGPU_CLI_MATESW=0: the host runs every mate-rescue alignment itself (same output)
 static int g_device_cigars = 1;   // BWAGPU_CLI_CIGARS=0: the host computes every CIGAR itself (same output)
+static int g_device_rescue = 0;   // BWAGPU_CLI_RESCUE=1: paired-end batches take the merged lists, their marking and their mem_pair from the device (bwagpu_batch_rescue, in place of bwagpu_batch_matesw + bwagpu_batch_pair; same output)
 static int g_device_pair = 0;     // BWAGPU_CLI_PAIR=1: paired-end batches take the marking and mem_pair of the pairs the rescue loop leaves alone from the device (bwagpu_batch_pair; same output)
 static int g_device_primary = 0;  // BWAGPU_CLI_PRIMARY=1: single-end batches take primary/secondary marking and mapQ from the device (bwagpu_batch_primary; same output)
 static std::atomic<long> g_n_primary_reads(0);   // ... reads finalized from such records (the BWAGPU_CLI_TRACE line at the end of the run)
@@ -345,6 +346,7 @@ struct Sub {      // one mem_process_seqs call (bwamem.c:1235-1264) on the reads
 	bwagpu_matesw_t *msw = nullptr; int64_t n_msw = 0;   // device-side mate-rescue alignments (bwagpu_batch_matesw)
 	bwagpu_primary_t *pri = nullptr;          // device-side marking + mapQ records of the regions, in each read's marked order (bwagpu_batch_primary; single-end, or paired-end with bwagpu_batch_pair)
 	bwagpu_pair_t *pairs = nullptr;           // device-side mem_pair records of the pairs as downloaded (bwagpu_batch_pair)
+	bwagpu_alnreg_t *m_all = nullptr; int32_t *m_src = nullptr; std::vector<int32_t> m_counts; bwagpu_rescue_t *rescue = nullptr;   // bwagpu_batch_rescue: the merged lists (read i: m_counts[i] regions), one record per pair; pri / pairs then describe these lists
 	Pestat pes[4]; bool have_pes = false;     // insert-size windows, when they had to be computed before the finalize stage
 	double t_dev = 0;
 };
@@ -406,7 +408,7 @@ static void device_sub(const std::vector<bwagpu_t*> &gpus, Sub &u, const RefSeqs
 	int D = (int)gpus.size();
 	const int units = pe ? n / 2 : n, per = pe ? 2 : 1;
 	if (D > units) D = units > 0 ? units : 1;
-	struct Shard { int lo = 0, hi = 0; std::vector<int64_t> off; bwagpu_alnreg_t *all = nullptr; int64_t tot = 0; bwagpu_cigar_t *cigs = nullptr; uint32_t *ops = nullptr; int64_t n_ops = 0; bwagpu_matesw_t *msw = nullptr; int64_t n_msw = 0; bwagpu_primary_t *pri = nullptr; bwagpu_pair_t *pairs = nullptr; };
+	struct Shard { int lo = 0, hi = 0; std::vector<int64_t> off; bwagpu_alnreg_t *all = nullptr; int64_t tot = 0; bwagpu_cigar_t *cigs = nullptr; uint32_t *ops = nullptr; int64_t n_ops = 0; bwagpu_matesw_t *msw = nullptr; int64_t n_msw = 0; bwagpu_primary_t *pri = nullptr; bwagpu_pair_t *pairs = nullptr; bwagpu_alnreg_t *m_all = nullptr; int32_t *m_src = nullptr; int64_t m_tot = 0; bwagpu_rescue_t *rescue = nullptr; };
 	std::vector<Shard> sh((size_t)D);
 	for (int d = 0; d < D; ++d) {
 		sh[d].lo = (int)((int64_t)units * d / D) * per; sh[d].hi = d + 1 == D ? n : (int)((int64_t)units * (d + 1) / D) * per;
@@ -518,7 +520,37 @@ static void device_sub(const std::vector<bwagpu_t*> &gpus, Sub &u, const RefSeqs
 	if (pes_thread.joinable()) pes_thread.join();
 	// mem_pair of the pairs as downloaded, and the marking of their ends, on the device too: the windows are known here.  Read i of the batch has id
 	// n_processed + i (mem_sam_pe: id << 1 | r with id = (n_processed + i) >> 1); a shard starts at an even read.
-	if (g_device_pair && pe && u.have_pes && !(u.opt.flag & (F_PRIMARY5 | F_NOPAIRING)) && !(u.n_processed & 1) && u.tot > 0) {
+	// The merge of mate-rescue hits, the marking of the merged lists and mem_pair on those records in one call, under the same conditions: it stands for both blocks below.
+	const bool dev_rescue = g_device_rescue && pe && u.have_pes && !(u.opt.flag & (F_PRIMARY5 | F_NOPAIRING)) && !(u.n_processed & 1) && u.tot > 0;
+	if (dev_rescue) {
+		bwagpu_pestat_t dp[4];
+		for (int d = 0; d < 4; ++d) { memset(&dp[d], 0, sizeof dp[d]); dp[d].low = u.pes[d].low; dp[d].high = u.pes[d].high; dp[d].failed = u.pes[d].failed; dp[d].avg = u.pes[d].avg; dp[d].std = u.pes[d].std; }
+		u.m_counts.assign((size_t)n, 0);
+		on_devices([&](int d) {
+			Shard &s = sh[d];
+			if (s.tot == 0) return;      // (no region: the merged lists are empty too)
+			int rc = bwagpu_batch_rescue(gpus[d], &u.opt, dp, u.n_processed + s.lo, u.m_counts.data() + s.lo, &s.m_all, &s.m_src, &s.m_tot, &s.rescue, &s.pri, nullptr, &s.pairs, nullptr);
+			if (rc != BWAGPU_OK) device_fail(gpus[d], rc);
+		});
+		int64_t mt = 0; for (auto &s : sh) mt += s.m_tot;
+		u.m_all = (bwagpu_alnreg_t*)malloc((size_t)(mt ? mt : 1) * sizeof(bwagpu_alnreg_t));
+		u.m_src = (int32_t*)malloc((size_t)(mt ? mt : 1) * 4);
+		u.pri = (bwagpu_primary_t*)malloc((size_t)(mt ? mt : 1) * sizeof(bwagpu_primary_t));
+		u.pairs = (bwagpu_pair_t*)malloc((size_t)(n / 2 + 1) * sizeof(bwagpu_pair_t));
+		u.rescue = (bwagpu_rescue_t*)malloc((size_t)(n / 2 + 1) * sizeof(bwagpu_rescue_t));
+		if (!u.m_all || !u.m_src || !u.pri || !u.pairs || !u.rescue) { fprintf(stderr, "[E::%s] out of memory\n", "mem_process_seqs"); exit(EXIT_FAILURE); }
+		int64_t k = 0;
+		for (auto &s : sh) {      // (records name regions and anchors by indices within their read: nothing moves with the shard)
+			const size_t np = (size_t)((s.hi - s.lo) / 2);
+			if (s.tot) {
+				if (s.m_tot) { memcpy(u.m_all + k, s.m_all, (size_t)s.m_tot * sizeof(bwagpu_alnreg_t)); memcpy(u.pri + k, s.pri, (size_t)s.m_tot * sizeof(bwagpu_primary_t)); memcpy(u.m_src + k, s.m_src, (size_t)s.m_tot * 4); }
+				memcpy(u.pairs + s.lo / 2, s.pairs, np * sizeof(bwagpu_pair_t)); memcpy(u.rescue + s.lo / 2, s.rescue, np * sizeof(bwagpu_rescue_t));
+			} else for (int p = s.lo / 2; p < s.hi / 2; ++p) { bwagpu_pair_t &r = u.pairs[p]; memset(&r, 0, sizeof r); r.z[0] = r.z[1] = -1; memset(&u.rescue[p], 0, sizeof u.rescue[p]); }
+			k += s.m_tot;
+			bwagpu_free(s.m_all); s.m_all = nullptr; bwagpu_free(s.m_src); s.m_src = nullptr; bwagpu_free(s.rescue); s.rescue = nullptr; bwagpu_free(s.pri); s.pri = nullptr; bwagpu_free(s.pairs); s.pairs = nullptr;
+		}
+	}
+	if (!dev_rescue && g_device_pair && pe && u.have_pes && !(u.opt.flag & (F_PRIMARY5 | F_NOPAIRING)) && !(u.n_processed & 1) && u.tot > 0) {
 		bwagpu_pestat_t dp[4];
 		for (int d = 0; d < 4; ++d) { memset(&dp[d], 0, sizeof dp[d]); dp[d].low = u.pes[d].low; dp[d].high = u.pes[d].high; dp[d].failed = u.pes[d].failed; dp[d].avg = u.pes[d].avg; dp[d].std = u.pes[d].std; }
 		on_devices([&](int d) {
@@ -538,7 +570,7 @@ static void device_sub(const std::vector<bwagpu_t*> &gpus, Sub &u, const RefSeqs
 			k += s.tot; bwagpu_free(s.pri); s.pri = nullptr; bwagpu_free(s.pairs); s.pairs = nullptr;
 		}
 	}
-	if (want_matesw) {
+	if (want_matesw && !dev_rescue) {
 		bwagpu_pes_t dp[4];
 		for (int d = 0; d < 4; ++d) { dp[d].low = u.pes[d].low; dp[d].high = u.pes[d].high; dp[d].failed = u.pes[d].failed; dp[d].pad_ = 0; }
 		on_devices([&](int d) {
@@ -577,14 +609,30 @@ static void finalize_sub(const RefSeqs &ref, Work &w, Sub &u, const Pestat *pes0
 	std::vector<Read> reads((size_t)n); std::vector<CigHints> hints(u.cigs ? (size_t)n : 0);
 	std::vector<int64_t> roff((size_t)n + 1, 0);
 	for (int i = 0; i < n; ++i) roff[i + 1] = roff[i] + u.counts[i];
+	std::vector<int64_t> moff;
+	std::vector<bwagpu_cigar_t> m_cigs;      // the CIGAR records in the merged lists' order: they follow `src`; a rescued hit has none (the host aligns it)
+	if (u.rescue) {
+		moff.assign((size_t)n + 1, 0); for (int i = 0; i < n; ++i) moff[i + 1] = moff[i] + u.m_counts[i];
+		if (u.cigs) {
+			m_cigs.resize((size_t)moff[n]);
+			parallel_for(u.opt.n_threads, n, [&](long i) {
+				for (int64_t k = moff[i]; k < moff[i + 1]; ++k) {
+					if (u.m_src[k] >= 0) m_cigs[(size_t)k] = u.cigs[roff[i] + u.m_src[k]];
+					else { memset(&m_cigs[(size_t)k], 0, sizeof(bwagpu_cigar_t)); m_cigs[(size_t)k].n_cigar = -1; }
+				}
+			});
+		}
+	}
 	parallel_for(u.opt.n_threads, n, [&](long i) {
 		const Seq &q = w.in.seqs[u.idx[i]];
 		const char *T = w.in.T(q);
-		if (u.cigs) { hints[i].regs = u.all + roff[i]; hints[i].cigs = u.cigs + roff[i]; hints[i].n = u.counts[i]; hints[i].ops = u.cig_ops; reads[i].hints = &hints[i]; }
+		if (u.cigs && u.rescue) { hints[i].regs = u.m_all + moff[i]; hints[i].cigs = m_cigs.data() + moff[i]; hints[i].n = u.m_counts[i]; hints[i].ops = u.cig_ops; reads[i].hints = &hints[i]; }
+		else if (u.cigs) { hints[i].regs = u.all + roff[i]; hints[i].cigs = u.cigs + roff[i]; hints[i].n = u.counts[i]; hints[i].ops = u.cig_ops; reads[i].hints = &hints[i]; }
 		reads[i].name = T + q.name;
 		reads[i].comment = copy_comment && q.has_comment ? T + q.comment : nullptr;
 		reads[i].seq = u.flat.data() + u.off[i]; reads[i].qual = q.has_qual ? T + q.qual : nullptr; reads[i].l_seq = q.l_seq;
-		if (u.pri) reads[i].pri = u.pri + roff[i];
+		if (u.rescue) { reads[i].merged = u.m_all + moff[i]; reads[i].n_merged = u.m_counts[i]; reads[i].pri = u.pri + moff[i]; if (!(i & 1)) reads[i].rescue = u.rescue + (i >> 1); }
+		else if (u.pri) reads[i].pri = u.pri + roff[i];
 		if (u.pairs && !(i & 1)) reads[i].pair = u.pairs + (i >> 1);
 	});
 	if (u.opt.flag & F_PE) for (int i = 0; i + 1 < n; i += 2) if (strcmp(reads[i].name, reads[i + 1].name) != 0) { fprintf(stderr, "[mem_sam_pe] paired reads have different names: \"%s\", \"%s\"\n", reads[i].name, reads[i + 1].name); exit(EXIT_FAILURE); }
@@ -598,6 +646,7 @@ static void finalize_sub(const RefSeqs &ref, Work &w, Sub &u, const Pestat *pes0
 		finalize_batch(u.opt, ref, u.n_processed, n, reads.data(), u.all, roff.data(), pes, u.opt.n_threads, rg_id, sam, g_verbose >= 3);
 		for (int i = 0; i < n; ++i) w.out[u.idx[i]].swap(sam[i]);
 	}
+	if (u.rescue) { free(u.rescue); u.rescue = nullptr; free(u.m_all); u.m_all = nullptr; free(u.m_src); u.m_src = nullptr; }
 	if (u.pairs) { free(u.pairs); u.pairs = nullptr; free(u.pri); u.pri = nullptr; }
 	if (u.pri) { g_n_primary_reads += n; bwagpu_free(u.pri); u.pri = nullptr; }
 	bwagpu_free(u.all); u.all = nullptr; bwagpu_free(u.cigs); u.cigs = nullptr; bwagpu_free(u.cig_ops); u.cig_ops = nullptr; bwagpu_free(u.msw); u.msw = nullptr;
@@ -865,6 +914,7 @@ int main(int argc, char *argv[])
 	if (getenv("BWAGPU_CLI_CIGARS")) g_device_cigars = atoi(getenv("BWAGPU_CLI_CIGARS"));
 	if (getenv("BWAGPU_CLI_PRIMARY")) g_device_primary = atoi(getenv("BWAGPU_CLI_PRIMARY"));
 	if (getenv("BWAGPU_CLI_PAIR")) g_device_pair = atoi(getenv("BWAGPU_CLI_PAIR"));
+	if (getenv("BWAGPU_CLI_RESCUE")) g_device_rescue = atoi(getenv("BWAGPU_CLI_RESCUE"));
 	int n_dev = getenv("BWAGPU_CLI_STREAMS") ? atoi(getenv("BWAGPU_CLI_STREAMS")) : 3;      // batches in flight on the device
 	if (n_dev < 1) n_dev = 1;
 	// devices: BWAGPU_DEVICES=0,1,... (default: the one of BWAGPU_DEVICE).  The index reaches the other devices by device-to-device copies over
@@ -1065,6 +1115,8 @@ int main(int argc, char *argv[])
 	to_out.close();
 	writer.join();
 	all_done = true; watchdog.join();
+	if (g_device_rescue && tl_trace && hostmem::g_pairs_merged_on_device.load() > 0)
+		fprintf(stderr, "[D::main_mem] %ld pairs merged on the device (BWAGPU_CLI_RESCUE), %ld of them with rescue alignments\n", hostmem::g_pairs_merged_on_device.load(), hostmem::g_pairs_merged_aligned.load());
 	if (g_device_pair && tl_trace) fprintf(stderr, "[D::main_mem] %ld pairs paired from device records (BWAGPU_CLI_PAIR)\n", hostmem::g_pairs_from_device.load());
 	if (g_device_primary && tl_trace) fprintf(stderr, "[D::main_mem] %ld reads finalized from device primary/mapQ records (BWAGPU_CLI_PRIMARY)\n", g_n_primary_reads.load());
 	if (g_verbose >= 3) { const double dt = now_s() - t_start; fprintf(stderr, "[M::%s] %ld reads in %.3f sec after the index was loaded: %.0f reads/s\n", "main_mem", n_reads_total.load(), dt, dt > 0 ? n_reads_total.load() / dt : 0.);

@@ -47,6 +47,9 @@ assert PRIMARY_DTYPE.itemsize == 32
 PESTAT_DTYPE = np.dtype({"names": ["low", "high", "failed", "avg", "std"], "formats": ["<i4", "<i4", "<i4", "<f8", "<f8"], "offsets": [0, 4, 8, 16, 24], "itemsize": 32})
 PAIR_DTYPE = np.dtype([("score", "<i4"), ("sub", "<i4"), ("n_sub", "<i4"), ("z", "<i4", (2,)), ("flags", "<i4"), ("n_cand", "<i8")])
 assert PESTAT_DTYPE.itemsize == 32 and PAIR_DTYPE.itemsize == 32
+# bwagpu_rescue_t: what the merge of mate-rescue hits did with one pair (bwagpu_batch_rescue / bwagpu_rescue_flat)
+RESCUE_DTYPE = np.dtype([("n_aligned", "<i4"), ("n_inline", "<i4"), ("flags", "<i4"), ("pad_", "<i4")])
+assert RESCUE_DTYPE.itemsize == 16
 
 INTV_DTYPE = np.dtype([("x0", "<u8"), ("x1", "<u8"), ("x2", "<u8"), ("info", "<u8")])
 SEED_DTYPE = np.dtype([("rbeg", "<i8"), ("qbeg", "<i4"), ("len", "<i4"), ("score", "<i4"), ("_pad", "<i4")])

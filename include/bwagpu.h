@@ -328,6 +328,41 @@ int bwagpu_pair_flat(bwagpu_t *h, const bwagpu_opt_t *opt, const bwagpu_pestat_t
  * wavefront does with its small LDS area, [2] with its large one (pairs with more work in HBM scratch). */
 void bwagpu_pair_limits(int32_t out[3]);
 
+/* The merge of mate-rescue hits on the device: mem_matesw's decision loop as mem_sam_pe drives it (bwamem_pair.c:137-206, :291-302), between the download and
+ * the marking.  For every pair (reads 2p, 2p + 1) the anchors are taken from the lists as downloaded, every rescue alignment the loop asks for is looked up among
+ * the results of bwagpu_batch_matesw's kernels (or computed in place when the initial lists did not foresee it), hits are inserted and the list is sorted and
+ * made non-redundant exactly as mem_sort_dedup_patch does without a reference. */
+typedef struct {
+	int32_t n_aligned;   /* mem_sam_pe's n for this pair (alignments run); -1 when flagged */
+	int32_t n_inline;    /* of those, computed inside the rescue kernel (no precomputed record) */
+	int32_t flags;       /* bit 0: a mate longer than the SW kernel's limit or a window beyond it: lists returned as downloaded, caller rescues itself */
+	int32_t pad_;
+} bwagpu_rescue_t;
+/* After bwagpu_batch_download of a batch whose reads 2p and 2p + 1 are mates (read i has id id0 + i, id0 even).  counts[i]: the length of read i's merged list;
+ * *regs: the merged lists, concatenated, in the order mem_sam_pe has them when it reaches mem_mark_primary_se (every byte as the reference's: a rescued hit is
+ * zero outside rid, is_alt, qb, qe, rb, re, score, csub, secondary = -1, seedcov, and n_comp, which is 1 once a sort of two or more regions has run over the list and 0 for a hit put into an empty list); *src: one entry per merged region, its index
+ * in that read's downloaded list, or -1 - (j << 2 | r) for a hit rescued from anchor j of the other end (the j-th of its regions within pen_unpaired of its best)
+ * in orientation r; *rescue: n / 2 records.  pri / n_pri (may be NULL): what bwagpu_primary_flat returns for the merged lists; pairs (may be NULL): what
+ * bwagpu_pair_flat returns for those records (pair p has id (id0 >> 1) + p).  A flagged pair's lists, and its records, are those of the download.
+ * MEM_F_NO_RESCUE in opt->flag: the lists come back unchanged with n_aligned = 0.  Everything returned is freed with bwagpu_free.  BWAGPU_EINVAL: before a
+ * download, an odd number of reads, an odd id0, a NULL h / opt / pes / counts / regs / src / n_regs / rescue, MEM_F_PRIMARY5 together with pairs. */
+int  bwagpu_batch_rescue(bwagpu_t *h, const bwagpu_opt_t *opt, const bwagpu_pestat_t pes[4], int64_t id0,
+		int32_t *counts /* n reads: merged list lengths */, bwagpu_alnreg_t **regs, int32_t **src, int64_t *n_regs,
+		bwagpu_rescue_t **rescue /* n/2 */,
+		bwagpu_primary_t **pri, int32_t *n_pri,      /* may be NULL: marking of the merged lists */
+		bwagpu_pair_t **pairs,                       /* may be NULL: mem_pair on those records */
+		float *kernel_ms);
+/* The same kernels on reads and lists of the caller: 2 n_pairs reads (nt4 codes 0..4, read i at seqs[off[i] .. off[i + 1])), counts_in[i] regions each,
+ * concatenated in regs_in (rid inside the index); ids: one per read (a pair's id is ids[2p] >> 1), may be NULL when pri and pairs are. */
+int  bwagpu_rescue_flat(bwagpu_t *h, const bwagpu_opt_t *opt, const bwagpu_pestat_t pes[4], int n_pairs,
+		const uint8_t *seqs, const int64_t *off,                       /* 2 n_pairs reads, nt4 */
+		const int32_t *counts_in, const bwagpu_alnreg_t *regs_in, const int64_t *ids /* per read; may be NULL when pri and pairs are */,
+		int32_t *counts, bwagpu_alnreg_t **regs, int32_t **src, int64_t *n_regs, bwagpu_rescue_t **rescue,
+		bwagpu_primary_t **pri, int32_t *n_pri, bwagpu_pair_t **pairs, float *kernel_ms);
+/* The sizes at which the kernels change their form, as compiled: out[0] the capacity of a pair's larger end (its regions plus four per anchor of the other end) up to
+ * which one lane replays the pair, [1] up to which a wavefront does with its sort keys in LDS (larger pairs: keys in HBM scratch); [2], [3] are zero. */
+void bwagpu_rescue_limits(int32_t out[4]);
+
 /* ---- index construction on the device -------------------------------------------------------- */
 /* The arrays `bwa index` leaves in bwt_t after bwt_bwtgen2/bwt_pac2bwt + bwt_bwtupdate_core + bwt_cal_sa
  * (bwtindex.c:64-120, 150-172; bwt.c:62-84), built from the 2-bit packed forward strand by a suffix sort in HBM
