@@ -16,7 +16,7 @@ try:   # torch bundles its own HIP runtime (libamdhip64); loading it first keeps
 except Exception:  # pragma: no cover
     torch = None
 
-from .structs import ALNREG_DTYPE, PAIR_DTYPE, PESTAT_DTYPE, PRIMARY_DTYPE, RESCUE_DTYPE, MemOpt
+from .structs import ALNREG_DTYPE, PAIR_DTYPE, PESTAT_DTYPE, PESTAT_INFO_DTYPE, PRIMARY_DTYPE, RESCUE_DTYPE, MemOpt
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 DEFAULT_LIB = os.path.join(HERE, "csrc", "libbwagpu.so")
@@ -61,6 +61,7 @@ EXPORTS = [
     "bwagpu_tap_chains", "bwagpu_tap_regs_raw", "bwagpu_index_buffers", "bwagpu_index_export", "bwagpu_clone", "bwagpu_index_ready",
     "bwagpu_batch_cigars", "bwagpu_batch_cigar_ops", "bwagpu_debug_phase", "bwagpu_batch_matesw", "bwagpu_clone_to_device", "bwagpu_index_build", "bwagpu_built_free", "bwagpu_abi_sizes", "bwagpu_debug_prof", "bwagpu_debug_hist", "bwagpu_debug_seed_x2", "bwagpu_debug_chain_hist", "bwagpu_debug_dp", "bwagpu_debug_sort", "bwagpu_debug_sort_limits", "bwagpu_set_cigar_filter", "bwagpu_batch_reserve", "bwagpu_batch_footprint", "bwagpu_mem_info",
     "bwagpu_batch_primary", "bwagpu_primary_flat", "bwagpu_primary_limits", "bwagpu_batch_pair", "bwagpu_pair_flat", "bwagpu_pair_limits", "bwagpu_batch_rescue", "bwagpu_rescue_flat", "bwagpu_rescue_limits",
+    "bwagpu_batch_pestat", "bwagpu_pestat_flat", "bwagpu_batch_pestat_hist", "bwagpu_pestat_finish", "bwagpu_pestat_limits",
     "bwagpu_trim", "bwagpu_set_option", "bwagpu_get_option", "bwagpu_set_default_option", "bwagpu_clear_default_options", "bwagpu_option_name",
 ]
 
@@ -118,6 +119,11 @@ def load_library(path: str | None = None) -> C.CDLL:
     L.bwagpu_batch_rescue.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 9
     L.bwagpu_rescue_flat.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 14
     L.bwagpu_rescue_limits.restype = None
+    L.bwagpu_batch_pestat.argtypes = [C.c_void_p] * 5
+    L.bwagpu_pestat_flat.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 5
+    L.bwagpu_batch_pestat_hist.argtypes = [C.c_void_p] * 5
+    L.bwagpu_pestat_finish.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.bwagpu_pestat_limits.restype = None
     L.bwagpu_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_longlong]
     L.bwagpu_get_option.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p]
     L.bwagpu_set_default_option.argtypes = [C.c_char_p, C.c_longlong]
@@ -377,6 +383,41 @@ class BwaGpu:
         out = (C.c_int32 * 4)()
         self.L.bwagpu_rescue_limits(out)
         return dict(zip(("lane_max", "lds_max"), list(out)[:2]))
+
+    def pestat(self, opt: MemOpt):
+        """bwagpu_batch_pestat: mem_pestat of the last download() on the device (reads 2p, 2p + 1 are mates).
+        -> (PESTAT_DTYPE[4], byte for byte the reference's mem_pestat_t[4]; one PESTAT_INFO_DTYPE record; device time of the kernels in ms)"""
+        pes, info, ms = np.zeros(4, dtype=PESTAT_DTYPE), np.zeros(1, dtype=PESTAT_INFO_DTYPE), C.c_float()
+        self._chk(self.L.bwagpu_batch_pestat(self.h, C.byref(opt), pes.ctypes.data, info.ctypes.data, C.byref(ms)))
+        return pes, info[0], ms.value
+
+    def pestat_flat(self, opt: MemOpt, counts: np.ndarray, regs: np.ndarray):
+        """bwagpu_pestat_flat: the same kernels on region lists of the caller (read i: counts[i] records of regs) -> (pes, info, ms)."""
+        counts = np.ascontiguousarray(counts, dtype=np.int32)
+        regs = np.ascontiguousarray(regs, dtype=ALNREG_DTYPE)
+        assert int(counts.sum()) == regs.shape[0]
+        pes, info, ms = np.zeros(4, dtype=PESTAT_DTYPE), np.zeros(1, dtype=PESTAT_INFO_DTYPE), C.c_float()
+        self._chk(self.L.bwagpu_pestat_flat(self.h, C.byref(opt), counts.shape[0], counts.ctypes.data, regs.ctypes.data, pes.ctypes.data, info.ctypes.data, C.byref(ms)))
+        return pes, info[0], ms.value
+
+    def pestat_hist(self, opt: MemOpt):
+        """bwagpu_batch_pestat_hist: the insert-size histogram of the last download(), uint32[4, max_ins + 1] by orientation; histograms of shards add.  -> (hist, ms)"""
+        p, n, ms = C.c_void_p(), C.c_int64(), C.c_float()
+        self._chk(self.L.bwagpu_batch_pestat_hist(self.h, C.byref(opt), C.byref(p), C.byref(n), C.byref(ms)))
+        return self._take(p, n.value, np.dtype("<u4")).reshape(4, -1), ms.value
+
+    def pestat_finish(self, opt: MemOpt, hist: np.ndarray):
+        """bwagpu_pestat_finish: the windows from a histogram (of one handle, or the sum of several handles') -> (pes, info, ms)."""
+        hist = np.ascontiguousarray(hist, dtype=np.uint32)
+        pes, info, ms = np.zeros(4, dtype=PESTAT_DTYPE), np.zeros(1, dtype=PESTAT_INFO_DTYPE), C.c_float()
+        self._chk(self.L.bwagpu_pestat_finish(self.h, C.byref(opt), hist.ctypes.data, hist.size, pes.ctypes.data, info.ctypes.data, C.byref(ms)))
+        return pes, info[0], ms.value
+
+    def pestat_limits(self) -> dict:
+        """bwagpu_pestat_limits: MIN_DIR_CNT and the largest max_ins the device histogram serves, as compiled."""
+        out = (C.c_int32 * 2)()
+        self.L.bwagpu_pestat_limits(out)
+        return dict(zip(("min_dir_cnt", "max_ins"), list(out)))
 
     def debug_dp(self, opt: MemOpt, kind: int, cases: np.ndarray, seqs: np.ndarray) -> np.ndarray:
         """bwagpu_debug_dp: one wavefront of a device DP routine per case (DP_CASE_DTYPE) -> int32[n_cases, 72]."""

@@ -41,6 +41,7 @@
 #include "dev_primary.h"
 #include "dev_pair.h"
 #include "dev_rescue.h"
+#include "dev_pestat.h"
 #include "dev_debug.h"
 
 #define BWAGPU_VERSION "bwagpu 0.1 (gfx950)"
@@ -97,6 +98,7 @@ struct bwagpu_s {
 	DevBuf d_pri_out, d_pri_npri, d_pri_lists, d_pri_ctr, d_pri_scratch, d_pri_log;      // bwagpu_batch_primary / bwagpu_primary_flat: records, return values, the wavefront forms' read lists and their lengths, HBM working arrays, the table of logarithms
 	DevBuf d_pair_out, d_pair_lists, d_pair_ctr, d_pair_scratch, d_pair_tab, d_pair_npri;      // bwagpu_batch_pair / bwagpu_pair_flat: records, the wavefront forms' pair lists and their lengths, HBM working arrays, the table of log(2 erfc) values, bwagpu_pair_flat's n_pri
 	std::vector<double> pair_tab; bwagpu_pestat_t pair_tab_pes[4] = {}; i64 pair_tab_cap = -1; i32 pair_toff[4] = {}, pair_tlen[4] = {}; bool pair_tab_dev = false;   // the table as last filled: for these windows and this capacity; resident in d_pair_tab
+	DevBuf d_pst_hist, d_pst_out;                                                         // bwagpu_batch_pestat and its kin (dev_pestat.h): the histogram of insert sizes, four windows and the info record (PstOut) -- resident for the next device-side consumer
 	DevBuf d_pf_regs, d_pf_cnt, d_pf_off, d_pf_ids;                                       // ... and the uploaded lists of bwagpu_primary_flat
 	std::vector<double> pri_log; i64 pri_log_dev = 0;                                      // log((double)k) by the host's libm for k < size; entries resident in d_pri_log
 	DevBuf d_msw_tasks, d_msw_out, d_msw_pes, d_msw_scratch;
@@ -505,7 +507,7 @@ extern "C" void bwagpu_destroy(bwagpu_t *h)
 		for (DevBuf *b : ib) b->release();
 		delete h->ibuf;
 	}
-	DevBuf *all[] = { &h->d_pair_out, &h->d_pair_lists, &h->d_pair_ctr, &h->d_pair_scratch, &h->d_pair_tab, &h->d_pair_npri, &h->d_pri_out, &h->d_pri_npri, &h->d_pri_lists, &h->d_pri_ctr, &h->d_pri_scratch, &h->d_pri_log, &h->d_pf_regs, &h->d_pf_cnt, &h->d_pf_off, &h->d_pf_ids, &h->d_heavy, &h->d_dd_tmp, &h->d_p2_tasks, &h->d_vr_tab, &h->d_vr_ovf, &h->d_intv_n3, &h->d_cigl_list, &h->d_cigl_z, &h->d_cigl_ops, &h->d_cigl_md, &h->d_seq_2b, &h->d_seq_flags, &h->d_cig_ext, &h->d_msw_tasks, &h->d_msw_out, &h->d_msw_pes, &h->d_msw_scratch, &h->d_pack_off, &h->d_regs_packed, &h->d_pack_read, &h->d_cigs, &h->d_seq, &h->d_seq_nib, &h->d_off, &h->d_ctr, &h->d_tmp_intv,
+	DevBuf *all[] = { &h->d_pst_hist, &h->d_pst_out, &h->d_pair_out, &h->d_pair_lists, &h->d_pair_ctr, &h->d_pair_scratch, &h->d_pair_tab, &h->d_pair_npri, &h->d_pri_out, &h->d_pri_npri, &h->d_pri_lists, &h->d_pri_ctr, &h->d_pri_scratch, &h->d_pri_log, &h->d_pf_regs, &h->d_pf_cnt, &h->d_pf_off, &h->d_pf_ids, &h->d_heavy, &h->d_dd_tmp, &h->d_p2_tasks, &h->d_vr_tab, &h->d_vr_ovf, &h->d_intv_n3, &h->d_cigl_list, &h->d_cigl_z, &h->d_cigl_ops, &h->d_cigl_md, &h->d_seq_2b, &h->d_seq_flags, &h->d_cig_ext, &h->d_msw_tasks, &h->d_msw_out, &h->d_msw_pes, &h->d_msw_scratch, &h->d_pack_off, &h->d_regs_packed, &h->d_pack_read, &h->d_cigs, &h->d_seq, &h->d_seq_nib, &h->d_off, &h->d_ctr, &h->d_tmp_intv,
 		&h->d_intv_n, &h->d_intv_off, &h->d_intv, &h->d_seed_n, &h->d_seed_off, &h->d_slot_pos, &h->d_slot_qbeg, &h->d_slot_len, &h->d_slot_rid, &h->d_slot_blob, &h->d_chain_n, &h->d_node_off,
 		&h->d_order, &h->d_bin_cnt, &h->d_seed_w, &h->d_seed_order, &h->d_nodes, &h->d_reg_off, &h->d_reg_cap_r, &h->d_reg_n_raw, &h->d_reg_n, &h->d_regs, &h->d_regs_raw, &h->d_dp_h, &h->d_dp_e, &h->d_minhsp };
 	for (DevBuf *b : all) b->release();
@@ -2203,6 +2205,143 @@ extern "C" int bwagpu_rescue_flat(bwagpu_t *h, const bwagpu_opt_t *opt, const bw
 	}
 	return rescue_run(h, opt, pes, n_reads, tot, D[bwagpu_s::RS_SEQ].as<u8>(), D[bwagpu_s::RS_SEQOFF].as<i64>(), D[bwagpu_s::RS_CNT_IN].as<i32>(), D[bwagpu_s::RS_OFF_IN].as<i64>(),
 					  D[bwagpu_s::RS_REGS_IN].as<bwagpu_alnreg_t>(), ids ? D[bwagpu_s::RS_IDS].as<i64>() : nullptr, 0, ids, counts, regs, src, n_regs, rescue, pri, n_pri, pairs, kernel_ms);
+}
+
+// ---- insert-size statistics on the device (dev_pestat.h) ------------------------------------------------------------------------------------------
+extern "C" void bwagpu_pestat_limits(int32_t out[2]) { out[0] = PST_MIN_DIR_CNT; out[1] = PST_MAX_INS; }
+
+static i64 pestat_bins(int max_ins) { return max_ins >= 0 ? 4 * ((i64)max_ins + 1) : 0; }
+static void pestat_none(bwagpu_pestat_t pes[4], bwagpu_pestat_info_t *info)      // no pair can qualify: :76 and :96-100 for every orientation
+{
+	memset(pes, 0, 4 * sizeof(bwagpu_pestat_t));
+	for (int d = 0; d < 4; ++d) pes[d].failed = 1;
+	if (info) memset(info, 0, sizeof *info);
+}
+static int pestat_max_ins_ok(bwagpu_t *h, const bwagpu_opt_t *opt)
+{
+	if (opt->max_ins <= PST_MAX_INS) return 1;
+	h->err = "max_ins " + std::to_string(opt->max_ins) + " is beyond the device histogram's " + std::to_string(PST_MAX_INS) + " (bwagpu_pestat_limits): mem_pestat of this batch is the host's";
+	return 0;
+}
+// k_pestat_collect over n_reads / 2 pairs into the handle's histogram (cleared first), in the stream; 1 <= max_ins <= PST_MAX_INS
+static int pestat_collect(bwagpu_t *h, const bwagpu_opt_t *opt, int n_reads, const i32 *d_cnt, const i64 *d_off, const bwagpu_alnreg_t *d_regs)
+{
+	const size_t bytes = (size_t)pestat_bins(opt->max_ins) * 4;
+	if (h->d_pst_hist.ensure(bytes)) { h->err = "hipMalloc failed (pestat)"; return BWAGPU_ENOMEM; }
+	HIPCHK(h, hipMemsetAsync(h->d_pst_hist.p, 0, bytes, h->stream));
+	const int n_pairs = n_reads >> 1;
+	if (n_pairs == 0) return BWAGPU_OK;
+	int nb = (n_pairs + PST_BLOCK - 1) / PST_BLOCK; if (nb > 256 * 8) nb = 256 * 8;
+	hipLaunchKernelGGL(k_pestat_collect, dim3(nb), dim3(PST_BLOCK), 0, h->stream, opt->mask_level, opt->min_seed_len * opt->a, opt->max_ins, h->l_pac, n_pairs, d_cnt, d_off, d_regs, h->d_pst_hist.as<unsigned int>());
+	HIPCHK(h, hipGetLastError());
+	return BWAGPU_OK;
+}
+// k_pestat_finish on the handle's histogram into its result buffer, in the stream
+static int pestat_finish(bwagpu_t *h, const bwagpu_opt_t *opt)
+{
+	if (h->d_pst_out.ensure(sizeof(PstOut))) { h->err = "hipMalloc failed (pestat)"; return BWAGPU_ENOMEM; }
+	HIPCHK(h, hipMemsetAsync(h->d_pst_out.p, 0, sizeof(PstOut), h->stream));
+	hipLaunchKernelGGL(k_pestat_finish, dim3(1), dim3(PST_BLOCK), 0, h->stream, h->d_pst_hist.as<unsigned int>(), opt->max_ins, h->d_pst_out.as<PstOut>());
+	HIPCHK(h, hipGetLastError());
+	return BWAGPU_OK;
+}
+// the result buffer to the host: the call's one wait
+static int pestat_fetch(bwagpu_t *h, bwagpu_pestat_t pes[4], bwagpu_pestat_info_t *info, float *kernel_ms)
+{
+	PstOut o;
+	HIPCHK(h, hipMemcpyAsync(&o, h->d_pst_out.p, sizeof o, hipMemcpyDeviceToHost, h->stream));
+	HIPCHK(h, wait_stream(h));
+	if (kernel_ms) (void)hipEventElapsedTime(kernel_ms, h->ev[0], h->ev[1]);
+	for (int d = 0; d < 4; ++d) if (o.info.n[d] >= ((i64)1 << 31)) { h->err = "2^31 or more pairs in one orientation: beyond mem_pestat's int arithmetic"; return BWAGPU_EINVAL; }
+	memcpy(pes, o.pes, sizeof o.pes);
+	if (info) *info = o.info;
+	return BWAGPU_OK;
+}
+// both kernels as one timed segment, then the fetch
+static int pestat_run(bwagpu_t *h, const bwagpu_opt_t *opt, int n_reads, const i32 *d_cnt, const i64 *d_off, const bwagpu_alnreg_t *d_regs, bwagpu_pestat_t pes[4], bwagpu_pestat_info_t *info, float *kernel_ms)
+{
+	(void)hipEventRecord(h->ev[0], h->stream);
+	int rc = pestat_collect(h, opt, n_reads, d_cnt, d_off, d_regs);
+	if (rc == BWAGPU_OK) rc = pestat_finish(h, opt);
+	(void)hipEventRecord(h->ev[1], h->stream);
+	return rc == BWAGPU_OK ? pestat_fetch(h, pes, info, kernel_ms) : rc;
+}
+
+extern "C" int bwagpu_batch_pestat(bwagpu_t *h, const bwagpu_opt_t *opt, bwagpu_pestat_t pes[4], bwagpu_pestat_info_t *info, float *kernel_ms)
+{
+	if (!h || !opt || !pes || !h->ran || !h->downloaded) return BWAGPU_EINVAL;
+	if (!pestat_max_ins_ok(h, opt)) return BWAGPU_EINVAL;
+	const BusyGuard busy(h->ibuf->busy);
+	HIPCHK(h, hipSetDevice(h->device));
+	if (kernel_ms) *kernel_ms = 0.f;
+	if (h->packed_tot <= 0 || h->n_reads < 2 || opt->max_ins <= 0) { pestat_none(pes, info); return BWAGPU_OK; }      // (without a region the packed arrays may not exist)
+	return pestat_run(h, opt, h->n_reads, h->d_reg_n.as<i32>(), h->d_pack_off.as<i64>(), h->d_regs_packed.as<bwagpu_alnreg_t>(), pes, info, kernel_ms);
+}
+
+extern "C" int bwagpu_pestat_flat(bwagpu_t *h, const bwagpu_opt_t *opt, int n_reads, const int32_t *counts, const bwagpu_alnreg_t *regs,
+								  bwagpu_pestat_t pes[4], bwagpu_pestat_info_t *info, float *kernel_ms)
+{
+	if (!h || !opt || !pes || n_reads < 0 || (n_reads > 0 && !counts)) return BWAGPU_EINVAL;
+	i64 tot = 0;
+	for (int i = 0; i < n_reads; ++i) { if (counts[i] < 0 || counts[i] > 0x3fffffff) return BWAGPU_EINVAL; tot += counts[i]; }
+	if (tot > 0 && !regs) return BWAGPU_EINVAL;
+	if (!pestat_max_ins_ok(h, opt)) return BWAGPU_EINVAL;
+	const BusyGuard busy(h->ibuf->busy);
+	HIPCHK(h, hipSetDevice(h->device));
+	if (kernel_ms) *kernel_ms = 0.f;
+	if (tot == 0 || n_reads < 2 || opt->max_ins <= 0) { pestat_none(pes, info); return BWAGPU_OK; }
+	std::vector<i64> off((size_t)n_reads);
+	i64 k = 0;
+	for (int i = 0; i < n_reads; ++i) { off[i] = k; k += counts[i]; }
+	if (h->d_pf_cnt.ensure((size_t)n_reads * 4) || h->d_pf_off.ensure((size_t)n_reads * 8) || h->d_pf_regs.ensure((size_t)tot * sizeof(bwagpu_alnreg_t))) { h->err = "hipMalloc failed (pestat)"; return BWAGPU_ENOMEM; }
+	HIPCHK(h, hipMemcpyAsync(h->d_pf_cnt.p, counts, (size_t)n_reads * 4, hipMemcpyHostToDevice, h->stream));
+	HIPCHK(h, hipMemcpyAsync(h->d_pf_off.p, off.data(), (size_t)n_reads * 8, hipMemcpyHostToDevice, h->stream));
+	HIPCHK(h, hipMemcpyAsync(h->d_pf_regs.p, regs, (size_t)tot * sizeof(bwagpu_alnreg_t), hipMemcpyHostToDevice, h->stream));
+	HIPCHK(h, wait_stream(h));      // (`off` is a local array)
+	return pestat_run(h, opt, n_reads, h->d_pf_cnt.as<i32>(), h->d_pf_off.as<i64>(), h->d_pf_regs.as<bwagpu_alnreg_t>(), pes, info, kernel_ms);
+}
+
+extern "C" int bwagpu_batch_pestat_hist(bwagpu_t *h, const bwagpu_opt_t *opt, uint32_t **hist, int64_t *n_bins, float *kernel_ms)
+{
+	if (!h || !opt || !hist || !n_bins || !h->ran || !h->downloaded) return BWAGPU_EINVAL;
+	if (!pestat_max_ins_ok(h, opt)) return BWAGPU_EINVAL;
+	const BusyGuard busy(h->ibuf->busy);
+	HIPCHK(h, hipSetDevice(h->device));
+	if (kernel_ms) *kernel_ms = 0.f;
+	const i64 nbins = pestat_bins(opt->max_ins);
+	uint32_t *res = (uint32_t*)result_alloc((size_t)(nbins ? nbins : 1) * 4);
+	if (!res) return BWAGPU_ENOMEM;
+	*hist = nullptr; *n_bins = 0;
+	if (h->packed_tot <= 0 || h->n_reads < 2 || opt->max_ins <= 0) memset(res, 0, (size_t)(nbins ? nbins : 1) * 4);      // nothing to count
+	else {
+		(void)hipEventRecord(h->ev[0], h->stream);
+		const int rc = pestat_collect(h, opt, h->n_reads, h->d_reg_n.as<i32>(), h->d_pack_off.as<i64>(), h->d_regs_packed.as<bwagpu_alnreg_t>());
+		(void)hipEventRecord(h->ev[1], h->stream);
+		if (rc != BWAGPU_OK) { bwagpu_free(res); return rc; }
+		hipError_t e = hipMemcpyAsync(res, h->d_pst_hist.p, (size_t)nbins * 4, hipMemcpyDeviceToHost, h->stream);
+		if (e == hipSuccess) e = wait_stream(h);
+		if (e != hipSuccess) { bwagpu_free(res); HIPCHK(h, e); }
+		if (kernel_ms) (void)hipEventElapsedTime(kernel_ms, h->ev[0], h->ev[1]);
+	}
+	*hist = res; *n_bins = nbins;
+	return BWAGPU_OK;
+}
+
+extern "C" int bwagpu_pestat_finish(bwagpu_t *h, const bwagpu_opt_t *opt, const uint32_t *hist, int64_t n_bins, bwagpu_pestat_t pes[4], bwagpu_pestat_info_t *info, float *kernel_ms)
+{
+	if (!h || !opt || !pes) return BWAGPU_EINVAL;
+	if (!pestat_max_ins_ok(h, opt)) return BWAGPU_EINVAL;
+	if (n_bins != pestat_bins(opt->max_ins) || (n_bins > 0 && !hist)) { h->err = "bwagpu_pestat_finish: the histogram does not have 4 * (max_ins + 1) bins"; return BWAGPU_EINVAL; }
+	const BusyGuard busy(h->ibuf->busy);
+	HIPCHK(h, hipSetDevice(h->device));
+	if (kernel_ms) *kernel_ms = 0.f;
+	if (opt->max_ins <= 0) { pestat_none(pes, info); return BWAGPU_OK; }
+	if (h->d_pst_hist.ensure((size_t)n_bins * 4)) { h->err = "hipMalloc failed (pestat)"; return BWAGPU_ENOMEM; }
+	HIPCHK(h, hipMemcpyAsync(h->d_pst_hist.p, hist, (size_t)n_bins * 4, hipMemcpyHostToDevice, h->stream));
+	(void)hipEventRecord(h->ev[0], h->stream);
+	const int rc = pestat_finish(h, opt);
+	(void)hipEventRecord(h->ev[1], h->stream);
+	return rc == BWAGPU_OK ? pestat_fetch(h, pes, info, kernel_ms) : rc;
 }
 
 extern "C" int bwagpu_align_flat(bwagpu_t *h, const bwagpu_opt_t *opt, int n, const uint8_t *seqs, const int64_t *off,

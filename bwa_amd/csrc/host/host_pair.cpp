@@ -115,6 +115,22 @@ template <class Get> static void pestat_impl(const bwagpu_opt_t &opt, int64_t l_
 		}
 }
 
+// What pestat_impl prints when verbose, from the record the device left (bwagpu_batch_pestat, bwagpu_pestat_finish): the lines in the reference's order.
+void pestat_print(const bwagpu_pestat_info_t &info, const bwagpu_pestat_t pes[4])
+{
+	fprintf(stderr, "[M::%s] # candidate unique pairs for (FF, FR, RF, RR): (%ld, %ld, %ld, %ld)\n", "mem_pestat", (long)info.n[0], (long)info.n[1], (long)info.n[2], (long)info.n[3]);
+	for (int d = 0; d < 4; ++d) {
+		if (info.n[d] < 10) { fprintf(stderr, "[M::%s] skip orientation %c%c as there are not enough pairs\n", "mem_pestat", "FR"[d >> 1 & 1], "FR"[d & 1]); continue; }
+		fprintf(stderr, "[M::%s] analyzing insert size distribution for orientation %c%c...\n", "mem_pestat", "FR"[d >> 1 & 1], "FR"[d & 1]);
+		fprintf(stderr, "[M::%s] (25, 50, 75) percentile: (%d, %d, %d)\n", "mem_pestat", info.p25[d], info.p50[d], info.p75[d]);
+		fprintf(stderr, "[M::%s] low and high boundaries for computing mean and std.dev: (%d, %d)\n", "mem_pestat", info.lo_out[d], info.hi_out[d]);
+		fprintf(stderr, "[M::%s] mean and std.dev: (%.2f, %.2f)\n", "mem_pestat", pes[d].avg, pes[d].std);
+		fprintf(stderr, "[M::%s] low and high boundaries for proper pairs: (%d, %d)\n", "mem_pestat", pes[d].low, pes[d].high);
+	}
+	for (int d = 0; d < 4; ++d)      // (an orientation with enough pairs that has failed fell to MIN_DIR_RATIO)
+		if (info.n[d] >= 10 && pes[d].failed) fprintf(stderr, "[M::%s] skip orientation %c%c\n", "mem_pestat", "FR"[d >> 1 & 1], "FR"[d & 1]);
+}
+
 // mem_pestat on a batch's flat region array (regions of read i at all[roff[i] .. roff[i+1]))
 void pestat_flat(const bwagpu_opt_t &opt, int64_t l_pac, int n, const bwagpu_alnreg_t *all, const int64_t *roff, Pestat pes[4], bool verbose, int n_threads)
 {

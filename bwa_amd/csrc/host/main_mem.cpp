@@ -40,6 +40,7 @@ static int g_verbose = 3;
 static int g_device_matesw = 1;   // BWAGPU_CLI_MATESW=0: the host runs every mate-rescue alignment itself (same output)
 static int g_device_cigars = 1;   // BWAGPU_CLI_CIGARS=0: the host computes every CIGAR itself (same output)
 static int g_device_rescue = 0;   // BWAGPU_CLI_RESCUE=1: paired-end batches take the merged lists, their marking and their mem_pair from the device (bwagpu_batch_rescue, in place of bwagpu_batch_matesw + bwagpu_batch_pair; same output)
+static int g_device_pestat = 0;   // BWAGPU_CLI_PESTAT=1: paired-end batches without -I take mem_pestat's windows from the device (bwagpu_batch_pestat; split over several devices: bwagpu_batch_pestat_hist per shard, summed, bwagpu_pestat_finish; same output)
 static int g_device_pair = 0;     // BWAGPU_CLI_PAIR=1: paired-end batches take the marking and mem_pair of the pairs the rescue loop leaves alone from the device (bwagpu_batch_pair; same output)
 static int g_device_primary = 0;  // BWAGPU_CLI_PRIMARY=1: single-end batches take primary/secondary marking and mapQ from the device (bwagpu_batch_primary; same output)
 static std::atomic<long> g_n_primary_reads(0);   // ... reads finalized from such records (the BWAGPU_CLI_TRACE line at the end of the run)
@@ -455,7 +456,33 @@ static void device_sub(const std::vector<bwagpu_t*> &gpus, Sub &u, const RefSeqs
 	const bool want_matesw = g_device_matesw && pe && !(u.opt.flag & F_NO_RESCUE) && u.tot > 0;
 	double t_pes = 0;
 	std::thread pes_thread;
-	if (want_matesw) {
+	// ... unless the windows come from the device (BWAGPU_CLI_PESTAT): the histogram of the packed lists of the download, right after it -- whether or not
+	// anything on the device needs the windows, so that the finalize stage does not call pestat_flat either.  Several devices: the shards' histograms add.
+	const bool dev_pestat = g_device_pestat && pe && !pes0 && u.opt.max_ins > 0 && u.opt.max_ins <= (1 << 22) && u.tot > 0;
+	if (dev_pestat) {
+		const double tp = now_s();
+		bwagpu_pestat_t dp[4]; bwagpu_pestat_info_t info;
+		if (D == 1) {
+			const int rc = bwagpu_batch_pestat(gpus[0], &u.opt, dp, &info, nullptr);
+			if (rc != BWAGPU_OK) device_fail(gpus[0], rc);
+		} else {
+			std::vector<uint32_t*> hs((size_t)D, nullptr); std::vector<int64_t> nbins((size_t)D, 0);
+			on_devices([&](int d) {
+				const int rc = bwagpu_batch_pestat_hist(gpus[d], &u.opt, &hs[d], &nbins[d], nullptr);
+				if (rc != BWAGPU_OK || nbins[d] != 4 * ((int64_t)u.opt.max_ins + 1)) device_fail(gpus[d], rc, "bwagpu_batch_pestat_hist returned another number of bins than 4 * (max_ins + 1)");
+			});
+			for (int d = 1; d < D; ++d) { for (int64_t k = 0; k < nbins[0]; ++k) hs[0][k] += hs[d][k]; bwagpu_free(hs[d]); }
+			const int rc = bwagpu_pestat_finish(gpus[0], &u.opt, hs[0], nbins[0], dp, &info, nullptr);
+			if (rc != BWAGPU_OK) device_fail(gpus[0], rc);
+			bwagpu_free(hs[0]);
+		}
+		for (int d = 0; d < 4; ++d) { u.pes[d].low = dp[d].low; u.pes[d].high = dp[d].high; u.pes[d].failed = dp[d].failed; u.pes[d].avg = dp[d].avg; u.pes[d].std = dp[d].std; }
+		u.have_pes = true;
+		if (g_verbose >= 3) pestat_print(info, dp);
+		t_pes = now_s() - tp;
+		if (trace) fprintf(stderr, "[D::device_sub] insert-size windows from %d device(s) (BWAGPU_CLI_PESTAT): %.3f s\n", D, t_pes);
+	}
+	if (want_matesw && !dev_pestat) {
 		if (pes0) memcpy(u.pes, pes0, sizeof u.pes);
 		else pes_thread = std::thread([&] {
 			const double tp = now_s();
@@ -915,6 +942,7 @@ int main(int argc, char *argv[])
 	if (getenv("BWAGPU_CLI_PRIMARY")) g_device_primary = atoi(getenv("BWAGPU_CLI_PRIMARY"));
 	if (getenv("BWAGPU_CLI_PAIR")) g_device_pair = atoi(getenv("BWAGPU_CLI_PAIR"));
 	if (getenv("BWAGPU_CLI_RESCUE")) g_device_rescue = atoi(getenv("BWAGPU_CLI_RESCUE"));
+	if (getenv("BWAGPU_CLI_PESTAT")) g_device_pestat = atoi(getenv("BWAGPU_CLI_PESTAT"));
 	int n_dev = getenv("BWAGPU_CLI_STREAMS") ? atoi(getenv("BWAGPU_CLI_STREAMS")) : 3;      // batches in flight on the device
 	if (n_dev < 1) n_dev = 1;
 	// devices: BWAGPU_DEVICES=0,1,... (default: the one of BWAGPU_DEVICE).  The index reaches the other devices by device-to-device copies over

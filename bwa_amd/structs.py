@@ -64,6 +64,11 @@ class MemPestat(C.Structure):
 
 assert C.sizeof(MemPestat) == 32 == PESTAT_DTYPE.itemsize and MemPestat.avg.offset == 16
 
+# bwagpu_pestat_info_t: what mem_pestat prints and what its scalars were made from, per orientation
+PESTAT_INFO_DTYPE = np.dtype([("n", "<i8", (4,)), ("p25", "<i4", (4,)), ("p50", "<i4", (4,)), ("p75", "<i4", (4,)), ("lo_out", "<i4", (4,)), ("hi_out", "<i4", (4,)),
+                              ("x", "<i8", (4,)), ("sum", "<f8", (4,)), ("sumsq", "<f8", (4,))])
+assert PESTAT_INFO_DTYPE.itemsize == 208
+
 
 def default_opt() -> MemOpt:
     """mem_opt_init() defaults (bwamem.c:74-110) incl. bwa_fill_scmat (bwa.c:136-145)."""

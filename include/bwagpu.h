@@ -363,6 +363,34 @@ int  bwagpu_rescue_flat(bwagpu_t *h, const bwagpu_opt_t *opt, const bwagpu_pesta
  * which one lane replays the pair, [1] up to which a wavefront does with its sort keys in LDS (larger pairs: keys in HBM scratch); [2], [3] are zero. */
 void bwagpu_rescue_limits(int32_t out[4]);
 
+/* The insert-size windows on the device: mem_pestat (bwamem_pair.c:72-135), the step of the paired-end path that needs the whole batch (bwamem.c:1258) and
+ * whose result, pes[4], every call above takes.  A kernel with one lane per pair (reads 2p, 2p + 1; a trailing unpaired read is ignored) applies the filter of
+ * :78-90 and counts the insert sizes into a histogram of 4 x (max_ins + 1) bins; a second kernel reads the order statistics, the mean, the standard deviation and
+ * the windows off the histogram.  pes is byte for byte the reference's mem_pestat_t[4], padding zero.  The histograms of several shards add, bin by bin. */
+typedef struct {            /* what mem_pestat prints and what its scalars were made from */
+	int64_t n[4];           /* candidate unique pairs per orientation (isize[d].n) */
+	int32_t p25[4], p50[4], p75[4];
+	int32_t lo_out[4], hi_out[4];   /* bounds used for mean and std.dev (:106-108) */
+	int64_t x[4];           /* values inside them */
+	double  sum[4], sumsq[4];       /* avg = sum / x, std = sqrt(sumsq / x) */
+} bwagpu_pestat_info_t;     /* (fields of an orientation with fewer than MIN_DIR_CNT pairs are zero, n apart) */
+/* After bwagpu_batch_download (the preconditions of bwagpu_batch_primary): mem_pestat of the downloaded lists.  info and kernel_ms (device time of both kernels,
+ * HIP events) may be NULL.  A batch without any region, fewer than two reads, or opt->max_ins <= 0: four failed orientations, nothing is launched.  The result
+ * also stays in a device buffer of the handle.  BWAGPU_EINVAL: before a download, NULL h / opt / pes, opt->max_ins above the limit (bwagpu_pestat_limits; see
+ * bwagpu_last_error -- the caller keeps its host function for that case). */
+int  bwagpu_batch_pestat(bwagpu_t *h, const bwagpu_opt_t *opt, bwagpu_pestat_t pes[4], bwagpu_pestat_info_t *info, float *kernel_ms);
+/* The same kernels on lists of the caller (read i: counts[i] regions, concatenated in regs; of a region qb, qe, score, rid and rb are read). */
+int  bwagpu_pestat_flat (bwagpu_t *h, const bwagpu_opt_t *opt, int n_reads, const int32_t *counts, const bwagpu_alnreg_t *regs,
+                         bwagpu_pestat_t pes[4], bwagpu_pestat_info_t *info, float *kernel_ms);
+/* The first kernel alone, for a batch cut over several handles: *hist receives the 4 * (max_ins + 1) counts of this handle's downloaded lists, orientation by
+ * orientation (*n_bins of them; 0 for a negative max_ins); free with bwagpu_free.  Preconditions and errors as bwagpu_batch_pestat. */
+int  bwagpu_batch_pestat_hist(bwagpu_t *h, const bwagpu_opt_t *opt, uint32_t **hist, int64_t *n_bins, float *kernel_ms);  /* 4 * (max_ins + 1) counts; bwagpu_free */
+/* The second kernel alone on a histogram of the caller -- the element-wise sum of the shards' -- on any handle, before or after a run.  BWAGPU_EINVAL also for
+ * n_bins other than 4 * (max_ins + 1) and for 2^31 or more pairs in one orientation.  _hist followed by _finish on one handle is bwagpu_batch_pestat. */
+int  bwagpu_pestat_finish(bwagpu_t *h, const bwagpu_opt_t *opt, const uint32_t *hist, int64_t n_bins,
+                          bwagpu_pestat_t pes[4], bwagpu_pestat_info_t *info, float *kernel_ms);
+void bwagpu_pestat_limits(int32_t out[2]);   /* MIN_DIR_CNT, largest max_ins served (1 << 22) */
+
 /* ---- index construction on the device -------------------------------------------------------- */
 /* The arrays `bwa index` leaves in bwt_t after bwt_bwtgen2/bwt_pac2bwt + bwt_bwtupdate_core + bwt_cal_sa
  * (bwtindex.c:64-120, 150-172; bwt.c:62-84), built from the 2-bit packed forward strand by a suffix sort in HBM
