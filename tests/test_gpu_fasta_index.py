@@ -9,6 +9,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import degenerate_cases
 import fasta_cases
 import refapi
 from bwa_amd import simdata
@@ -48,6 +49,21 @@ def test_gpu_fasta_corpus_equals_bwa_index(tmp_path):
             assert not _diff(mine, ref), (p, chunk, _diff(mine, ref))
 
 
+def test_gpu_fasta_degenerate_texts_equal_bwa_index(tmp_path):
+    """The FASTA route on texts of tests/degenerate_cases.py: a genome of one base, a 20 kb poly-A, contigs of one base, two equal contigs."""
+    need_ref()
+    cases = degenerate_cases.index_cases()
+    for name in ("rand1", "polyA20000", "contig_of_one_base", "two_equal_contigs"):
+        g = cases[name]
+        fa = str(tmp_path / (name + ".fa"))
+        simdata.write_fasta(fa, g, degenerate_cases.contig_lens(name, g))
+        refapi.build_index(fa)
+        mine = str(tmp_path / ("mine_" + name))
+        info = build_index_from_fasta(fa, mine)
+        assert info["l_pac"] == g.shape[0] and info["n_seqs"] == len(degenerate_cases.contig_lens(name, g)), name
+        assert not _diff(mine, fa), (name, _diff(mine, fa))
+
+
 def test_gpu_fasta_parse_one_byte_chunks():
     for name, data in fasta_cases.small_cases().items():
         want = parse_fasta(_Bytes(data))
@@ -63,6 +79,16 @@ class _Bytes:
         out = self.data[self.pos:self.pos + n]
         self.pos += len(out)
         return out
+
+
+def mem_sam_pair(cli, runs, args):
+    """SAM text (without @PG) of `bwa mem` and of `cli mem`, each on its own (index prefix, input files) of `runs`; both must exit 0."""
+    outs = []
+    for binary, (idx, files) in zip((refapi.REF_BWA, cli), runs):
+        p = subprocess.run([binary, "mem"] + list(args) + [idx] + list(files), stdout=subprocess.PIPE, stderr=subprocess.PIPE)
+        assert p.returncode == 0, (binary, p.stderr.decode()[-1000:])
+        outs.append(b"\n".join(l for l in p.stdout.split(b"\n") if not l.startswith(b"@PG")))
+    return outs
 
 
 def test_gpu_cli_index_64mbp_and_mem(tmp_path):
@@ -84,10 +110,6 @@ def test_gpu_cli_index_64mbp_and_mem(tmp_path):
     r1, r2 = simdata.make_reads_pe(g, 20000, seed=66)
     f1, f2 = str(tmp_path / "h1.fq"), str(tmp_path / "h2.fq")
     simdata.write_fastq(f1, r1, suffix="/1"); simdata.write_fastq(f2, r2, suffix="/2")
-    outs = []
-    for binary, idx in ((refapi.REF_BWA, fa), (cli, str(tmp_path / "gpu0"))):
-        p = subprocess.run([binary, "mem", "-K", "10000000", "-t", "16", idx, f1, f2], stdout=subprocess.PIPE, stderr=subprocess.PIPE)
-        assert p.returncode == 0, p.stderr.decode()[-1000:]
-        outs.append(b"\n".join(l for l in p.stdout.split(b"\n") if not l.startswith(b"@PG")))
+    outs = mem_sam_pair(cli, ((fa, [f1, f2]), (str(tmp_path / "gpu0"), [f1, f2])), ["-K", "10000000", "-t", "16"])
     assert outs[0] == outs[1], "SAM on the bwa-amd index"
     assert outs[0].count(b"\n") >= 40000

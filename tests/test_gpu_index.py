@@ -14,8 +14,10 @@ import shutil
 import numpy as np
 import pytest
 
+import degenerate_cases
 import refapi
 import testdata
+import test_index_build
 from cmputil import assert_regs_equal
 from bwa_amd import simdata
 from bwa_amd.index import build_index
@@ -47,6 +49,56 @@ def test_gpu_built_index_equals_bwa_index_64mbp():
     for ext in ("bwt", "sa", "pac", "ann", "amb"):
         os.remove(prefix + "." + ext); os.remove(fa + "." + ext)
     os.remove(fa)
+
+
+@pytest.fixture(scope="module")
+def degenerate_ref():
+    """`bwa index` of every text of tests/degenerate_cases.py, and `bwa bwt2sa -i` of each .bwt at the other SA intervals, under TMP; removed afterwards."""
+    import subprocess
+    need_ref()
+    d = os.path.join(TMP, "degenerate")
+    os.makedirs(d, exist_ok=True)
+    out = {}
+    for name, g in degenerate_cases.index_cases().items():
+        fa = os.path.join(d, name + ".fa")
+        simdata.write_fasta(fa, g, degenerate_cases.contig_lens(name, g))
+        refapi.build_index(fa)
+        for intv in SA_INTERVALS:
+            subprocess.run([refapi.REF_BWA, "bwt2sa", "-i", str(intv), fa + ".bwt", fa + f".sa{intv}"], check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
+        out[name] = (g, degenerate_cases.contigs(name, g), fa)
+    yield out, d
+    shutil.rmtree(d, ignore_errors=True)
+
+
+SA_INTERVALS = (1, 2, 64)
+
+
+@pytest.mark.parametrize("env", test_index_build.BUILDER_ENVS, ids=["default", "buckets2", "buckets3_split_sort", "buckets6"])
+def test_gpu_index_degenerate_texts_equal_bwa_index(monkeypatch, degenerate_ref, env):
+    """The device twin of tests/test_index_build.py::test_index_degenerate_texts_equal_bwa_index: texts shorter than a key, a prefix-table entry, an Occ
+    block, a packed word and an SA sample, and texts that are all repeat, through every form of the builder with rocPRIM's own sorts and scans (the two-sort
+    form of a doubling round among them).  All five files equal `bwa index`'s."""
+    ref, d = degenerate_ref
+    for k in ("BWAGPU_INDEX_BUCKET_BASES", "BWAGPU_INDEX_SPLIT_SORT"):
+        monkeypatch.delenv(k, raising=False)
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    assert len(ref) == 75
+    bad = test_index_build.degenerate_mismatches(ref, d)
+    assert not bad, f"{len(bad)} of {len(ref)} texts under {env}:\n" + "\n".join(bad)
+
+
+@pytest.mark.parametrize("intv", SA_INTERVALS)
+def test_gpu_index_degenerate_texts_sa_intervals(monkeypatch, degenerate_ref, intv):
+    """build_index(..., sa_intv=) on the same texts against the reference's `bwa bwt2sa -i`: n_sa = (n + intv) / intv down to n = 2 (one base), every row
+    stored at interval 1, none but the header's at 64 on the shortest texts; sa[0] is never stored."""
+    ref, d = degenerate_ref
+    for k in ("BWAGPU_INDEX_BUCKET_BASES", "BWAGPU_INDEX_SPLIT_SORT"):
+        monkeypatch.delenv(k, raising=False)
+    fa1 = ref["rand1"][2]
+    assert os.path.getsize(fa1 + f".sa{intv}") == 56 + 8 * ((2 + intv) // intv - 1)      # (bwt_dump_sa: 7 words, then n_sa - 1 values)
+    bad = test_index_build.degenerate_mismatches(ref, d, sa_intv=intv)
+    assert not bad, f"{len(bad)} of {len(ref)} texts at sa_intv {intv}:\n" + "\n".join(bad)
 
 
 L_BIG = 2_200_000_000          # seq_len = 4.4e9 > 2^32

@@ -603,3 +603,120 @@ def test_many_contigs_with_alt_at_scale(tmp_path):
             outs.append(b"\n".join(l for l in p.stdout.split(b"\n") if not l.startswith(b"@PG")))
         assert outs[0] == outs[1], f"SAM with 3000 ALT contigs, {len(files)} file(s)"
         assert outs[0].count(b"AH:*") == n_alt and b"\tpa:f:" in outs[0] and b"\tXA:Z:" in outs[0]
+
+
+# ---- tiny and degenerate genomes (tests/degenerate_cases.py) ----------------------------------------------------------------------------------------------
+import degenerate_cases
+
+DEGENERATE_OPTIONS = [{"ptab_m": 0}, {"occ32": 0}, {"chain_regs": 0}] + [
+    {"dedup_heavy": h, "dedup_stage": s, "dedup_big": b, "dedup_net": n} for h, s, b, n in ((0, -1, -1, -1), (2, 16, -1, 12), (2, 16, 32, 0), (8, 0, -1, -1), (-1, 512, 0, 4))]
+                                                                                # (the settings of test_dedup_list_gives_identical_results, all of them)
+
+
+def _degenerate_index(d, name):
+    g, lens, reads = degenerate_cases.align_cases()[name]
+    fa = os.path.join(str(d), name + ".fa")
+    simdata.write_fasta(fa, g, lens)
+    import refapi
+    refapi.build_index(fa)
+    return fa, g, reads
+
+
+def check_degenerate_genome(make, name, fa, g, reads):
+    """make(options) -> a handle on the index `fa`.  Every read of `reads`, under every setting: regions, interval taps, chain taps and marking records
+    against the compiled reference."""
+    import refapi
+    import test_primary
+    opt = default_opt()
+    seqs, off = testdata.ragged(reads)
+    ref = refapi.RefIndex(fa)
+    dev = make({})
+    try:
+        want = ref.align(opt, seqs, off)
+        if name in degenerate_cases.MANY_REGIONS:
+            # the reference's own output says the batch is the many-regions case: beyond the marking kernel's small LDS form and the sorts' counting form,
+            # and on polyA2000 beyond twice that (the <1024> form of k_primary_wave with room to spare; max_occ caps a read at 500 regions)
+            wide = max(dev.primary_limits()["lds_small"], dev.debug_sort_limits()["dd_net_default"] - 1)
+            assert int(want[0].max()) > wide, (name, want[0].tolist())
+            assert name != "polyA2000" or int(want[0].max()) > 2 * wide, (name, want[0].tolist())
+        dev.set_taps(True)
+        dev.upload(seqs, off); dev.run(opt)
+        counts, regs = dev.download()
+        assert_regs_equal(*want, counts, regs, f"{name}, SA interval as loaded")
+        # SA intervals, read by read: k = 0, the primary row inside, a symbol's whole range
+        n_iv, iv = dev.tap_intervals()
+        k = 0
+        for i, rd in enumerate(reads):
+            w = ref.intervals(opt, np.ascontiguousarray(rd))
+            got = iv[k:k + n_iv[i]]
+            k += int(n_iv[i])
+            assert n_iv[i] == w.shape[0], f"{name}, read {i}: {n_iv[i]} intervals, reference {w.shape[0]}"
+            for f in ("x0", "x2", "info"):
+                assert np.array_equal(got[f], w[f]), f"{name}, read {i}: interval field {f}"
+        assert k == iv.shape[0]
+        # chains and their seeds after mem_chain_flt
+        cn, ch, cs = dev.tap_chains()
+        kc = ks = 0
+        for i, rd in enumerate(reads):
+            hdr, seeds = ref.chains(opt, np.ascontiguousarray(rd), 1)
+            assert cn[i] == hdr.shape[0], f"{name}, read {i}: {cn[i]} chains, reference {hdr.shape[0]}"
+            ns = int(hdr["n"].sum())
+            got_h, got_s = ch[kc:kc + cn[i]], cs[ks:ks + ns]
+            for f, gname in (("n_seeds", "n"), ("rid", "rid"), ("w", "w"), ("kept", "kept"), ("is_alt", "is_alt"), ("frac_rep", "frac_rep"), ("pos", "pos")):
+                assert np.array_equal(got_h[f], hdr[gname]), f"{name}, read {i}: chain field {f}"
+            for f in ("rbeg", "qbeg", "len"):
+                assert np.array_equal(got_s[f], seeds[f]), f"{name}, read {i}: seed field {f}"
+            kc += int(cn[i]); ks += ns
+        assert kc == ch.shape[0] and ks == cs.shape[0]
+        # marking and mapQ of the same download (k_primary_lane / k_primary_wave in each of its forms) against the reference's own functions
+        for id0 in (0, (1 << 33) + 5):
+            ids = id0 + np.arange(counts.shape[0], dtype=np.int64)
+            w_rec, w_np = test_primary.ref_primary(opt, counts, regs, ids)
+            rec, n_pri, _ = dev.primary(opt, id0)
+            test_primary.assert_records_equal(rec, n_pri, w_rec, w_np, counts, f"{name}, marking records, id0 {id0}")
+        for intv in (2, 1):
+            dev.densify_sa(intv)
+            assert_regs_equal(*want, *dev.align(opt, seqs, off), f"{name}, SA densified to {intv}")
+    finally:
+        dev.close()
+    for options in DEGENERATE_OPTIONS:
+        dev = make(options)
+        try:
+            assert_regs_equal(*want, *dev.align(opt, seqs, off), f"{name}, options {options}")
+        finally:
+            dev.close()
+    ref.close()
+    return want
+
+
+@pytest.mark.parametrize("name", degenerate_cases.ALIGN_NAMES)
+def test_degenerate_genomes_vs_reference(tmp_path, name):
+    """Genomes shorter than a prefix-table entry, an Occ block or an SA sample, and genomes that are all repeat (reads with hundreds of regions, SA
+    intervals wider than max_occ, duplicate chain positions): regions byte for byte the compiled reference's mem_align1_core with the SA as loaded and
+    densified, without prefix tables, on the 64-byte blocks, with the tree form of chaining and under every listing of k_dedup_wave; interval and chain
+    taps and the marking records equal the reference's.  No read is left out."""
+    import refapi
+    from bwa_amd.api import BwaGpu
+    assert refapi.have_ref(), "oracle/_ref (the compiled reference) is missing on the GPU box"
+    assert set(degenerate_cases.ALIGN_NAMES) == set(degenerate_cases.align_cases())
+    fa, g, reads = _degenerate_index(tmp_path, name)
+    check_degenerate_genome(lambda options: BwaGpu(fa, options=options), name, fa, g, reads)
+
+
+@pytest.mark.parametrize("name", ["polyA300", "tandem3", "two_equal_contigs"])
+def test_degenerate_genomes_cli_sam_equals_bwa_mem(tmp_path, name):
+    """`bwa-amd mem` against `bwa mem`, single-end, on pure repeats and on two equal contigs: k_cigar on repeats, XA lists, supplementary records."""
+    import refapi
+    from test_gpu_fasta_index import mem_sam_pair
+    from bwa_amd import build as b
+    assert refapi.have_ref(), "oracle/_ref (the compiled reference) is missing on the GPU box"
+    _, cli = b.build_host(verbose=False)
+    fa, g, reads = _degenerate_index(tmp_path, name)
+    fq = str(tmp_path / "reads.fq")
+    degenerate_cases.write_fastq(fq, reads)
+    want, got = mem_sam_pair(cli, ((fa, [fq]), (fa, [fq])), ["-t", "2"])
+    if got != want:
+        for a, c in zip(want.split(b"\n"), got.split(b"\n")):
+            assert a == c, f"{name}: first differing SAM line\nwant {a[:300]!r}\ngot  {c[:300]!r}"
+    assert got == want, name
+    assert want.count(b"\n") >= len(reads)

@@ -303,6 +303,38 @@ def test_hostsim_occ32_layout_across_superblocks():
     orc.close()
 
 
+def test_hostsim_degenerate_genomes(tmp_path):
+    """The alignment subset of tests/degenerate_cases.py (genomes of 1 to 200 bases, poly-A, tandem repeats, a palindrome, X + rc(X), X + X, contigs of one
+    base, two equal contigs; polyA2000 is left to the device, tests/test_gpu_parity.py): every read's regions equal the compiled reference's
+    mem_align1_core, with the prefix tables and the 32-byte blocks and without either."""
+    import degenerate_cases
+    import refapi
+    if not refapi.have_ref():
+        pytest.skip("oracle/_ref not built (needed to index the genomes)")
+    most = {}
+    for name, (g, lens, reads) in degenerate_cases.align_cases().items():
+        if name == "polyA2000":
+            continue
+        fa = str(tmp_path / (name + ".fa"))
+        simdata.write_fasta(fa, g, lens)
+        refapi.build_index(fa)
+        seqs, off = testdata.ragged(reads)
+        ref = refapi.RefIndex(fa)
+        want = ref.align(default_opt(), seqs, off)
+        ref.close()
+        most[name] = int(want[0].max())
+        for options in ({}, {"ptab_m": 0, "occ32": 0}):
+            s2 = sim_handle(fa, **options)
+            try:
+                assert_regs_equal(*want, *s2.align(default_opt(), seqs, off), f"{name} (l_pac {g.shape[0]}), options {options}")
+                wide = s2.primary_limits()["lds_small"]
+            finally:
+                s2.close()
+    # (from the reference's own output) the repeats really are the many-regions case: a read with more regions than the first LDS forms hold
+    for name in degenerate_cases.MANY_REGIONS:
+        assert name == "polyA2000" or most[name] > wide, (name, most[name])
+
+
 @pytest.mark.parametrize("env", [{}, {"occ32": 0}])
 def test_hostsim_densified_sa_equals_the_walk(env):
     """bwagpu_densify_sa fills the new samples from one LF walk per OLD sample (k_densify); every kept row must hold what the oracle's
