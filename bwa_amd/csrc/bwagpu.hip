@@ -18,6 +18,7 @@
 #include <algorithm>
 #include <atomic>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -99,11 +100,11 @@ struct bwagpu_s {
 	DevBuf d_pair_out, d_pair_lists, d_pair_ctr, d_pair_scratch, d_pair_tab, d_pair_npri;      // bwagpu_batch_pair / bwagpu_pair_flat: records, the wavefront forms' pair lists and their lengths, HBM working arrays, the table of log(2 erfc) values, bwagpu_pair_flat's n_pri
 	std::vector<double> pair_tab; bwagpu_pestat_t pair_tab_pes[4] = {}; i64 pair_tab_cap = -1; i32 pair_toff[4] = {}, pair_tlen[4] = {}; bool pair_tab_dev = false;   // the table as last filled: for these windows and this capacity; resident in d_pair_tab
 	DevBuf d_pst_hist, d_pst_out;                                                         // bwagpu_batch_pestat and its kin (dev_pestat.h): the histogram of insert sizes, four windows and the info record (PstOut) -- resident for the next device-side consumer
-	DevBuf d_pf_regs, d_pf_cnt, d_pf_off, d_pf_ids;                                       // ... and the uploaded lists of bwagpu_primary_flat
+	DevBuf d_pf_regs, d_pf_cnt, d_pf_off, d_pf_ids;                                       // ... and the uploaded lists of the *_flat calls (FlatLists)
 	std::vector<double> pri_log; i64 pri_log_dev = 0;                                      // log((double)k) by the host's libm for k < size; entries resident in d_pri_log
 	DevBuf d_msw_tasks, d_msw_out, d_msw_pes, d_msw_scratch;
-	enum { RS_X, RS_TOFF, RS_TIX, RS_ARENA, RS_ASRC, RS_ACNT, RS_POFF, RS_REGS, RS_SRC, RS_OUT, RS_LISTS, RS_CTR, RS_KEYS, RS_STAGE, RS_SEQ, RS_SEQOFF, RS_IDS, RS_PAIRIDS, RS_CNT_IN, RS_OFF_IN, RS_REGS_IN, RS_N };
-	DevBuf d_rs[RS_N];      // bwagpu_batch_rescue / bwagpu_rescue_flat (dev_rescue.h): anchors x 4 per read and their prefix sums, the task table, the arena of working lists (regions, src, lengths), the packed merged lists (offsets, regions, src), records, the wavefront forms' pair lists and their lengths, HBM sort keys; bwagpu_rescue_flat's uploads
+	enum { RS_X, RS_TOFF, RS_TIX, RS_ARENA, RS_ASRC, RS_ACNT, RS_POFF, RS_REGS, RS_SRC, RS_OUT, RS_LISTS, RS_CTR, RS_KEYS, RS_STAGE, RS_SEQ, RS_SEQOFF, RS_PAIRIDS, RS_N };
+	DevBuf d_rs[RS_N];      // bwagpu_batch_rescue / bwagpu_rescue_flat (dev_rescue.h): anchors x 4 per read and their prefix sums, the task table, the arena of working lists (regions, src, lengths), the packed merged lists (offsets, regions, src), records, the wavefront forms' pair lists and their lengths, HBM sort keys; bwagpu_rescue_flat's sequences, the pairs' ids
 	i64 cigl_z_cap = 0;                          // bytes per direction matrix of the long CIGAR tier's scratch (grows with the batches)
 	DevBuf d_cigl_z, d_cigl_ops, d_cigl_md, d_cigl_list;      // scratch of the long-segment CIGAR tier (k_cigar_long): direction matrices, operations, MD strings per workgroup
 	DevBuf d_cig_ext; i64 cig_ext_n = -1;   // operation array of the last bwagpu_batch_cigars (records with 7..64 operations point into it)
@@ -1562,12 +1563,101 @@ extern "C" int bwagpu_batch_cigar_ops(bwagpu_t *h, uint32_t **ops, int64_t *n_op
 	return BWAGPU_OK;
 }
 
-// The task kernels of mate rescue on n reads (reads 2p, 2p + 1 mates; sequences d_seq / d_seqoff, lists d_cnt / d_off / d_regs): k_matesw_tasks, then k_matesw_sw
-// on the *nt tasks it found, results in d_msw_out.  d_toff / d_tix: the table of dev_rescue.h, or null.  Returns with the alignment kernel in the stream.
-static int matesw_launch(bwagpu_t *h, const bwagpu_opt_t *opt, const bwagpu_pes_t pes[4], int n, const u8 *d_seq, const i64 *d_seqoff, const i32 *d_cnt, const i64 *d_off,
-						 const bwagpu_alnreg_t *d_regs, const i64 *d_toff, i32 *d_tix, i64 task_cap, unsigned long long *n_tasks_out)
+// ---- what the post-alignment stages share (mate rescue, marking, pairing, insert sizes) ------------------------------------------------------------
+// A result block until it goes to the caller (`*out = r.release()`, the last statement that can fail behind it): every other way out of a function hands it
+// back through bwagpu_free, so HIPCHK and plain returns work while one is held.
+struct ResultFree { void operator()(void *p) const { bwagpu_free(p); } };
+template <class T> using ResultBlock = std::unique_ptr<T[], ResultFree>;
+template <class T> static ResultBlock<T> result_block(size_t n) { return ResultBlock<T>((T*)result_alloc((n ? n : 1) * sizeof(T))); }
+
+// The region lists of n reads, tot regions in all, the longest of max_cnt.  On the device: counts d_cnt, offsets d_off into d_regs, read i's id d_ids[i] or (null)
+// id0 + i.  h_*: the same arrays on the host, each null where the host has none -- ListsMirror then brings it over for the records that come back flagged.
+struct RegLists {
+	int n = 0, max_cnt = 0; i64 tot = 0;
+	const i32 *d_cnt = nullptr; const i64 *d_off = nullptr; const bwagpu_alnreg_t *d_regs = nullptr; const i64 *d_ids = nullptr; i64 id0 = 0;
+	const i32 *h_cnt = nullptr; const i64 *h_off = nullptr; const bwagpu_alnreg_t *h_regs = nullptr; const i64 *h_ids = nullptr;
+};
+// the packed regions of the last download
+static RegLists lists_of_batch(const bwagpu_t *h, i64 id0)
 {
-	const int waves = 1024;
+	RegLists L; L.n = h->n_reads; L.tot = h->packed_tot < 0 ? 0 : h->packed_tot; L.max_cnt = h->packed_max; L.id0 = id0;
+	L.d_cnt = h->d_reg_n.as<i32>(); L.d_off = h->d_pack_off.as<i64>(); L.d_regs = h->d_regs_packed.as<bwagpu_alnreg_t>();
+	return L;
+}
+// Counts, offsets and regions of L that are not on the host, fetched into vectors of this object (one wait); L.h_* then point at them.
+struct ListsMirror {
+	std::vector<i32> cnt; std::vector<i64> off; std::vector<bwagpu_alnreg_t> regs;
+	hipError_t fetch(bwagpu_t *h, RegLists &L)
+	{
+		hipError_t e = hipSuccess;
+		if (!L.h_cnt) { cnt.resize((size_t)L.n); e = hipMemcpyAsync(cnt.data(), L.d_cnt, (size_t)L.n * 4, hipMemcpyDeviceToHost, h->stream); L.h_cnt = cnt.data(); }
+		if (e == hipSuccess && !L.h_off) { off.resize((size_t)L.n); e = hipMemcpyAsync(off.data(), L.d_off, (size_t)L.n * 8, hipMemcpyDeviceToHost, h->stream); L.h_off = off.data(); }
+		if (e == hipSuccess && !L.h_regs) { regs.resize((size_t)(L.tot ? L.tot : 1)); if (L.tot) e = hipMemcpyAsync(regs.data(), L.d_regs, (size_t)L.tot * sizeof(bwagpu_alnreg_t), hipMemcpyDeviceToHost, h->stream); L.h_regs = regs.data(); }
+		return e == hipSuccess ? wait_stream(h) : e;
+	}
+};
+// The lists of a *_flat call: n counts and the regions back to back.  scan(): what all these calls require of them -- counts of 0 .. 2^30 - 1, regions where a
+// count is positive and, where the call checks contigs (rid_n, or null), the first rid_n[i] <= counts[i] regions of list i on a contig of the index -- and the
+// offsets, the total, the largest count; false: BWAGPU_EINVAL.  upload(): into the handle's d_pf_* buffers (with n_ids ids, or none), waits -- `off` is this
+// object's --, and describes them in L with the caller's arrays as the host mirror.  `what` names the call in the error text.
+struct FlatLists {
+	std::vector<i64> off; size_t n = 0; i64 tot = 0; int max_cnt = 0;
+	bool scan(const bwagpu_t *h, size_t n_, const i32 *counts, const bwagpu_alnreg_t *regs, const i32 *rid_n)
+	{
+		n = n_; off.assign(n + 1, 0);
+		for (size_t i = 0; i < n; ++i) {
+			if (counts[i] < 0 || counts[i] > 0x3fffffff || (counts[i] > 0 && !regs)) return false;
+			for (int k = 0; rid_n && k < rid_n[i]; ++k) if (regs[tot + k].rid < 0 || regs[tot + k].rid >= h->n_seqs) return false;
+			if (counts[i] > max_cnt) max_cnt = counts[i];
+			off[i] = tot; tot += counts[i];
+		}
+		off[n] = tot;
+		return true;
+	}
+	int upload(bwagpu_t *h, const char *what, const i32 *counts, const bwagpu_alnreg_t *regs, const i64 *ids, size_t n_ids, RegLists &L)
+	{
+		L = RegLists(); L.n = (int)n; L.tot = tot; L.max_cnt = max_cnt;
+		if (n == 0) return BWAGPU_OK;
+		if (h->d_pf_cnt.ensure(n * 4) || h->d_pf_off.ensure((n + 1) * 8) || (ids && h->d_pf_ids.ensure(n_ids * 8)) || h->d_pf_regs.ensure((size_t)(tot ? tot : 1) * sizeof(bwagpu_alnreg_t))) {
+			h->err = std::string("hipMalloc failed (") + what + ")"; return BWAGPU_ENOMEM;
+		}
+		HIPCHK(h, hipMemcpyAsync(h->d_pf_cnt.p, counts, n * 4, hipMemcpyHostToDevice, h->stream));
+		HIPCHK(h, hipMemcpyAsync(h->d_pf_off.p, off.data(), (n + 1) * 8, hipMemcpyHostToDevice, h->stream));
+		if (ids) HIPCHK(h, hipMemcpyAsync(h->d_pf_ids.p, ids, n_ids * 8, hipMemcpyHostToDevice, h->stream));
+		if (tot) HIPCHK(h, hipMemcpyAsync(h->d_pf_regs.p, regs, (size_t)tot * sizeof(bwagpu_alnreg_t), hipMemcpyHostToDevice, h->stream));
+		HIPCHK(h, wait_stream(h));
+		L.d_cnt = h->d_pf_cnt.as<i32>(); L.d_off = h->d_pf_off.as<i64>(); L.d_regs = h->d_pf_regs.as<bwagpu_alnreg_t>(); L.d_ids = ids ? h->d_pf_ids.as<i64>() : nullptr;
+		L.h_cnt = counts; L.h_off = off.data(); L.h_regs = regs; L.h_ids = ids;
+		return BWAGPU_OK;
+	}
+};
+// the largest argument a logarithm of the marking can get: a region's longer side, its seed coverage, its incoming sub_n plus the increments of both rounds plus one
+static i64 pri_log_need(const i32 *counts, const bwagpu_alnreg_t *regs, int n)
+{
+	i64 need = 0, k = 0;
+	for (int i = 0; i < n; ++i)
+		for (int j = 0; j < counts[i]; ++j, ++k) {
+			const bwagpu_alnreg_t &a = regs[k];
+			const i64 lq = (i64)a.qe - a.qb, lr = a.re - a.rb, sn = (i64)a.sub_n + 2 * (i64)counts[i] + 1;
+			need = std::max(std::max(need, lq), std::max(std::max(lr, sn), (i64)a.seedcov));
+		}
+	return need;
+}
+// the largest n_pri[2p] + n_pri[2p + 1]: sizes the pairing kernels' HBM form
+static i64 max_pair_sum(const i32 *npri, int np)
+{
+	i64 m = 0;
+	for (int p = 0; p < np; ++p) m = std::max(m, (i64)npri[2 * (size_t)p] + npri[2 * (size_t)p + 1]);
+	return m;
+}
+static bwagpu_pes_t pes_of(const bwagpu_pestat_t &pe) { bwagpu_pes_t r; r.low = pe.low; r.high = pe.high; r.failed = pe.failed; r.pad_ = 0; return r; }
+
+// The task kernels of mate rescue on the reads of L (reads 2p, 2p + 1 mates; sequences d_seq / d_seqoff): k_matesw_tasks, then k_matesw_sw on the *nt tasks it
+// found, results in d_msw_out.  d_toff / d_tix: the table of dev_rescue.h, or null.  Returns with the alignment kernel in the stream.
+static int matesw_launch(bwagpu_t *h, const bwagpu_opt_t *opt, const bwagpu_pes_t pes[4], const RegLists &L, const u8 *d_seq, const i64 *d_seqoff, const i64 *d_toff, i32 *d_tix,
+						 i64 task_cap, unsigned long long *n_tasks_out)
+{
+	const int waves = 1024, n = L.n;
 	if (h->d_msw_tasks.ensure((size_t)task_cap * sizeof(MateTask)) || h->d_msw_out.ensure((size_t)task_cap * sizeof(bwagpu_matesw_t)) ||
 		h->d_msw_pes.ensure(4 * sizeof(bwagpu_pes_t)) || h->d_ctr.ensure(sizeof(Counters))) {
 		h->err = "hipMalloc failed (mate rescue)"; return BWAGPU_ENOMEM;
@@ -1578,7 +1668,7 @@ static int matesw_launch(bwagpu_t *h, const bwagpu_opt_t *opt, const bwagpu_pes_
 	HIPCHK(h, hipMemcpyAsync(h->d_msw_pes.p, pes, 4 * sizeof(bwagpu_pes_t), hipMemcpyHostToDevice, h->stream));
 	int nb = (n / 2 + BLOCK - 1) / BLOCK; if (nb > 8192) nb = 8192; if (nb < 1) nb = 1;
 	(void)hipEventRecord(h->ev[4], h->stream);      // (ev[4] .. ev[5]: the task kernel; ev[6]: ahead of the alignment kernel -- rescue_run's kernel time is the sum of its segments, not a span over its host waits)
-	hipLaunchKernelGGL(k_matesw_tasks, dim3(nb), dim3(BLOCK), 0, h->stream, h->ix, *opt, n, d_cnt, d_off, d_regs,
+	hipLaunchKernelGGL(k_matesw_tasks, dim3(nb), dim3(BLOCK), 0, h->stream, h->ix, *opt, n, L.d_cnt, L.d_off, L.d_regs,
 					   h->d_msw_pes.as<bwagpu_pes_t>(), h->d_msw_tasks.as<MateTask>(), n_tasks, task_cap, d_toff, d_tix);
 	HIPCHK(h, hipGetLastError());
 	(void)hipEventRecord(h->ev[5], h->stream);
@@ -1609,17 +1699,15 @@ extern "C" int bwagpu_batch_matesw(bwagpu_t *h, const bwagpu_opt_t *opt, const b
 	*out = nullptr; *n_out = 0;
 	if (n == 0 || h->packed_tot == 0) { *out = (bwagpu_matesw_t*)malloc(sizeof(bwagpu_matesw_t)); return *out ? BWAGPU_OK : BWAGPU_ENOMEM; }
 	unsigned long long nt = 0;
-	const int rc = matesw_launch(h, opt, pes, n, h->d_seq.as<u8>(), h->d_off.as<i64>(), h->d_reg_n.as<i32>(), h->d_pack_off.as<i64>(), h->d_regs_packed.as<bwagpu_alnreg_t>(), nullptr, nullptr,
-								 (i64)n * 2 + 1024 /* more candidates than this are simply left to the host */, &nt);
+	const int rc = matesw_launch(h, opt, pes, lists_of_batch(h, 0), h->d_seq.as<u8>(), h->d_off.as<i64>(), nullptr, nullptr, (i64)n * 2 + 1024 /* more candidates than this are simply left to the host */, &nt);
 	if (rc != BWAGPU_OK) { (void)wait_stream(h); return rc; }
-	bwagpu_matesw_t *res = (bwagpu_matesw_t*)result_alloc((size_t)(nt ? nt : 1) * sizeof(bwagpu_matesw_t));
+	ResultBlock<bwagpu_matesw_t> res = result_block<bwagpu_matesw_t>((size_t)nt);
 	if (!res) { (void)wait_stream(h); return BWAGPU_ENOMEM; }
 	if (nt) {
-		hipError_t e = hipMemcpyAsync(res, h->d_msw_out.p, (size_t)nt * sizeof(bwagpu_matesw_t), hipMemcpyDeviceToHost, h->stream);
-		if (e == hipSuccess) e = wait_stream(h);
-		if (e != hipSuccess) { bwagpu_free(res); HIPCHK(h, e); }
+		HIPCHK(h, hipMemcpyAsync(res.get(), h->d_msw_out.p, (size_t)nt * sizeof(bwagpu_matesw_t), hipMemcpyDeviceToHost, h->stream));
+		HIPCHK(h, wait_stream(h));
 	}
-	*out = res; *n_out = (int64_t)nt;
+	*out = res.release(); *n_out = (int64_t)nt;
 	return BWAGPU_OK;
 }
 
@@ -1627,16 +1715,16 @@ extern "C" int bwagpu_batch_matesw(bwagpu_t *h, const bwagpu_opt_t *opt, const b
 extern "C" void bwagpu_primary_limits(int32_t out[4]) { out[0] = PRI_LANE_MAX; out[1] = PRI_LDS_SMALL; out[2] = PRI_LDS_BIG; out[3] = PRI_SCAN; }
 
 static const i64 PRI_LOG_MAX = (i64)1 << 22;      // entries the table of logarithms is grown to at most (32 MB); arguments beyond it are the host's
-// The kernels of both entry points on n_reads lists (counts d_cnt, offsets d_off into d_regs; ids d_ids, or id0 + i): records to a result block (*out), return
-// values to n_pri.  max_cnt = the largest count (sizes the HBM form), log_need = the largest argument of a logarithm to expect; host_cnt / host_regs:
-// the lists on the host, or null -- they are then fetched from the device if a record comes back flagged.
-static int primary_run(bwagpu_t *h, const bwagpu_opt_t *opt, int n_reads, i64 tot, int max_cnt, i64 log_need, const i32 *d_cnt, const i64 *d_off, const bwagpu_alnreg_t *d_regs,
-					   const i64 *d_ids, i64 id0, const i32 *host_cnt, const bwagpu_alnreg_t *host_regs, bwagpu_primary_t **out, int32_t *n_pri, float *kernel_ms)
+// The kernels of both entry points on the lists L (its largest count sizes the HBM form): records to a result block (*out), return values to n_pri.
+// log_need = the largest argument of a logarithm to expect.
+static int primary_run(bwagpu_t *h, const bwagpu_opt_t *opt, RegLists L, i64 log_need, bwagpu_primary_t **out, int32_t *n_pri, float *kernel_ms)
 {
+	const int n_reads = L.n, max_cnt = L.max_cnt;
+	const i64 tot = L.tot;
 	if (kernel_ms) *kernel_ms = 0.f;
-	bwagpu_primary_t *res = (bwagpu_primary_t*)result_alloc((size_t)(tot ? tot : 1) * sizeof(bwagpu_primary_t));
+	ResultBlock<bwagpu_primary_t> res = result_block<bwagpu_primary_t>((size_t)tot);
 	if (!res) return BWAGPU_ENOMEM;
-	if (n_reads == 0) { *out = res; return BWAGPU_OK; }
+	if (n_reads == 0) { *out = res.release(); return BWAGPU_OK; }
 	// the table of logarithms: the host's log() of every integer a mapQ of this batch can ask for (option pri_log_cap: a table of exactly that many entries, for tests)
 	i64 log_n = log_need + 1 < 4096 ? 4096 : log_need + 1;
 	if (log_n > PRI_LOG_MAX) log_n = PRI_LOG_MAX;
@@ -1646,7 +1734,7 @@ static int primary_run(bwagpu_t *h, const bwagpu_opt_t *opt, int n_reads, i64 to
 	const void *log_was = h->d_pri_log.p;
 	if (h->d_pri_out.ensure((size_t)(tot ? tot : 1) * sizeof(bwagpu_primary_t)) || h->d_pri_npri.ensure((size_t)n_reads * 4) || h->d_pri_lists.ensure((size_t)n_reads * 3 * 4) ||
 		h->d_pri_ctr.ensure(4 * sizeof(unsigned int)) || h->d_pri_log.ensure((size_t)log_n * 8) || (n_hbm && h->d_pri_scratch.ensure((size_t)n_hbm * max_cnt * PRI_WORDS * 4))) {
-		bwagpu_free(res); h->err = "hipMalloc failed (primary)"; return BWAGPU_ENOMEM;
+		h->err = "hipMalloc failed (primary)"; return BWAGPU_ENOMEM;
 	}
 	hipError_t e = hipSuccess;
 	if (h->pri_log_dev < log_n || h->d_pri_log.p != log_was) { /* (a buffer that had to grow is a new one) */ e = hipMemcpyAsync(h->d_pri_log.p, h->pri_log.data(), (size_t)log_n * 8, hipMemcpyHostToDevice, h->stream); h->pri_log_dev = log_n; }
@@ -1658,57 +1746,50 @@ static int primary_run(bwagpu_t *h, const bwagpu_opt_t *opt, int n_reads, i64 to
 	(void)hipEventRecord(h->ev[0], h->stream);
 	if (e == hipSuccess) {
 		int nb = (n_reads + PRI_LANE_BLOCK - 1) / PRI_LANE_BLOCK; if (nb > 256 * 12) nb = 256 * 12;
-		hipLaunchKernelGGL(k_primary_lane, dim3(nb), dim3(PRI_LANE_BLOCK), 0, h->stream, *opt, n_reads, d_cnt, d_off, d_regs, d_ids, id0, lg, d_out, d_npri, lists, list_n);
+		hipLaunchKernelGGL(k_primary_lane, dim3(nb), dim3(PRI_LANE_BLOCK), 0, h->stream, *opt, n_reads, L.d_cnt, L.d_off, L.d_regs, L.d_ids, L.id0, lg, d_out, d_npri, lists, list_n);
 		e = hipGetLastError();
 	}
 	// the wavefront forms draw their reads from the lists the first kernel left (their lengths stay on the device); a form no read of the batch can need is not launched
 	if (e == hipSuccess && max_cnt > PRI_LANE_MAX) {
 		const int nb = n_reads < 256 * 16 ? n_reads : 256 * 16;
-		hipLaunchKernelGGL(k_primary_wave<PRI_LDS_SMALL>, dim3(nb), dim3(64), 0, h->stream, *opt, d_cnt, d_off, d_regs, d_ids, id0, lg, d_out, d_npri, lists, list_n, (u64*)nullptr, 0);
+		hipLaunchKernelGGL(k_primary_wave<PRI_LDS_SMALL>, dim3(nb), dim3(64), 0, h->stream, *opt, L.d_cnt, L.d_off, L.d_regs, L.d_ids, L.id0, lg, d_out, d_npri, lists, list_n, (u64*)nullptr, 0);
 		e = hipGetLastError();
 	}
 	if (e == hipSuccess && max_cnt > PRI_LDS_SMALL) {
 		const int nb = n_reads < 256 * 3 ? n_reads : 256 * 3;
-		hipLaunchKernelGGL(k_primary_wave<PRI_LDS_BIG>, dim3(nb), dim3(64), 0, h->stream, *opt, d_cnt, d_off, d_regs, d_ids, id0, lg, d_out, d_npri, lists + n_reads, list_n + 1, (u64*)nullptr, 0);
+		hipLaunchKernelGGL(k_primary_wave<PRI_LDS_BIG>, dim3(nb), dim3(64), 0, h->stream, *opt, L.d_cnt, L.d_off, L.d_regs, L.d_ids, L.id0, lg, d_out, d_npri, lists + n_reads, list_n + 1, (u64*)nullptr, 0);
 		e = hipGetLastError();
 	}
 	if (e == hipSuccess && n_hbm) {
-		hipLaunchKernelGGL(k_primary_wave<0>, dim3(n_hbm), dim3(64), 0, h->stream, *opt, d_cnt, d_off, d_regs, d_ids, id0, lg, d_out, d_npri, lists + (size_t)2 * n_reads, list_n + 2, h->d_pri_scratch.as<u64>(), max_cnt);
+		hipLaunchKernelGGL(k_primary_wave<0>, dim3(n_hbm), dim3(64), 0, h->stream, *opt, L.d_cnt, L.d_off, L.d_regs, L.d_ids, L.id0, lg, d_out, d_npri, lists + (size_t)2 * n_reads, list_n + 2, h->d_pri_scratch.as<u64>(), max_cnt);
 		e = hipGetLastError();
 	}
 	(void)hipEventRecord(h->ev[1], h->stream);
 	std::vector<i32> np((size_t)n_reads);
-	if (e == hipSuccess && tot) e = hipMemcpyAsync(res, d_out, (size_t)tot * sizeof(bwagpu_primary_t), hipMemcpyDeviceToHost, h->stream);
+	if (e == hipSuccess && tot) e = hipMemcpyAsync(res.get(), d_out, (size_t)tot * sizeof(bwagpu_primary_t), hipMemcpyDeviceToHost, h->stream);
 	if (e == hipSuccess) e = hipMemcpyAsync(np.data(), d_npri, (size_t)n_reads * 4, hipMemcpyDeviceToHost, h->stream);
 	if (e == hipSuccess) e = wait_stream(h);
-	if (e != hipSuccess) { bwagpu_free(res); HIPCHK(h, e); }
+	HIPCHK(h, e);
 	if (kernel_ms) (void)hipEventElapsedTime(kernel_ms, h->ev[0], h->ev[1]);
-	for (int i = 0; i < n_reads; ++i) if (np[i] < 0) { bwagpu_free(res); h->err = "internal: a read outgrew the marking kernel's working arrays"; return BWAGPU_EHIP; }
+	for (int i = 0; i < n_reads; ++i) if (np[i] < 0) { h->err = "internal: a read outgrew the marking kernel's working arrays"; return BWAGPU_EHIP; }
 	if (n_pri) memcpy(n_pri, np.data(), (size_t)n_reads * 4);
 	// records whose mapQ needed a logarithm outside the table: the same function with the host's log()
 	bool any = false;
 	for (i64 k = 0; k < tot && !any; ++k) any = (res[k].flags & 1) != 0;
 	if (any) {
-		std::vector<i32> cnt_; std::vector<bwagpu_alnreg_t> regs_;
-		if (!host_cnt) {
-			cnt_.resize((size_t)n_reads); regs_.resize((size_t)tot);
-			e = hipMemcpyAsync(cnt_.data(), d_cnt, (size_t)n_reads * 4, hipMemcpyDeviceToHost, h->stream);
-			if (e == hipSuccess) e = hipMemcpyAsync(regs_.data(), d_regs, (size_t)tot * sizeof(bwagpu_alnreg_t), hipMemcpyDeviceToHost, h->stream);
-			if (e == hipSuccess) e = wait_stream(h);
-			if (e != hipSuccess) { bwagpu_free(res); HIPCHK(h, e); }
-			host_cnt = cnt_.data(); host_regs = regs_.data();
-		}
+		ListsMirror M;
+		HIPCHK(h, M.fetch(h, L));
 		i64 base = 0;
 		for (int i = 0; i < n_reads; ++i) {
-			for (int k = 0; k < host_cnt[i]; ++k) {
+			for (int k = 0; k < L.h_cnt[i]; ++k) {
 				bwagpu_primary_t &r = res[base + k];
 				int miss = 0;
-				if (r.flags & 1) r.mapq = pri_mapq(*opt, host_regs[base + r.src], r.sub, r.sub_n, PriLogLibm(), miss);
+				if (r.flags & 1) r.mapq = pri_mapq(*opt, L.h_regs[base + r.src], r.sub, r.sub_n, PriLogLibm(), miss);
 			}
-			base += host_cnt[i];
+			base += L.h_cnt[i];
 		}
 	}
-	*out = res;
+	*out = res.release();
 	return BWAGPU_OK;
 }
 
@@ -1724,15 +1805,14 @@ extern "C" int bwagpu_batch_primary(bwagpu_t *h, const bwagpu_opt_t *opt, int64_
 	if (h->packed_max + 2 > log_need) log_need = h->packed_max + 2;
 	*out = nullptr; *n_out = 0;
 	if (tot == 0) {      // no region in the whole batch: nothing to run (and the packed arrays may not exist)
-		bwagpu_primary_t *res = (bwagpu_primary_t*)result_alloc(sizeof(bwagpu_primary_t));
+		ResultBlock<bwagpu_primary_t> res = result_block<bwagpu_primary_t>(0);
 		if (!res) return BWAGPU_ENOMEM;
 		if (n_pri) for (int i = 0; i < h->n_reads; ++i) n_pri[i] = 0;
 		if (kernel_ms) *kernel_ms = 0.f;
-		*out = res;
+		*out = res.release();
 		return BWAGPU_OK;
 	}
-	const int rc = primary_run(h, opt, h->n_reads, tot, h->packed_max, log_need, h->d_reg_n.as<i32>(), h->d_pack_off.as<i64>(), h->d_regs_packed.as<bwagpu_alnreg_t>(), nullptr, id0,
-							   nullptr, nullptr, out, n_pri, kernel_ms);
+	const int rc = primary_run(h, opt, lists_of_batch(h, id0), log_need, out, n_pri, kernel_ms);
 	if (rc == BWAGPU_OK) *n_out = tot;
 	return rc;
 }
@@ -1741,38 +1821,13 @@ extern "C" int bwagpu_primary_flat(bwagpu_t *h, const bwagpu_opt_t *opt, int n_r
 								   bwagpu_primary_t **out, int32_t *n_pri, float *kernel_ms)
 {
 	if (!h || !opt || n_reads < 0 || !out || (n_reads > 0 && (!counts || !ids))) return BWAGPU_EINVAL;
-	i64 tot = 0; int max_cnt = 0;
-	for (int i = 0; i < n_reads; ++i) { if (counts[i] < 0 || counts[i] > 0x3fffffff) return BWAGPU_EINVAL; tot += counts[i]; if (counts[i] > max_cnt) max_cnt = counts[i]; }
-	if (tot > 0 && !regs) return BWAGPU_EINVAL;
+	FlatLists F; RegLists L;
+	if (!F.scan(h, (size_t)n_reads, counts, regs, nullptr)) return BWAGPU_EINVAL;
 	const BusyGuard busy(h->ibuf->busy);
 	HIPCHK(h, hipSetDevice(h->device));
 	*out = nullptr;
-	// the largest argument a logarithm can get: a region's longer side, its seed coverage, its incoming sub_n plus the increments of both rounds plus one
-	std::vector<i64> off((size_t)n_reads);
-	i64 log_need = 0, k = 0;
-	for (int i = 0; i < n_reads; ++i) {
-		off[i] = k;
-		for (int j = 0; j < counts[i]; ++j, ++k) {
-			const bwagpu_alnreg_t &a = regs[k];
-			const i64 lq = (i64)a.qe - a.qb, lr = a.re - a.rb, sn = (i64)a.sub_n + 2 * (i64)counts[i] + 1;
-			if (lq > log_need) log_need = lq;
-			if (lr > log_need) log_need = lr;
-			if (a.seedcov > log_need) log_need = a.seedcov;
-			if (sn > log_need) log_need = sn;
-		}
-	}
-	if (n_reads && (h->d_pf_cnt.ensure((size_t)n_reads * 4) || h->d_pf_off.ensure((size_t)n_reads * 8) || h->d_pf_ids.ensure((size_t)n_reads * 8) || h->d_pf_regs.ensure((size_t)(tot ? tot : 1) * sizeof(bwagpu_alnreg_t)))) {
-		h->err = "hipMalloc failed (primary)"; return BWAGPU_ENOMEM;
-	}
-	if (n_reads) {
-		HIPCHK(h, hipMemcpyAsync(h->d_pf_cnt.p, counts, (size_t)n_reads * 4, hipMemcpyHostToDevice, h->stream));
-		HIPCHK(h, hipMemcpyAsync(h->d_pf_off.p, off.data(), (size_t)n_reads * 8, hipMemcpyHostToDevice, h->stream));
-		HIPCHK(h, hipMemcpyAsync(h->d_pf_ids.p, ids, (size_t)n_reads * 8, hipMemcpyHostToDevice, h->stream));
-		if (tot) HIPCHK(h, hipMemcpyAsync(h->d_pf_regs.p, regs, (size_t)tot * sizeof(bwagpu_alnreg_t), hipMemcpyHostToDevice, h->stream));
-		HIPCHK(h, wait_stream(h));      // (`off` is a local array)
-	}
-	return primary_run(h, opt, n_reads, tot, max_cnt, log_need, h->d_pf_cnt.as<i32>(), h->d_pf_off.as<i64>(), h->d_pf_regs.as<bwagpu_alnreg_t>(), h->d_pf_ids.as<i64>(), 0,
-					   counts, regs, out, n_pri, kernel_ms);
+	const int rc = F.upload(h, "primary", counts, regs, ids, (size_t)n_reads, L);
+	return rc != BWAGPU_OK ? rc : primary_run(h, opt, L, pri_log_need(counts, regs, n_reads), out, n_pri, kernel_ms);
 }
 
 // ---- pairing on the device (dev_pair.h) ------------------------------------------------------------------------------------------------------------
@@ -1791,7 +1846,7 @@ static double pair_tab_value(i64 dist, const bwagpu_pestat_t &pe)
 static bwagpu_pair_t pair_host(const bwagpu_opt_t &opt, const bwagpu_pestat_t pes[4], i64 l_pac, const std::vector<i64> &ctg_off, const bwagpu_alnreg_t *a0, const bwagpu_primary_t *s0, int n0,
 							   const bwagpu_alnreg_t *a1, const bwagpu_primary_t *s1, int n1, int id)
 {
-	bwagpu_pair_t rec; rec.score = rec.sub = rec.n_sub = 0; rec.z[0] = rec.z[1] = -1; rec.flags = 1; rec.n_cand = 0;
+	bwagpu_pair_t rec = pair_none(); rec.flags = 1;
 	std::vector<std::pair<u64, u64>> v;
 	for (int r = 0; r < 2; ++r)
 		for (int i = 0; i < (r ? n1 : n0); ++i) {
@@ -1828,18 +1883,18 @@ static bwagpu_pair_t pair_host(const bwagpu_opt_t &opt, const bwagpu_pestat_t pe
 	return rec;
 }
 
-// The kernels of both entry points on n_pairs pairs (reads 2p, 2p + 1: lists at d_off[] of d_regs, the first d_npri[] places of each; d_src: the marking records
-// at the same offsets, or null; ids d_ids, or id0 + p): records to a result block (*out).  max_sum = the largest n_pri[2p] + n_pri[2p + 1] to expect (sizes the HBM
-// form).  The same lists on the host, for the pairs that come back flagged: host_npri, and host_off / host_regs (tot regions) / host_ids or null -- they are then
-// fetched from the device --, host_src (null with d_src).
-static int pair_run(bwagpu_t *h, const bwagpu_opt_t *opt, const bwagpu_pestat_t pes[4], int n_pairs, i64 tot, i64 max_sum, const i32 *d_npri, const i64 *d_off, const bwagpu_alnreg_t *d_regs,
-					const bwagpu_primary_t *d_src, const i64 *d_ids, i64 id0, const i32 *host_npri, const i64 *host_off, const bwagpu_alnreg_t *host_regs, const bwagpu_primary_t *host_src,
-					const i64 *host_ids, bwagpu_pair_t **out, float *kernel_ms)
+// What pairing reads besides the lists, on the device and (always) on the host: the first npri[] places of each list take part; src: the marking records at the
+// lists' offsets, or null on both sides; pair p has id ids[p], or (null on both sides) id0 + p -- the lists' own ids are the reads'.
+struct PairSel { const i32 *d_npri, *h_npri; const bwagpu_primary_t *d_src, *h_src; const i64 *d_ids, *h_ids; i64 id0; };
+// The kernels of both entry points on the L.n / 2 pairs of the lists L (reads 2p, 2p + 1) as S selects them: records to a result block (*out).
+static int pair_run(bwagpu_t *h, const bwagpu_opt_t *opt, const bwagpu_pestat_t pes[4], RegLists L, const PairSel &S, bwagpu_pair_t **out, float *kernel_ms)
 {
+	const int n_pairs = L.n / 2;
+	const i64 max_sum = max_pair_sum(S.h_npri, n_pairs);
 	if (kernel_ms) *kernel_ms = 0.f;
-	bwagpu_pair_t *res = (bwagpu_pair_t*)result_alloc((size_t)(n_pairs ? n_pairs : 1) * sizeof(bwagpu_pair_t));
+	ResultBlock<bwagpu_pair_t> res = result_block<bwagpu_pair_t>((size_t)n_pairs);
 	if (!res) return BWAGPU_ENOMEM;
-	if (n_pairs == 0) { *out = res; return BWAGPU_OK; }
+	if (n_pairs == 0) { *out = res.release(); return BWAGPU_OK; }
 	// the table: for every orientation that has not failed, the distances low .. high as far as the capacity goes, in the order of the orientations
 	const i64 cap = h->cfg.pair_tab_cap > 0 ? h->cfg.pair_tab_cap : PAIR_TAB_DEFAULT;
 	if (!h->pair_tab_dev || h->pair_tab_cap != cap || memcmp(h->pair_tab_pes, pes, sizeof h->pair_tab_pes) != 0) {
@@ -1855,11 +1910,11 @@ static int pair_run(bwagpu_t *h, const bwagpu_opt_t *opt, const bwagpu_pestat_t 
 		memcpy(h->pair_tab_pes, pes, sizeof h->pair_tab_pes); h->pair_tab_cap = cap; h->pair_tab_dev = false;
 	}
 	const int n_hbm = max_sum > PAIR_LDS_BIG ? (n_pairs < 64 ? n_pairs : 64) : 0;      // workgroups of the HBM form
-	if (max_sum > 0x3fffffff) { bwagpu_free(res); return BWAGPU_EINVAL; }
+	if (max_sum > 0x3fffffff) return BWAGPU_EINVAL;
 	const void *tab_was = h->d_pair_tab.p;
 	if (h->d_pair_out.ensure((size_t)n_pairs * sizeof(bwagpu_pair_t)) || h->d_pair_lists.ensure((size_t)n_pairs * 3 * 4) || h->d_pair_ctr.ensure(4 * sizeof(unsigned int)) ||
 		h->d_pair_tab.ensure(h->pair_tab.size() * 8) || (n_hbm && h->d_pair_scratch.ensure((size_t)n_hbm * (size_t)max_sum * PAIR_WORDS * 4))) {
-		bwagpu_free(res); h->err = "hipMalloc failed (pair)"; return BWAGPU_ENOMEM;
+		h->err = "hipMalloc failed (pair)"; return BWAGPU_ENOMEM;
 	}
 	hipError_t e = hipSuccess;
 	if (!h->pair_tab_dev || h->d_pair_tab.p != tab_was) { e = hipMemcpyAsync(h->d_pair_tab.p, h->pair_tab.data(), h->pair_tab.size() * 8, hipMemcpyHostToDevice, h->stream); h->pair_tab_dev = true; }
@@ -1873,49 +1928,46 @@ static int pair_run(bwagpu_t *h, const bwagpu_opt_t *opt, const bwagpu_pestat_t 
 	(void)hipEventRecord(h->ev[0], h->stream);
 	if (e == hipSuccess) {
 		int nb = (n_pairs + PAIR_LANE_BLOCK - 1) / PAIR_LANE_BLOCK; if (nb > 256 * 12) nb = 256 * 12;
-		hipLaunchKernelGGL(k_pair_lane, dim3(nb), dim3(PAIR_LANE_BLOCK), 0, h->stream, *opt, P, h->l_pac, h->n_seqs, ctg, n_pairs, d_npri, d_off, d_regs, d_src, d_ids, id0, d_out, lists, list_n);
+		hipLaunchKernelGGL(k_pair_lane, dim3(nb), dim3(PAIR_LANE_BLOCK), 0, h->stream, *opt, P, h->l_pac, h->n_seqs, ctg, n_pairs, S.d_npri, L.d_off, L.d_regs, S.d_src, S.d_ids, S.id0, d_out, lists, list_n);
 		e = hipGetLastError();
 	}
 	// the wavefront forms draw their pairs from the lists the first kernel left; a form no pair of the batch can need is not launched
 	if (e == hipSuccess && max_sum > PAIR_LANE_MAX) {
 		const int nb = n_pairs < 256 * 16 ? n_pairs : 256 * 16;
-		hipLaunchKernelGGL(k_pair_wave<PAIR_LDS_SMALL>, dim3(nb), dim3(64), 0, h->stream, *opt, P, h->l_pac, h->n_seqs, ctg, d_npri, d_off, d_regs, d_src, d_ids, id0, d_out, lists, list_n, (u64*)nullptr, 0);
+		hipLaunchKernelGGL(k_pair_wave<PAIR_LDS_SMALL>, dim3(nb), dim3(64), 0, h->stream, *opt, P, h->l_pac, h->n_seqs, ctg, S.d_npri, L.d_off, L.d_regs, S.d_src, S.d_ids, S.id0, d_out, lists, list_n, (u64*)nullptr, 0);
 		e = hipGetLastError();
 	}
 	if (e == hipSuccess && max_sum > PAIR_LDS_SMALL) {
 		const int nb = n_pairs < 256 * 4 ? n_pairs : 256 * 4;
-		hipLaunchKernelGGL(k_pair_wave<PAIR_LDS_BIG>, dim3(nb), dim3(64), 0, h->stream, *opt, P, h->l_pac, h->n_seqs, ctg, d_npri, d_off, d_regs, d_src, d_ids, id0, d_out, lists + n_pairs, list_n + 1, (u64*)nullptr, 0);
+		hipLaunchKernelGGL(k_pair_wave<PAIR_LDS_BIG>, dim3(nb), dim3(64), 0, h->stream, *opt, P, h->l_pac, h->n_seqs, ctg, S.d_npri, L.d_off, L.d_regs, S.d_src, S.d_ids, S.id0, d_out, lists + n_pairs, list_n + 1, (u64*)nullptr, 0);
 		e = hipGetLastError();
 	}
 	if (e == hipSuccess && n_hbm) {
-		hipLaunchKernelGGL(k_pair_wave<0>, dim3(n_hbm), dim3(64), 0, h->stream, *opt, P, h->l_pac, h->n_seqs, ctg, d_npri, d_off, d_regs, d_src, d_ids, id0, d_out, lists + (size_t)2 * n_pairs, list_n + 2,
+		hipLaunchKernelGGL(k_pair_wave<0>, dim3(n_hbm), dim3(64), 0, h->stream, *opt, P, h->l_pac, h->n_seqs, ctg, S.d_npri, L.d_off, L.d_regs, S.d_src, S.d_ids, S.id0, d_out, lists + (size_t)2 * n_pairs, list_n + 2,
 						   h->d_pair_scratch.as<u64>(), (int)max_sum);
 		e = hipGetLastError();
 	}
 	(void)hipEventRecord(h->ev[1], h->stream);
-	if (e == hipSuccess) e = hipMemcpyAsync(res, d_out, (size_t)n_pairs * sizeof(bwagpu_pair_t), hipMemcpyDeviceToHost, h->stream);
+	if (e == hipSuccess) e = hipMemcpyAsync(res.get(), d_out, (size_t)n_pairs * sizeof(bwagpu_pair_t), hipMemcpyDeviceToHost, h->stream);
 	if (e == hipSuccess) e = wait_stream(h);
-	if (e != hipSuccess) { bwagpu_free(res); HIPCHK(h, e); }
+	HIPCHK(h, e);
 	if (kernel_ms) (void)hipEventElapsedTime(kernel_ms, h->ev[0], h->ev[1]);
 	bool any = false;
 	for (int p = 0; p < n_pairs; ++p) {
-		if (res[p].flags & 2) { bwagpu_free(res); h->err = "internal: a pair outgrew the pairing kernel's working arrays"; return BWAGPU_EHIP; }
+		if (res[p].flags & 2) { h->err = "internal: a pair outgrew the pairing kernel's working arrays"; return BWAGPU_EHIP; }
 		any |= (res[p].flags & 1) != 0;
 	}
 	if (any) {      // pairs that met a distance outside the table: the same function with the host's erfc / log
-		std::vector<i64> off_, ids_; std::vector<bwagpu_alnreg_t> regs_;
-		if (!host_off) { off_.resize((size_t)n_pairs * 2); e = hipMemcpyAsync(off_.data(), d_off, (size_t)n_pairs * 2 * 8, hipMemcpyDeviceToHost, h->stream); host_off = off_.data(); }
-		if (e == hipSuccess && !host_regs) { regs_.resize((size_t)(tot ? tot : 1)); if (tot) e = hipMemcpyAsync(regs_.data(), d_regs, (size_t)tot * sizeof(bwagpu_alnreg_t), hipMemcpyDeviceToHost, h->stream); host_regs = regs_.data(); }
-		if (e == hipSuccess) e = wait_stream(h);
-		if (e != hipSuccess) { bwagpu_free(res); HIPCHK(h, e); }
+		ListsMirror M;
+		HIPCHK(h, M.fetch(h, L));
 		for (int p = 0; p < n_pairs; ++p) {
 			if (!(res[p].flags & 1)) continue;
-			const i64 o0 = host_off[2 * (size_t)p], o1 = host_off[2 * (size_t)p + 1];
-			res[p] = pair_host(*opt, pes, h->l_pac, h->h_ctg_off, host_regs + o0, host_src ? host_src + o0 : nullptr, host_npri[2 * (size_t)p], host_regs + o1, host_src ? host_src + o1 : nullptr,
-							   host_npri[2 * (size_t)p + 1], (int)(host_ids ? host_ids[p] : id0 + p));
+			const i64 o0 = L.h_off[2 * (size_t)p], o1 = L.h_off[2 * (size_t)p + 1];
+			res[p] = pair_host(*opt, pes, h->l_pac, h->h_ctg_off, L.h_regs + o0, S.h_src ? S.h_src + o0 : nullptr, S.h_npri[2 * (size_t)p], L.h_regs + o1, S.h_src ? S.h_src + o1 : nullptr,
+							   S.h_npri[2 * (size_t)p + 1], (int)(S.h_ids ? S.h_ids[p] : S.id0 + p));
 		}
 	}
-	*out = res;
+	*out = res.release();
 	return BWAGPU_OK;
 }
 
@@ -1928,28 +1980,29 @@ extern "C" int bwagpu_batch_pair(bwagpu_t *h, const bwagpu_opt_t *opt, const bwa
 	if (pri) *pri = nullptr;
 	if (n_pri_recs) *n_pri_recs = 0;
 	const int np = h->n_reads / 2;
-	bwagpu_primary_t *recs = nullptr; int64_t n_recs = 0; float ms_pri = 0.f, ms_pair = 0.f;
+	bwagpu_primary_t *recs_ = nullptr; int64_t n_recs = 0; float ms_pri = 0.f, ms_pair = 0.f;
 	std::vector<i32> npri((size_t)h->n_reads);
-	int rc = bwagpu_batch_primary(h, opt, id0, &recs, &n_recs, npri.data(), &ms_pri);
+	int rc = bwagpu_batch_primary(h, opt, id0, &recs_, &n_recs, npri.data(), &ms_pri);
 	if (rc != BWAGPU_OK) return rc;
+	ResultBlock<bwagpu_primary_t> recs(recs_);
 	const BusyGuard busy(h->ibuf->busy);
-	if (hipSetDevice(h->device) != hipSuccess) { bwagpu_free(recs); h->err = "hipSetDevice failed"; return BWAGPU_EHIP; }
-	bwagpu_pair_t *res = nullptr;
+	if (hipSetDevice(h->device) != hipSuccess) { h->err = "hipSetDevice failed"; return BWAGPU_EHIP; }
+	ResultBlock<bwagpu_pair_t> res;
 	if (n_recs == 0) {      // no region in the whole batch: every pair is without a candidate (and the packed arrays may not exist)
-		res = (bwagpu_pair_t*)result_alloc((size_t)(np ? np : 1) * sizeof(bwagpu_pair_t));
-		if (!res) { bwagpu_free(recs); return BWAGPU_ENOMEM; }
-		for (int p = 0; p < np; ++p) { res[p].score = res[p].sub = res[p].n_sub = 0; res[p].z[0] = res[p].z[1] = -1; res[p].flags = 0; res[p].n_cand = 0; }
-	} else {
-		i64 max_sum = 0;
-		for (int p = 0; p < np; ++p) { const i64 s = (i64)npri[2 * (size_t)p] + npri[2 * (size_t)p + 1]; if (s > max_sum) max_sum = s; }
-		rc = pair_run(h, opt, pes, np, n_recs, max_sum, h->d_pri_npri.as<i32>(), h->d_pack_off.as<i64>(), h->d_regs_packed.as<bwagpu_alnreg_t>(), h->d_pri_out.as<bwagpu_primary_t>(), nullptr, id0 >> 1,
-					  npri.data(), nullptr, nullptr, recs, nullptr, &res, &ms_pair);
-		if (rc != BWAGPU_OK) { bwagpu_free(recs); return rc; }
+		res = result_block<bwagpu_pair_t>((size_t)np);
+		if (!res) return BWAGPU_ENOMEM;
+		for (int p = 0; p < np; ++p) res[p] = pair_none();
+	} else {      // the marking's records and return values are still in its buffers
+		const PairSel S = { h->d_pri_npri.as<i32>(), npri.data(), h->d_pri_out.as<bwagpu_primary_t>(), recs.get(), nullptr, nullptr, id0 >> 1 };
+		bwagpu_pair_t *r = nullptr;
+		rc = pair_run(h, opt, pes, lists_of_batch(h, id0), S, &r, &ms_pair);
+		if (rc != BWAGPU_OK) return rc;
+		res.reset(r);
 	}
-	*pairs = res; *n_pairs = np;
+	*pairs = res.release(); *n_pairs = np;
 	if (n_pri) memcpy(n_pri, npri.data(), (size_t)h->n_reads * 4);
 	if (kernel_ms) *kernel_ms = ms_pri + ms_pair;
-	if (pri) { *pri = recs; if (n_pri_recs) *n_pri_recs = n_recs; } else bwagpu_free(recs);
+	if (pri) { *pri = recs.release(); if (n_pri_recs) *n_pri_recs = n_recs; }
 	return BWAGPU_OK;
 }
 
@@ -1958,52 +2011,39 @@ extern "C" int bwagpu_pair_flat(bwagpu_t *h, const bwagpu_opt_t *opt, const bwag
 {
 	if (!h || !opt || !pes || n_pairs < 0 || n_pairs > 0x3fffffff || !pairs || (n_pairs > 0 && (!counts || !n_pri || !ids))) return BWAGPU_EINVAL;
 	const size_t n_reads = (size_t)n_pairs * 2;
-	std::vector<i64> off(n_reads ? n_reads : 1);
-	i64 tot = 0, max_sum = 0;
-	for (size_t i = 0; i < n_reads; ++i) {
-		if (counts[i] < 0 || counts[i] > 0x3fffffff || n_pri[i] < 0 || n_pri[i] > counts[i] || (counts[i] > 0 && !regs)) return BWAGPU_EINVAL;
-		off[i] = tot;
-		for (int k = 0; k < n_pri[i]; ++k) if (regs[tot + k].rid < 0 || regs[tot + k].rid >= h->n_seqs) return BWAGPU_EINVAL;
-		tot += counts[i];
-		if (i & 1) { const i64 s = (i64)n_pri[i - 1] + n_pri[i]; if (s > max_sum) max_sum = s; }
-	}
+	for (size_t i = 0; i < n_reads; ++i) if (n_pri[i] < 0 || n_pri[i] > counts[i]) return BWAGPU_EINVAL;
+	FlatLists F; RegLists L;
+	if (!F.scan(h, n_reads, counts, regs, n_pri)) return BWAGPU_EINVAL;
 	const BusyGuard busy(h->ibuf->busy);
 	HIPCHK(h, hipSetDevice(h->device));
 	*pairs = nullptr;
-	if (n_pairs && (h->d_pair_npri.ensure(n_reads * 4) || h->d_pf_off.ensure(n_reads * 8) || h->d_pf_ids.ensure((size_t)n_pairs * 8) || h->d_pf_regs.ensure((size_t)(tot ? tot : 1) * sizeof(bwagpu_alnreg_t)))) {
-		h->err = "hipMalloc failed (pair)"; return BWAGPU_ENOMEM;
-	}
+	const int rc = F.upload(h, "pair", counts, regs, ids, (size_t)n_pairs, L);
+	if (rc != BWAGPU_OK) return rc;
 	if (n_pairs) {
-		HIPCHK(h, hipMemcpyAsync(h->d_pair_npri.p, n_pri, n_reads * 4, hipMemcpyHostToDevice, h->stream));
-		HIPCHK(h, hipMemcpyAsync(h->d_pf_off.p, off.data(), n_reads * 8, hipMemcpyHostToDevice, h->stream));
-		HIPCHK(h, hipMemcpyAsync(h->d_pf_ids.p, ids, (size_t)n_pairs * 8, hipMemcpyHostToDevice, h->stream));
-		if (tot) HIPCHK(h, hipMemcpyAsync(h->d_pf_regs.p, regs, (size_t)tot * sizeof(bwagpu_alnreg_t), hipMemcpyHostToDevice, h->stream));
-		HIPCHK(h, wait_stream(h));      // (`off` is a local array)
+		if (h->d_pair_npri.ensure(n_reads * 4)) { h->err = "hipMalloc failed (pair)"; return BWAGPU_ENOMEM; }
+		HIPCHK(h, hipMemcpyAsync(h->d_pair_npri.p, n_pri, n_reads * 4, hipMemcpyHostToDevice, h->stream));      // (the caller's array, in the stream ahead of the kernels)
 	}
-	return pair_run(h, opt, pes, n_pairs, tot, max_sum, h->d_pair_npri.as<i32>(), h->d_pf_off.as<i64>(), h->d_pf_regs.as<bwagpu_alnreg_t>(), nullptr, h->d_pf_ids.as<i64>(), 0,
-					n_pri, off.data(), regs, nullptr, ids, pairs, kernel_ms);
+	const PairSel S = { h->d_pair_npri.as<i32>(), n_pri, nullptr, nullptr, L.d_ids, ids, 0 };
+	L.d_ids = L.h_ids = nullptr;      // (the ids given are the pairs')
+	return pair_run(h, opt, pes, L, S, pairs, kernel_ms);
 }
 
 // ---- the merge of mate-rescue hits on the device (dev_rescue.h) -----------------------------------------------------------------------------------
 extern "C" void bwagpu_rescue_limits(int32_t out[4]) { out[0] = RESC_LANE_MAX; out[1] = RESC_LDS_MAX; out[2] = 0; out[3] = 0; }
 
-template <class T> static T *result_block(size_t n) { return (T*)result_alloc((n ? n : 1) * sizeof(T)); }
-
-// The kernels of both entry points on n_reads = 2 n_pairs reads (sequences d_seq / d_seqoff; lists d_cnt / d_off / d_regs, tot regions; read i has id d_ids[i], or
-// id0 + i): the task kernels, the replay, the packing, then -- for pri / pairs -- the marking and pairing kernels on the packed merged lists.
-static int rescue_run(bwagpu_t *h, const bwagpu_opt_t *opt, const bwagpu_pestat_t pes[4], int n_reads, i64 tot, const u8 *d_seq, const i64 *d_seqoff, const i32 *d_cnt, const i64 *d_off,
-					  const bwagpu_alnreg_t *d_regs, const i64 *d_ids, i64 id0, const i64 *host_ids, int32_t *counts, bwagpu_alnreg_t **regs, int32_t **src, int64_t *n_regs,
-					  bwagpu_rescue_t **rescue, bwagpu_primary_t **pri, int32_t *n_pri, bwagpu_pair_t **pairs, float *kernel_ms)
+// The kernels of both entry points on the L.n = 2 n_pairs reads of the lists L (sequences d_seq / d_seqoff): the task kernels, the replay, the packing, then -- for
+// pri / pairs -- the marking and pairing kernels on the packed merged lists.
+static int rescue_run(bwagpu_t *h, const bwagpu_opt_t *opt, const bwagpu_pestat_t pes[4], const RegLists &L, const u8 *d_seq, const i64 *d_seqoff, int32_t *counts, bwagpu_alnreg_t **regs,
+					  int32_t **src, int64_t *n_regs, bwagpu_rescue_t **rescue, bwagpu_primary_t **pri, int32_t *n_pri, bwagpu_pair_t **pairs, float *kernel_ms)
 {
-	const int np = n_reads / 2;
+	const int n_reads = L.n, np = n_reads / 2;
+	const i64 tot = L.tot;
 	*regs = nullptr; *src = nullptr; *n_regs = 0; *rescue = nullptr;
 	if (pri) *pri = nullptr;
 	if (pairs) *pairs = nullptr;
 	if (kernel_ms) *kernel_ms = 0.f;
-	bwagpu_alnreg_t *res_regs = nullptr; int32_t *res_src = nullptr; bwagpu_rescue_t *res_rec = nullptr; bwagpu_primary_t *res_pri = nullptr; bwagpu_pair_t *res_pair = nullptr;
-	struct Undo { bwagpu_alnreg_t *&a; int32_t *&b; bwagpu_rescue_t *&c; bwagpu_primary_t *&d; bwagpu_pair_t *&e; bool keep = false;
-		~Undo() { if (!keep) { if (a) bwagpu_free(a); if (b) bwagpu_free(b); if (c) bwagpu_free(c); if (d) bwagpu_free(d); if (e) bwagpu_free(e); } } } undo{res_regs, res_src, res_rec, res_pri, res_pair};
-	res_rec = result_block<bwagpu_rescue_t>((size_t)np);
+	ResultBlock<bwagpu_alnreg_t> res_regs; ResultBlock<int32_t> res_src; ResultBlock<bwagpu_primary_t> res_pri; ResultBlock<bwagpu_pair_t> res_pair;
+	ResultBlock<bwagpu_rescue_t> res_rec = result_block<bwagpu_rescue_t>((size_t)np);
 	if (!res_rec) return BWAGPU_ENOMEM;
 	std::vector<i32> npri((size_t)n_reads, 0);
 	i64 mtot = 0;
@@ -2014,8 +2054,7 @@ static int rescue_run(bwagpu_t *h, const bwagpu_opt_t *opt, const bwagpu_pestat_
 		res_regs = result_block<bwagpu_alnreg_t>(0); res_src = result_block<int32_t>(0);
 		if (!res_regs || !res_src) return BWAGPU_ENOMEM;
 	} else {
-		bwagpu_pes_t pes4[4];
-		for (int d = 0; d < 4; ++d) { pes4[d].low = pes[d].low; pes4[d].high = pes[d].high; pes4[d].failed = pes[d].failed; pes4[d].pad_ = 0; }
+		const bwagpu_pes_t pes4[4] = { pes_of(pes[0]), pes_of(pes[1]), pes_of(pes[2]), pes_of(pes[3]) };
 		DevBuf *D = h->d_rs;
 		if (D[bwagpu_s::RS_X].ensure((size_t)n_reads * 4) || D[bwagpu_s::RS_TOFF].ensure(((size_t)n_reads + 1) * 8) || D[bwagpu_s::RS_CTR].ensure(64) || D[bwagpu_s::RS_ACNT].ensure((size_t)n_reads * 4) ||
 			D[bwagpu_s::RS_POFF].ensure(((size_t)n_reads + 1) * 8) || D[bwagpu_s::RS_OUT].ensure((size_t)np * sizeof(bwagpu_rescue_t)) || D[bwagpu_s::RS_LISTS].ensure((size_t)np * 2 * 4)) {
@@ -2028,7 +2067,7 @@ static int rescue_run(bwagpu_t *h, const bwagpu_opt_t *opt, const bwagpu_pestat_
 		HIPCHK(h, hipMemsetAsync(D[bwagpu_s::RS_CTR].p, 0, 64, h->stream));
 		(void)hipEventRecord(h->ev[2], h->stream);
 		int nb = (np + BLOCK - 1) / BLOCK; if (nb > 8192) nb = 8192;
-		hipLaunchKernelGGL(k_rescue_count, dim3(nb), dim3(BLOCK), 0, h->stream, *opt, n_reads, d_cnt, d_off, d_regs, d_x, d_maxcap);
+		hipLaunchKernelGGL(k_rescue_count, dim3(nb), dim3(BLOCK), 0, h->stream, *opt, n_reads, L.d_cnt, L.d_off, L.d_regs, d_x, d_maxcap);
 		HIPCHK(h, hipGetLastError());
 		hipLaunchKernelGGL(k_rescue_scan, dim3(1), dim3(256), 0, h->stream, d_x, n_reads, d_toff);
 		HIPCHK(h, hipGetLastError());
@@ -2049,7 +2088,7 @@ static int rescue_run(bwagpu_t *h, const bwagpu_opt_t *opt, const bwagpu_pestat_
 		HIPCHK(h, hipMemsetAsync(d_tix, 0xff, (size_t)(extra ? extra : 1) * 4, h->stream));
 		unsigned long long nt = 0;
 		if (extra) {
-			const int rc = matesw_launch(h, opt, pes4, n_reads, d_seq, d_seqoff, d_cnt, d_off, d_regs, d_toff, d_tix, extra /* four per anchor: every task has its record */, &nt);
+			const int rc = matesw_launch(h, opt, pes4, L, d_seq, d_seqoff, d_toff, d_tix, extra /* four per anchor: every task has its record */, &nt);
 			if (rc != BWAGPU_OK) { (void)wait_stream(h); return rc; }
 		} else {      // (no anchor in the batch: the replay copies the lists and reads neither windows nor tasks)
 			if (h->d_msw_pes.ensure(4 * sizeof(bwagpu_pes_t)) || h->d_msw_out.ensure(sizeof(bwagpu_matesw_t))) { h->err = "hipMalloc failed (rescue)"; return BWAGPU_ENOMEM; }
@@ -2057,7 +2096,7 @@ static int rescue_run(bwagpu_t *h, const bwagpu_opt_t *opt, const bwagpu_pestat_
 			(void)hipEventRecord(h->ev[6], h->stream);
 		}
 		RescIn R;
-		R.seq = d_seq; R.seq_off = d_seqoff; R.cnt = d_cnt; R.off = d_off; R.regs = d_regs; R.pes = h->d_msw_pes.as<bwagpu_pes_t>();
+		R.seq = d_seq; R.seq_off = d_seqoff; R.cnt = L.d_cnt; R.off = L.d_off; R.regs = L.d_regs; R.pes = h->d_msw_pes.as<bwagpu_pes_t>();
 		R.toff = d_toff; R.tix = d_tix; R.mres = h->d_msw_out.as<bwagpu_matesw_t>(); R.n_tasks = (i64)nt;
 		R.arena = D[bwagpu_s::RS_ARENA].as<bwagpu_alnreg_t>(); R.asrc = D[bwagpu_s::RS_ASRC].as<i32>(); R.acnt = d_acnt; R.out = D[bwagpu_s::RS_OUT].as<bwagpu_rescue_t>();
 		i32 *lists = D[bwagpu_s::RS_LISTS].as<i32>();
@@ -2076,7 +2115,7 @@ static int rescue_run(bwagpu_t *h, const bwagpu_opt_t *opt, const bwagpu_pestat_
 		(void)hipEventRecord(h->ev[7], h->stream);
 		HIPCHK(h, hipMemcpyAsync(&mtot, d_poff + n_reads, 8, hipMemcpyDeviceToHost, h->stream));
 		HIPCHK(h, hipMemcpyAsync(counts, d_acnt, (size_t)n_reads * 4, hipMemcpyDeviceToHost, h->stream));
-		HIPCHK(h, hipMemcpyAsync(res_rec, R.out, (size_t)np * sizeof(bwagpu_rescue_t), hipMemcpyDeviceToHost, h->stream));
+		HIPCHK(h, hipMemcpyAsync(res_rec.get(), R.out, (size_t)np * sizeof(bwagpu_rescue_t), hipMemcpyDeviceToHost, h->stream));
 		HIPCHK(h, wait_stream(h));
 		if (mtot < 0 || mtot > tot + extra) { h->err = "internal: merged lists larger than their arena"; return BWAGPU_EHIP; }
 		for (int p = 0; p < np; ++p) if (res_rec[p].flags & 2) { h->err = "internal: a pair outgrew the rescue kernel's working lists"; return BWAGPU_EHIP; }
@@ -2089,8 +2128,8 @@ static int rescue_run(bwagpu_t *h, const bwagpu_opt_t *opt, const bwagpu_pestat_
 		HIPCHK(h, hipGetLastError());
 		(void)hipEventRecord(h->ev[1], h->stream);
 		if (mtot) {
-			HIPCHK(h, hipMemcpyAsync(res_regs, D[bwagpu_s::RS_REGS].p, (size_t)mtot * sizeof(bwagpu_alnreg_t), hipMemcpyDeviceToHost, h->stream));
-			HIPCHK(h, hipMemcpyAsync(res_src, D[bwagpu_s::RS_SRC].p, (size_t)mtot * 4, hipMemcpyDeviceToHost, h->stream));
+			HIPCHK(h, hipMemcpyAsync(res_regs.get(), D[bwagpu_s::RS_REGS].p, (size_t)mtot * sizeof(bwagpu_alnreg_t), hipMemcpyDeviceToHost, h->stream));
+			HIPCHK(h, hipMemcpyAsync(res_src.get(), D[bwagpu_s::RS_SRC].p, (size_t)mtot * 4, hipMemcpyDeviceToHost, h->stream));
 		}
 		HIPCHK(h, wait_stream(h));
 		{	// the kernels' segments between the call's host waits: count + scan, the task kernel, alignments + replay + scan, packing
@@ -2102,56 +2141,45 @@ static int rescue_run(bwagpu_t *h, const bwagpu_opt_t *opt, const bwagpu_pestat_
 			ms_resc = a + b + c + d;
 		}
 	}
-	// marking and pairing of the merged lists: the kernels of bwagpu_batch_primary / bwagpu_batch_pair, pointed at the packed merged lists
+	// marking and pairing of the merged lists: the kernels of bwagpu_batch_primary / bwagpu_batch_pair, pointed at the packed merged lists (k_rescue_pack's; on
+	// the host the call's own results; the offsets stay on the device) under the ids of L
+	RegLists M; M.n = n_reads; M.tot = mtot; M.d_ids = L.d_ids; M.id0 = L.id0; M.h_ids = L.h_ids; M.h_cnt = counts; M.h_regs = res_regs.get();
+	M.d_cnt = h->d_rs[bwagpu_s::RS_ACNT].as<i32>(); M.d_off = h->d_rs[bwagpu_s::RS_POFF].as<i64>(); M.d_regs = h->d_rs[bwagpu_s::RS_REGS].as<bwagpu_alnreg_t>();
+	for (int i = 0; i < n_reads; ++i) M.max_cnt = std::max(M.max_cnt, counts[i]);
 	if (pri || pairs) {
 		if (mtot == 0) { res_pri = result_block<bwagpu_primary_t>(0); if (!res_pri) return BWAGPU_ENOMEM; }
 		else {
-			i64 log_need = 0, k = 0; int max_cnt = 0;
-			for (int i = 0; i < n_reads; ++i) {
-				if (counts[i] > max_cnt) max_cnt = counts[i];
-				for (int j = 0; j < counts[i]; ++j, ++k) {
-					const bwagpu_alnreg_t &a = res_regs[k];
-					const i64 lq = (i64)a.qe - a.qb, lr = a.re - a.rb, sn = (i64)a.sub_n + 2 * (i64)counts[i] + 1;
-					if (lq > log_need) log_need = lq;
-					if (lr > log_need) log_need = lr;
-					if (a.seedcov > log_need) log_need = a.seedcov;
-					if (sn > log_need) log_need = sn;
-				}
-			}
-			const int rc = primary_run(h, opt, n_reads, mtot, max_cnt, log_need, h->d_rs[bwagpu_s::RS_ACNT].as<i32>(), h->d_rs[bwagpu_s::RS_POFF].as<i64>(), h->d_rs[bwagpu_s::RS_REGS].as<bwagpu_alnreg_t>(),
-									   d_ids, id0, counts, res_regs, &res_pri, npri.data(), &ms_pri);
+			bwagpu_primary_t *r = nullptr;
+			const int rc = primary_run(h, opt, M, pri_log_need(counts, res_regs.get(), n_reads), &r, npri.data(), &ms_pri);
 			if (rc != BWAGPU_OK) return rc;
+			res_pri.reset(r);
 		}
 	}
 	if (pairs) {
 		if (mtot == 0) {
 			res_pair = result_block<bwagpu_pair_t>((size_t)np);
 			if (!res_pair) return BWAGPU_ENOMEM;
-			for (int p = 0; p < np; ++p) { res_pair[p].score = res_pair[p].sub = res_pair[p].n_sub = 0; res_pair[p].z[0] = res_pair[p].z[1] = -1; res_pair[p].flags = 0; res_pair[p].n_cand = 0; }
+			for (int p = 0; p < np; ++p) res_pair[p] = pair_none();
 		} else {
-			i64 max_sum = 0;
-			for (int p = 0; p < np; ++p) { const i64 s2 = (i64)npri[2 * (size_t)p] + npri[2 * (size_t)p + 1]; if (s2 > max_sum) max_sum = s2; }
+			PairSel S = { h->d_pri_npri.as<i32>(), npri.data(), h->d_pri_out.as<bwagpu_primary_t>(), res_pri.get(), nullptr, nullptr, L.id0 >> 1 };
 			std::vector<i64> pid;
-			const i64 *d_pid = nullptr;
-			if (host_ids) {      // a pair's id is its first read's id >> 1 (bwamem_pair.c:349-354)
+			if (L.h_ids) {      // a pair's id is its first read's id >> 1 (bwamem_pair.c:349-354)
 				pid.resize((size_t)np);
-				for (int p = 0; p < np; ++p) pid[(size_t)p] = host_ids[2 * (size_t)p] >> 1;
+				for (int p = 0; p < np; ++p) pid[(size_t)p] = L.h_ids[2 * (size_t)p] >> 1;
 				if (h->d_rs[bwagpu_s::RS_PAIRIDS].ensure((size_t)np * 8)) { h->err = "hipMalloc failed (rescue)"; return BWAGPU_ENOMEM; }
 				HIPCHK(h, hipMemcpyAsync(h->d_rs[bwagpu_s::RS_PAIRIDS].p, pid.data(), (size_t)np * 8, hipMemcpyHostToDevice, h->stream));
 				HIPCHK(h, wait_stream(h));
-				d_pid = h->d_rs[bwagpu_s::RS_PAIRIDS].as<i64>();
+				S.d_ids = h->d_rs[bwagpu_s::RS_PAIRIDS].as<i64>(); S.h_ids = pid.data();
 			}
-			std::vector<i64> poff((size_t)n_reads);
-			{ i64 run = 0; for (int i = 0; i < n_reads; ++i) { poff[(size_t)i] = run; run += counts[i]; } }
-			const int rc = pair_run(h, opt, pes, np, mtot, max_sum, h->d_pri_npri.as<i32>(), h->d_rs[bwagpu_s::RS_POFF].as<i64>(), h->d_rs[bwagpu_s::RS_REGS].as<bwagpu_alnreg_t>(), h->d_pri_out.as<bwagpu_primary_t>(),
-									d_pid, id0 >> 1, npri.data(), poff.data(), res_regs, res_pri, host_ids ? pid.data() : nullptr, &res_pair, &ms_pair);
+			bwagpu_pair_t *r = nullptr;
+			const int rc = pair_run(h, opt, pes, M, S, &r, &ms_pair);
 			if (rc != BWAGPU_OK) return rc;
+			res_pair.reset(r);
 		}
 	}
-	undo.keep = true;
-	*regs = res_regs; *src = res_src; *n_regs = mtot; *rescue = res_rec;
-	if (pri) *pri = res_pri; else if (res_pri) bwagpu_free(res_pri);
-	if (pairs) *pairs = res_pair;
+	*regs = res_regs.release(); *src = res_src.release(); *n_regs = mtot; *rescue = res_rec.release();
+	if (pri) *pri = res_pri.release();
+	if (pairs) *pairs = res_pair.release();
 	if (n_pri) memcpy(n_pri, npri.data(), (size_t)n_reads * 4);
 	if (kernel_ms) *kernel_ms = ms_resc + ms_pri + ms_pair;
 	return BWAGPU_OK;
@@ -2164,9 +2192,7 @@ extern "C" int bwagpu_batch_rescue(bwagpu_t *h, const bwagpu_opt_t *opt, const b
 	if ((h->n_reads & 1) || (id0 & 1) || opt->e_del <= 0 || opt->e_ins <= 0 || (pairs && (opt->flag & 0x800 /* MEM_F_PRIMARY5 */))) return BWAGPU_EINVAL;
 	const BusyGuard busy(h->ibuf->busy);
 	HIPCHK(h, hipSetDevice(h->device));
-	const i64 tot = h->packed_tot < 0 ? 0 : h->packed_tot;
-	return rescue_run(h, opt, pes, h->n_reads, tot, h->d_seq.as<u8>(), h->d_off.as<i64>(), h->d_reg_n.as<i32>(), h->d_pack_off.as<i64>(), h->d_regs_packed.as<bwagpu_alnreg_t>(), nullptr, id0, nullptr,
-					  counts, regs, src, n_regs, rescue, pri, n_pri, pairs, kernel_ms);
+	return rescue_run(h, opt, pes, lists_of_batch(h, id0), h->d_seq.as<u8>(), h->d_off.as<i64>(), counts, regs, src, n_regs, rescue, pri, n_pri, pairs, kernel_ms);
 }
 
 extern "C" int bwagpu_rescue_flat(bwagpu_t *h, const bwagpu_opt_t *opt, const bwagpu_pestat_t pes[4], int n_pairs, const uint8_t *seqs, const int64_t *off, const int32_t *counts_in,
@@ -2177,34 +2203,21 @@ extern "C" int bwagpu_rescue_flat(bwagpu_t *h, const bwagpu_opt_t *opt, const bw
 	if (n_pairs > 0 && (!seqs || !off || !counts_in || !counts || ((pri || pairs) && !ids))) return BWAGPU_EINVAL;
 	if (opt->e_del <= 0 || opt->e_ins <= 0 || (pairs && (opt->flag & 0x800 /* MEM_F_PRIMARY5 */))) return BWAGPU_EINVAL;
 	const int n_reads = 2 * n_pairs;
-	std::vector<i64> roff((size_t)n_reads + 1, 0);
-	i64 tot = 0;
-	for (int i = 0; i < n_reads; ++i) {
-		if (counts_in[i] < 0 || counts_in[i] > 0x3fffffff || off[i + 1] < off[i] || off[i] < 0 || off[i + 1] - off[i] > 0x3fffffff || (counts_in[i] > 0 && !regs_in)) return BWAGPU_EINVAL;
-		roff[(size_t)i] = tot;
-		for (int k = 0; k < counts_in[i]; ++k) if (regs_in[tot + k].rid < 0 || regs_in[tot + k].rid >= h->n_seqs) return BWAGPU_EINVAL;
-		tot += counts_in[i];
-	}
+	for (int i = 0; i < n_reads; ++i) if (off[i + 1] < off[i] || off[i] < 0 || off[i + 1] - off[i] > 0x3fffffff) return BWAGPU_EINVAL;
+	FlatLists F; RegLists L;
+	if (!F.scan(h, (size_t)n_reads, counts_in, regs_in, counts_in)) return BWAGPU_EINVAL;
 	const i64 n_bases = n_reads ? off[n_reads] : 0;
 	for (i64 k = n_reads ? off[0] : 0; k < n_bases; ++k) if (seqs[k] > 4) return BWAGPU_EINVAL;
 	const BusyGuard busy(h->ibuf->busy);
 	HIPCHK(h, hipSetDevice(h->device));
 	DevBuf *D = h->d_rs;
-	if (n_reads) {
-		if (D[bwagpu_s::RS_SEQ].ensure((size_t)(n_bases ? n_bases : 1)) || D[bwagpu_s::RS_SEQOFF].ensure(((size_t)n_reads + 1) * 8) || D[bwagpu_s::RS_CNT_IN].ensure((size_t)n_reads * 4) ||
-			D[bwagpu_s::RS_OFF_IN].ensure(((size_t)n_reads + 1) * 8) || D[bwagpu_s::RS_REGS_IN].ensure((size_t)(tot ? tot : 1) * sizeof(bwagpu_alnreg_t)) || (ids && D[bwagpu_s::RS_IDS].ensure((size_t)n_reads * 8))) {
-			h->err = "hipMalloc failed (rescue)"; return BWAGPU_ENOMEM;
-		}
+	if (n_reads) {      // the sequences and their offsets (the caller's arrays, in the stream ahead of the lists: upload() waits)
+		if (D[bwagpu_s::RS_SEQ].ensure((size_t)(n_bases ? n_bases : 1)) || D[bwagpu_s::RS_SEQOFF].ensure(((size_t)n_reads + 1) * 8)) { h->err = "hipMalloc failed (rescue)"; return BWAGPU_ENOMEM; }
 		if (n_bases) HIPCHK(h, hipMemcpyAsync(D[bwagpu_s::RS_SEQ].p, seqs, (size_t)n_bases, hipMemcpyHostToDevice, h->stream));
 		HIPCHK(h, hipMemcpyAsync(D[bwagpu_s::RS_SEQOFF].p, off, ((size_t)n_reads + 1) * 8, hipMemcpyHostToDevice, h->stream));
-		HIPCHK(h, hipMemcpyAsync(D[bwagpu_s::RS_CNT_IN].p, counts_in, (size_t)n_reads * 4, hipMemcpyHostToDevice, h->stream));
-		HIPCHK(h, hipMemcpyAsync(D[bwagpu_s::RS_OFF_IN].p, roff.data(), ((size_t)n_reads + 1) * 8, hipMemcpyHostToDevice, h->stream));
-		if (tot) HIPCHK(h, hipMemcpyAsync(D[bwagpu_s::RS_REGS_IN].p, regs_in, (size_t)tot * sizeof(bwagpu_alnreg_t), hipMemcpyHostToDevice, h->stream));
-		if (ids) HIPCHK(h, hipMemcpyAsync(D[bwagpu_s::RS_IDS].p, ids, (size_t)n_reads * 8, hipMemcpyHostToDevice, h->stream));
-		HIPCHK(h, wait_stream(h));      // (`roff` is a local array)
 	}
-	return rescue_run(h, opt, pes, n_reads, tot, D[bwagpu_s::RS_SEQ].as<u8>(), D[bwagpu_s::RS_SEQOFF].as<i64>(), D[bwagpu_s::RS_CNT_IN].as<i32>(), D[bwagpu_s::RS_OFF_IN].as<i64>(),
-					  D[bwagpu_s::RS_REGS_IN].as<bwagpu_alnreg_t>(), ids ? D[bwagpu_s::RS_IDS].as<i64>() : nullptr, 0, ids, counts, regs, src, n_regs, rescue, pri, n_pri, pairs, kernel_ms);
+	const int rc = F.upload(h, "rescue", counts_in, regs_in, ids, (size_t)n_reads, L);
+	return rc != BWAGPU_OK ? rc : rescue_run(h, opt, pes, L, D[bwagpu_s::RS_SEQ].as<u8>(), D[bwagpu_s::RS_SEQOFF].as<i64>(), counts, regs, src, n_regs, rescue, pri, n_pri, pairs, kernel_ms);
 }
 
 // ---- insert-size statistics on the device (dev_pestat.h) ------------------------------------------------------------------------------------------
@@ -2223,16 +2236,16 @@ static int pestat_max_ins_ok(bwagpu_t *h, const bwagpu_opt_t *opt)
 	h->err = "max_ins " + std::to_string(opt->max_ins) + " is beyond the device histogram's " + std::to_string(PST_MAX_INS) + " (bwagpu_pestat_limits): mem_pestat of this batch is the host's";
 	return 0;
 }
-// k_pestat_collect over n_reads / 2 pairs into the handle's histogram (cleared first), in the stream; 1 <= max_ins <= PST_MAX_INS
-static int pestat_collect(bwagpu_t *h, const bwagpu_opt_t *opt, int n_reads, const i32 *d_cnt, const i64 *d_off, const bwagpu_alnreg_t *d_regs)
+// k_pestat_collect over the L.n / 2 pairs of the lists L into the handle's histogram (cleared first), in the stream; 1 <= max_ins <= PST_MAX_INS
+static int pestat_collect(bwagpu_t *h, const bwagpu_opt_t *opt, const RegLists &L)
 {
 	const size_t bytes = (size_t)pestat_bins(opt->max_ins) * 4;
 	if (h->d_pst_hist.ensure(bytes)) { h->err = "hipMalloc failed (pestat)"; return BWAGPU_ENOMEM; }
 	HIPCHK(h, hipMemsetAsync(h->d_pst_hist.p, 0, bytes, h->stream));
-	const int n_pairs = n_reads >> 1;
+	const int n_pairs = L.n >> 1;
 	if (n_pairs == 0) return BWAGPU_OK;
 	int nb = (n_pairs + PST_BLOCK - 1) / PST_BLOCK; if (nb > 256 * 8) nb = 256 * 8;
-	hipLaunchKernelGGL(k_pestat_collect, dim3(nb), dim3(PST_BLOCK), 0, h->stream, opt->mask_level, opt->min_seed_len * opt->a, opt->max_ins, h->l_pac, n_pairs, d_cnt, d_off, d_regs, h->d_pst_hist.as<unsigned int>());
+	hipLaunchKernelGGL(k_pestat_collect, dim3(nb), dim3(PST_BLOCK), 0, h->stream, opt->mask_level, opt->min_seed_len * opt->a, opt->max_ins, h->l_pac, n_pairs, L.d_cnt, L.d_off, L.d_regs, h->d_pst_hist.as<unsigned int>());
 	HIPCHK(h, hipGetLastError());
 	return BWAGPU_OK;
 }
@@ -2258,10 +2271,10 @@ static int pestat_fetch(bwagpu_t *h, bwagpu_pestat_t pes[4], bwagpu_pestat_info_
 	return BWAGPU_OK;
 }
 // both kernels as one timed segment, then the fetch
-static int pestat_run(bwagpu_t *h, const bwagpu_opt_t *opt, int n_reads, const i32 *d_cnt, const i64 *d_off, const bwagpu_alnreg_t *d_regs, bwagpu_pestat_t pes[4], bwagpu_pestat_info_t *info, float *kernel_ms)
+static int pestat_run(bwagpu_t *h, const bwagpu_opt_t *opt, const RegLists &L, bwagpu_pestat_t pes[4], bwagpu_pestat_info_t *info, float *kernel_ms)
 {
 	(void)hipEventRecord(h->ev[0], h->stream);
-	int rc = pestat_collect(h, opt, n_reads, d_cnt, d_off, d_regs);
+	int rc = pestat_collect(h, opt, L);
 	if (rc == BWAGPU_OK) rc = pestat_finish(h, opt);
 	(void)hipEventRecord(h->ev[1], h->stream);
 	return rc == BWAGPU_OK ? pestat_fetch(h, pes, info, kernel_ms) : rc;
@@ -2275,30 +2288,22 @@ extern "C" int bwagpu_batch_pestat(bwagpu_t *h, const bwagpu_opt_t *opt, bwagpu_
 	HIPCHK(h, hipSetDevice(h->device));
 	if (kernel_ms) *kernel_ms = 0.f;
 	if (h->packed_tot <= 0 || h->n_reads < 2 || opt->max_ins <= 0) { pestat_none(pes, info); return BWAGPU_OK; }      // (without a region the packed arrays may not exist)
-	return pestat_run(h, opt, h->n_reads, h->d_reg_n.as<i32>(), h->d_pack_off.as<i64>(), h->d_regs_packed.as<bwagpu_alnreg_t>(), pes, info, kernel_ms);
+	return pestat_run(h, opt, lists_of_batch(h, 0), pes, info, kernel_ms);
 }
 
 extern "C" int bwagpu_pestat_flat(bwagpu_t *h, const bwagpu_opt_t *opt, int n_reads, const int32_t *counts, const bwagpu_alnreg_t *regs,
 								  bwagpu_pestat_t pes[4], bwagpu_pestat_info_t *info, float *kernel_ms)
 {
 	if (!h || !opt || !pes || n_reads < 0 || (n_reads > 0 && !counts)) return BWAGPU_EINVAL;
-	i64 tot = 0;
-	for (int i = 0; i < n_reads; ++i) { if (counts[i] < 0 || counts[i] > 0x3fffffff) return BWAGPU_EINVAL; tot += counts[i]; }
-	if (tot > 0 && !regs) return BWAGPU_EINVAL;
+	FlatLists F; RegLists L;
+	if (!F.scan(h, (size_t)n_reads, counts, regs, nullptr)) return BWAGPU_EINVAL;
 	if (!pestat_max_ins_ok(h, opt)) return BWAGPU_EINVAL;
 	const BusyGuard busy(h->ibuf->busy);
 	HIPCHK(h, hipSetDevice(h->device));
 	if (kernel_ms) *kernel_ms = 0.f;
-	if (tot == 0 || n_reads < 2 || opt->max_ins <= 0) { pestat_none(pes, info); return BWAGPU_OK; }
-	std::vector<i64> off((size_t)n_reads);
-	i64 k = 0;
-	for (int i = 0; i < n_reads; ++i) { off[i] = k; k += counts[i]; }
-	if (h->d_pf_cnt.ensure((size_t)n_reads * 4) || h->d_pf_off.ensure((size_t)n_reads * 8) || h->d_pf_regs.ensure((size_t)tot * sizeof(bwagpu_alnreg_t))) { h->err = "hipMalloc failed (pestat)"; return BWAGPU_ENOMEM; }
-	HIPCHK(h, hipMemcpyAsync(h->d_pf_cnt.p, counts, (size_t)n_reads * 4, hipMemcpyHostToDevice, h->stream));
-	HIPCHK(h, hipMemcpyAsync(h->d_pf_off.p, off.data(), (size_t)n_reads * 8, hipMemcpyHostToDevice, h->stream));
-	HIPCHK(h, hipMemcpyAsync(h->d_pf_regs.p, regs, (size_t)tot * sizeof(bwagpu_alnreg_t), hipMemcpyHostToDevice, h->stream));
-	HIPCHK(h, wait_stream(h));      // (`off` is a local array)
-	return pestat_run(h, opt, n_reads, h->d_pf_cnt.as<i32>(), h->d_pf_off.as<i64>(), h->d_pf_regs.as<bwagpu_alnreg_t>(), pes, info, kernel_ms);
+	if (F.tot == 0 || n_reads < 2 || opt->max_ins <= 0) { pestat_none(pes, info); return BWAGPU_OK; }
+	const int rc = F.upload(h, "pestat", counts, regs, nullptr, 0, L);
+	return rc != BWAGPU_OK ? rc : pestat_run(h, opt, L, pes, info, kernel_ms);
 }
 
 extern "C" int bwagpu_batch_pestat_hist(bwagpu_t *h, const bwagpu_opt_t *opt, uint32_t **hist, int64_t *n_bins, float *kernel_ms)
@@ -2309,21 +2314,20 @@ extern "C" int bwagpu_batch_pestat_hist(bwagpu_t *h, const bwagpu_opt_t *opt, ui
 	HIPCHK(h, hipSetDevice(h->device));
 	if (kernel_ms) *kernel_ms = 0.f;
 	const i64 nbins = pestat_bins(opt->max_ins);
-	uint32_t *res = (uint32_t*)result_alloc((size_t)(nbins ? nbins : 1) * 4);
+	ResultBlock<uint32_t> res = result_block<uint32_t>((size_t)nbins);
 	if (!res) return BWAGPU_ENOMEM;
 	*hist = nullptr; *n_bins = 0;
-	if (h->packed_tot <= 0 || h->n_reads < 2 || opt->max_ins <= 0) memset(res, 0, (size_t)(nbins ? nbins : 1) * 4);      // nothing to count
+	if (h->packed_tot <= 0 || h->n_reads < 2 || opt->max_ins <= 0) memset(res.get(), 0, (size_t)(nbins ? nbins : 1) * 4);      // nothing to count
 	else {
 		(void)hipEventRecord(h->ev[0], h->stream);
-		const int rc = pestat_collect(h, opt, h->n_reads, h->d_reg_n.as<i32>(), h->d_pack_off.as<i64>(), h->d_regs_packed.as<bwagpu_alnreg_t>());
+		const int rc = pestat_collect(h, opt, lists_of_batch(h, 0));
 		(void)hipEventRecord(h->ev[1], h->stream);
-		if (rc != BWAGPU_OK) { bwagpu_free(res); return rc; }
-		hipError_t e = hipMemcpyAsync(res, h->d_pst_hist.p, (size_t)nbins * 4, hipMemcpyDeviceToHost, h->stream);
-		if (e == hipSuccess) e = wait_stream(h);
-		if (e != hipSuccess) { bwagpu_free(res); HIPCHK(h, e); }
+		if (rc != BWAGPU_OK) return rc;
+		HIPCHK(h, hipMemcpyAsync(res.get(), h->d_pst_hist.p, (size_t)nbins * 4, hipMemcpyDeviceToHost, h->stream));
+		HIPCHK(h, wait_stream(h));
 		if (kernel_ms) (void)hipEventElapsedTime(kernel_ms, h->ev[0], h->ev[1]);
 	}
-	*hist = res; *n_bins = nbins;
+	*hist = res.release(); *n_bins = nbins;
 	return BWAGPU_OK;
 }
 

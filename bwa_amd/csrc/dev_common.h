@@ -231,3 +231,20 @@ struct Batch {
 	i32 *order;                // [n_reads] permutation of read indices
 	u32 *bin_cnt;              // [2 * ORDER_BINS]: counts, then fill cursors / starts
 };
+
+// The hand-over of the lane-per-item kernels to their wavefront forms: every lane whose `tier` is t in 0 .. NT - 1 appends `idx` to list t of `lists` (n entries
+// each, lengths in list_n[]) -- a ballot per tier, one atomicAdd per wavefront and list, the lane's place by the population count below it.  Lanes with nothing
+// to hand over pass a negative tier.  Wave-uniform control flow only: every lane of the wavefront has to arrive.
+template <int NT>
+DEVFN void tier_push(int tier, int idx, int n, i32 *lists, unsigned int *list_n, int lane)
+{
+	for (int t = 0; t < NT; ++t) {
+		const unsigned long long m = __ballot(tier == t);
+		if (m == 0) continue;
+		const int leader = __ffsll(m) - 1;
+		int base = 0;
+		if (lane == leader) base = (int)atomicAdd(&list_n[t], (unsigned int)__popcll(m));
+		base = __shfl(base, leader);
+		if (tier == t) lists[(size_t)t * n + base + __popcll(m & ((1ull << lane) - 1))] = idx;
+	}
+}

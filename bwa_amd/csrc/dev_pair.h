@@ -170,7 +170,7 @@ DEVFN bwagpu_pair_t pair_read(const PairView &V, const bwagpu_opt_t &opt, const 
 	return rec;
 }
 
-DEVFN bwagpu_pair_t pair_none() { bwagpu_pair_t r; r.score = r.sub = r.n_sub = 0; r.z[0] = r.z[1] = -1; r.flags = 0; r.n_cand = 0; return r; }
+__host__ __device__ inline bwagpu_pair_t pair_none() { bwagpu_pair_t r; r.score = r.sub = r.n_sub = 0; r.z[0] = r.z[1] = -1; r.flags = 0; r.n_cand = 0; return r; }
 
 // One lane per pair: reads 2p and 2p + 1 (lists at off[] of regs, n_pri[] places each; src: the marking records at the same offsets, or null).  Pair p has id
 // ids[p], or id0 + p, truncated to int (:208).  Pairs with more than PAIR_LANE_MAX hits are handed to the wavefront forms: list t of `lists` (n_pairs entries
@@ -187,15 +187,7 @@ __global__ void __launch_bounds__(PAIR_LANE_BLOCK) k_pair_lane(bwagpu_opt_t opt,
 		const bool live = n0 > 0 && n1 > 0;
 		const i64 n = (i64)n0 + n1;
 		const int tier = !live || n <= PAIR_LANE_MAX ? -1 : n <= PAIR_LDS_SMALL ? 0 : n <= PAIR_LDS_BIG ? 1 : 2;
-		for (int t = 0; t < 3; ++t) {
-			const unsigned long long m = __ballot(tier == t);
-			if (m == 0) continue;
-			const int leader = __ffsll(m) - 1;
-			int base = 0;
-			if (lane == leader) base = (int)atomicAdd(&list_n[t], (unsigned int)__popcll(m));
-			base = __shfl(base, leader);
-			if (tier == t) lists[(size_t)t * n_pairs + base + __popcll(m & ((1ull << lane) - 1))] = p;
-		}
+		tier_push<3>(tier, p, n_pairs, lists, list_n, lane);
 		if (p < n_pairs && !live) out[p] = pair_none();
 		if (live && tier < 0) {
 			const i64 o0 = off[2 * (size_t)p], o1 = off[2 * (size_t)p + 1];

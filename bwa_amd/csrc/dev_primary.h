@@ -230,15 +230,7 @@ __global__ void __launch_bounds__(PRI_LANE_BLOCK) k_primary_lane(bwagpu_opt_t op
 		const int r = (int)(r0 + threadIdx.x);
 		const int n = r < n_reads ? cnt[r] : 0;
 		const int tier = n <= PRI_LANE_MAX ? -1 : n <= PRI_LDS_SMALL ? 0 : n <= PRI_LDS_BIG ? 1 : 2;
-		for (int t = 0; t < 3; ++t) {
-			const unsigned long long m = __ballot(tier == t);
-			if (m == 0) continue;
-			const int leader = __ffsll(m) - 1;
-			int base = 0;
-			if (lane == leader) base = (int)atomicAdd(&list_n[t], (unsigned int)__popcll(m));
-			base = __shfl(base, leader);
-			if (tier == t) lists[(size_t)t * n_reads + base + __popcll(m & ((1ull << lane) - 1))] = r;
-		}
+		tier_push<3>(tier, r, n_reads, lists, list_n, lane);
 		if (r < n_reads && n <= 0) n_pri[r] = 0;
 		if (n >= 1 && tier < 0) n_pri[r] = pri_read<1>(V, opt, lg, regs + off[r], n, ids ? ids[r] : id0 + r, out + off[r], 0);
 	}

@@ -461,15 +461,7 @@ __global__ void __launch_bounds__(RESC_LANE_BLOCK) k_rescue_lane(DevIndex ix, bw
 			if (rc == RESC_HANDOVER) tier = 0;
 			else if (rc != RESC_DONE) resc_give_up<1>(R, p, rc, 0);
 		}
-		for (int t = 0; t < 2; ++t) {
-			const unsigned long long m = __ballot(tier == t);
-			if (m == 0) continue;
-			const int leader = __ffsll(m) - 1;
-			int base = 0;
-			if (lane == leader) base = (int)atomicAdd(&list_n[t], (unsigned int)__popcll(m));
-			base = __shfl(base, leader);
-			if (tier == t) lists[(size_t)t * n_pairs + base + __popcll(m & ((1ull << lane) - 1))] = p;
-		}
+		tier_push<2>(tier, p, n_pairs, lists, list_n, lane);
 	}
 }
 

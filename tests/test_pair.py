@@ -281,6 +281,22 @@ def run_fuzz(dev, ref, seed, thin):
     for form in range(4):
         assert seen[form] == set(FAMILIES), (form, seen[form])
     assert {"0", "1", ">64"} <= ncand and any_extra
+    run_mixed(dev, ref, seed)
+
+
+def run_mixed(dev, ref, seed):
+    """128 consecutive pairs whose sizes run through every form of the kernels (and the pairs with an empty end) within each wavefront, a cycle of seven, so the
+    places shift from one wavefront to the next: the lanes' hand-over with all three lists live in one ballot and no list taking a whole wavefront."""
+    rng = np.random.default_rng(seed + 1000)
+    meta = dev.index_meta()
+    opt = tp.ref_opt()
+    cyc = ((2, 2), (3, 2), (0, 3), (LDS_SMALL // 2, LDS_SMALL // 2 + 1), (1, 1), (LDS_BIG // 2, LDS_BIG // 2 + 1), (LDS_SMALL // 2, LDS_SMALL // 2))
+    assert {form_of(a, b) for a, b in cyc} == {0, 1, 2, 3}
+    cells = [cyc[i % len(cyc)] + (FAMILIES[i % len(FAMILIES)], "four") for i in range(128)]
+    (v, pes, group, counts, n_pri, regs, ids), = build_call(rng, meta, cells)
+    want = ref_pairs(ref, opt, pes, meta["ctg_offset"], counts, n_pri, regs, ids)
+    got, _ = dev.pair_flat(opt, pes, counts, n_pri, regs, ids)
+    assert_pairs_equal(got, want, f"128 pairs of mixed forms, seed {seed}")
 
 
 def run_tab_cap(dev, ref, seed):

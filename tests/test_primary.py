@@ -179,6 +179,21 @@ def run_fuzz(dev, seed, thin):
     for form in range(4):
         assert seen_f[form] == set(FAMILIES) and seen_m[form] == set(ALT_MODES), (form, seen_f[form], seen_m[form])
     assert seen_np == {"zero", "all", "between"}      # both rounds of bwamem.c:564-577 ran, and neither
+    run_mixed(dev, seed)
+
+
+def run_mixed(dev, seed):
+    """128 consecutive reads whose sizes run through every form of the kernels within each wavefront (a cycle of seven, so the places shift from one wavefront
+    to the next): the lanes' hand-over with all three lists live in one ballot and no list taking a whole wavefront."""
+    rng = np.random.default_rng(seed + 1000)
+    opt = ref_opt()
+    cyc = (LANE_MAX, LDS_SMALL + 1, 0, LANE_MAX + 1, LDS_BIG + 1, 1, LDS_SMALL)
+    counts = np.array([cyc[i % len(cyc)] for i in range(128)], dtype=np.int32)
+    regs = np.concatenate([make_list(rng, int(n), FAMILIES[i % len(FAMILIES)], ALT_MODES[i % len(ALT_MODES)], i % 4 == 0) for i, n in enumerate(counts)])
+    ids = rng.integers(0, 1 << 40, counts.shape[0]).astype(np.int64)
+    want, want_np = ref_primary(opt, counts, regs, ids)
+    got, n_pri, _ = dev.primary_flat(opt, counts, regs, ids)
+    assert_records_equal(got, n_pri, want, want_np, counts, f"128 reads of mixed forms, seed {seed}")
 
 
 # ---- real batches ---------------------------------------------------------------------------------------------------------------------------------------

@@ -267,6 +267,30 @@ def run_fuzz(dev, ref, g, seed, thin):
         assert seen.get(form) == set(FAMILIES), (form, set(FAMILIES) - seen.get(form, set()))
     assert inline["removal"] > 0, "no pair of the removal family needed an alignment nobody precomputed"
     assert all(v == 0 for f, v in inline.items() if f != "removal"), inline
+    run_mixed(dev, ref, g, seed)
+
+
+def run_mixed(dev, ref, g, seed):
+    """128 consecutive pairs whose capacities run through every form of the kernels within each wavefront, a cycle of seven, so the places shift from one
+    wavefront to the next: the lanes' hand-over with both lists live in one ballot and no list taking a whole wavefront.  Mostly pairs that need no alignment
+    (a consistent hit is there already, or no anchor): the merge and the hand-over are what is looked at."""
+    rng = np.random.default_rng(seed + 1000)
+    meta = dev.index_meta()
+    opt = tp.ref_opt()
+    opt.max_matesw = 3
+    pes = fuzz_pes("one")
+    fills = (0, LANE_MAX - 3, LDS_MAX - 3, 1, LANE_MAX - 4, LDS_MAX - 4, LANE_MAX)      # capacities (one anchor: these + 4, at least 13): lane, LDS, HBM, lane, lane, LDS, LDS
+    reads, lists = [], []
+    for i in range(128):
+        r, l = make_case(rng, g, meta, opt, pes, "rescued" if i % 16 == 5 else ("consistent", "empty")[i % 2], fills[i % len(fills)])
+        reads += r; lists += l
+    seqs, off = testdata.ragged(reads)
+    counts = np.array([a.shape[0] for a in lists], dtype=np.int32)
+    regs = np.concatenate(lists)
+    ids = int(rng.integers(0, 1 << 20)) * 2 + np.arange(len(lists), dtype=np.int64)
+    want = ref_all(ref, opt, pes, meta["ctg_offset"], seqs, off, counts, regs, ids)
+    got = dev.rescue_flat(opt, pes, seqs, off, counts, regs, ids)
+    assert_rescue_equal(got, want, counts, regs, f"128 pairs of mixed forms, seed {seed}")
 
 
 # ---- real batches -----------------------------------------------------------------------------------------------------------------------------------------
