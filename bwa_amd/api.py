@@ -16,7 +16,7 @@ try:   # torch bundles its own HIP runtime (libamdhip64); loading it first keeps
 except Exception:  # pragma: no cover
     torch = None
 
-from .structs import ALNREG_DTYPE, PAIR_DTYPE, PESTAT_DTYPE, PESTAT_INFO_DTYPE, PRIMARY_DTYPE, RESCUE_DTYPE, MemOpt
+from .structs import ALN_DTYPE, ALNREG_DTYPE, PAIR_DTYPE, PESTAT_DTYPE, PESTAT_INFO_DTYPE, PRIMARY_DTYPE, RESCUE_DTYPE, MemOpt
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 DEFAULT_LIB = os.path.join(HERE, "csrc", "libbwagpu.so")
@@ -62,6 +62,7 @@ EXPORTS = [
     "bwagpu_batch_cigars", "bwagpu_batch_cigar_ops", "bwagpu_debug_phase", "bwagpu_batch_matesw", "bwagpu_clone_to_device", "bwagpu_index_build", "bwagpu_built_free", "bwagpu_abi_sizes", "bwagpu_debug_prof", "bwagpu_debug_hist", "bwagpu_debug_seed_x2", "bwagpu_debug_chain_hist", "bwagpu_debug_dp", "bwagpu_debug_sort", "bwagpu_debug_sort_limits", "bwagpu_set_cigar_filter", "bwagpu_batch_reserve", "bwagpu_batch_footprint", "bwagpu_mem_info",
     "bwagpu_batch_primary", "bwagpu_primary_flat", "bwagpu_primary_limits", "bwagpu_batch_pair", "bwagpu_pair_flat", "bwagpu_pair_limits", "bwagpu_batch_rescue", "bwagpu_rescue_flat", "bwagpu_rescue_limits",
     "bwagpu_batch_pestat", "bwagpu_pestat_flat", "bwagpu_batch_pestat_hist", "bwagpu_pestat_finish", "bwagpu_pestat_limits",
+    "bwagpu_batch_alns", "bwagpu_alns_flat", "bwagpu_alns_limits", "bwagpu_aln_size",
     "bwagpu_trim", "bwagpu_set_option", "bwagpu_get_option", "bwagpu_set_default_option", "bwagpu_clear_default_options", "bwagpu_option_name",
 ]
 
@@ -124,6 +125,9 @@ def load_library(path: str | None = None) -> C.CDLL:
     L.bwagpu_batch_pestat_hist.argtypes = [C.c_void_p] * 5
     L.bwagpu_pestat_finish.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
     L.bwagpu_pestat_limits.restype = None
+    L.bwagpu_batch_alns.argtypes = [C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 6
+    L.bwagpu_alns_flat.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 6 + [C.c_int64] + [C.c_void_p] * 5
+    L.bwagpu_alns_limits.restype = None
     L.bwagpu_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_longlong]
     L.bwagpu_get_option.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p]
     L.bwagpu_set_default_option.argtypes = [C.c_char_p, C.c_longlong]
@@ -309,6 +313,36 @@ class BwaGpu:
         out = (C.c_int32 * 4)()
         self.L.bwagpu_primary_limits(out)
         return dict(zip(("lane_max", "lds_small", "lds_big", "scan"), list(out)))
+
+    def alns(self, opt: MemOpt, id0: int = 0):
+        """bwagpu_batch_alns: after download() and cigars(), mem_reg2aln of every region and mem_reg2sam's list of every read on the device; read i has id
+        id0 + i.  -> (ALN_DTYPE records in marked order per read, n_aln int32[n reads], PRIMARY_DTYPE records, n_pri, device time of the kernels in ms)"""
+        p, n, pr, ms = C.c_void_p(), C.c_int64(), C.c_void_p(), C.c_float()
+        n_aln = np.zeros(self._n, dtype=np.int32); n_pri = np.zeros(self._n, dtype=np.int32)
+        self._chk(self.L.bwagpu_batch_alns(self.h, C.byref(opt), int(id0), C.byref(p), C.byref(n), n_aln.ctypes.data, C.byref(pr), n_pri.ctypes.data, C.byref(ms)))
+        return self._take(p, n.value, ALN_DTYPE), n_aln, self._take(pr, n.value, PRIMARY_DTYPE), n_pri, ms.value
+
+    def alns_flat(self, opt: MemOpt, counts: np.ndarray, regs: np.ndarray, ids: np.ndarray, read_len: np.ndarray, cigs: np.ndarray, ops: np.ndarray):
+        """bwagpu_alns_flat: the same kernels on unmarked lists of the caller (read i: counts[i] records of regs, id ids[i], read_len[i] bases) with one CIGAR
+        record per region (cigs) and their operation array (ops) -> (records, n_aln, marking records, n_pri, ms)."""
+        counts = np.ascontiguousarray(counts, dtype=np.int32)
+        regs = np.ascontiguousarray(regs, dtype=ALNREG_DTYPE)
+        ids = np.ascontiguousarray(ids, dtype=np.int64)
+        read_len = np.ascontiguousarray(read_len, dtype=np.int32)
+        cigs = np.ascontiguousarray(cigs, dtype=CIGAR_DTYPE)
+        ops = np.ascontiguousarray(ops, dtype=np.uint32)
+        assert counts.shape == ids.shape == read_len.shape and int(counts.sum()) == regs.shape[0] == cigs.shape[0]
+        p, pr, ms = C.c_void_p(), C.c_void_p(), C.c_float()
+        n_aln = np.zeros(counts.shape[0], dtype=np.int32); n_pri = np.zeros(counts.shape[0], dtype=np.int32)
+        self._chk(self.L.bwagpu_alns_flat(self.h, C.byref(opt), counts.shape[0], counts.ctypes.data, regs.ctypes.data, ids.ctypes.data, read_len.ctypes.data,
+                                          cigs.ctypes.data, ops.ctypes.data, ops.shape[0], C.byref(p), n_aln.ctypes.data, C.byref(pr), n_pri.ctypes.data, C.byref(ms)))
+        return self._take(p, regs.shape[0], ALN_DTYPE), n_aln, self._take(pr, regs.shape[0], PRIMARY_DTYPE), n_pri, ms.value
+
+    def alns_limits(self) -> dict:
+        """bwagpu_alns_limits: the region count up to which one lane makes a read's list, and the regions a wavefront takes per step."""
+        out = (C.c_int32 * 2)()
+        self.L.bwagpu_alns_limits(out)
+        return dict(zip(("lane_max", "step"), list(out)))
 
     def pair(self, opt: MemOpt, pes: np.ndarray, id0: int = 0):
         """bwagpu_batch_pair: marking, then mem_pair of every pair (reads 2p, 2p + 1) of the last download() on the device; pes = PESTAT_DTYPE[4], read i has

@@ -43,6 +43,7 @@
 #include "dev_pair.h"
 #include "dev_rescue.h"
 #include "dev_pestat.h"
+#include "dev_alns.h"
 #include "dev_debug.h"
 
 #define BWAGPU_VERSION "bwagpu 0.1 (gfx950)"
@@ -100,6 +101,7 @@ struct bwagpu_s {
 	DevBuf d_pair_out, d_pair_lists, d_pair_ctr, d_pair_scratch, d_pair_tab, d_pair_npri;      // bwagpu_batch_pair / bwagpu_pair_flat: records, the wavefront forms' pair lists and their lengths, HBM working arrays, the table of log(2 erfc) values, bwagpu_pair_flat's n_pri
 	std::vector<double> pair_tab; bwagpu_pestat_t pair_tab_pes[4] = {}; i64 pair_tab_cap = -1; i32 pair_toff[4] = {}, pair_tlen[4] = {}; bool pair_tab_dev = false;   // the table as last filled: for these windows and this capacity; resident in d_pair_tab
 	DevBuf d_pst_hist, d_pst_out;                                                         // bwagpu_batch_pestat and its kin (dev_pestat.h): the histogram of insert sizes, four windows and the info record (PstOut) -- resident for the next device-side consumer
+	DevBuf d_aln_out, d_aln_n, d_aln_list, d_aln_ctr, d_aln_cigs, d_aln_ops, d_aln_len;                  // bwagpu_batch_alns / bwagpu_alns_flat (dev_alns.h): records, aa.n per read, the wavefront form's read list and its length; bwagpu_alns_flat's CIGAR records, operation array and read lengths
 	DevBuf d_pf_regs, d_pf_cnt, d_pf_off, d_pf_ids;                                       // ... and the uploaded lists of the *_flat calls (FlatLists)
 	std::vector<double> pri_log; i64 pri_log_dev = 0;                                      // log((double)k) by the host's libm for k < size; entries resident in d_pri_log
 	DevBuf d_msw_tasks, d_msw_out, d_msw_pes, d_msw_scratch;
@@ -508,7 +510,7 @@ extern "C" void bwagpu_destroy(bwagpu_t *h)
 		for (DevBuf *b : ib) b->release();
 		delete h->ibuf;
 	}
-	DevBuf *all[] = { &h->d_pst_hist, &h->d_pst_out, &h->d_pair_out, &h->d_pair_lists, &h->d_pair_ctr, &h->d_pair_scratch, &h->d_pair_tab, &h->d_pair_npri, &h->d_pri_out, &h->d_pri_npri, &h->d_pri_lists, &h->d_pri_ctr, &h->d_pri_scratch, &h->d_pri_log, &h->d_pf_regs, &h->d_pf_cnt, &h->d_pf_off, &h->d_pf_ids, &h->d_heavy, &h->d_dd_tmp, &h->d_p2_tasks, &h->d_vr_tab, &h->d_vr_ovf, &h->d_intv_n3, &h->d_cigl_list, &h->d_cigl_z, &h->d_cigl_ops, &h->d_cigl_md, &h->d_seq_2b, &h->d_seq_flags, &h->d_cig_ext, &h->d_msw_tasks, &h->d_msw_out, &h->d_msw_pes, &h->d_msw_scratch, &h->d_pack_off, &h->d_regs_packed, &h->d_pack_read, &h->d_cigs, &h->d_seq, &h->d_seq_nib, &h->d_off, &h->d_ctr, &h->d_tmp_intv,
+	DevBuf *all[] = { &h->d_pst_hist, &h->d_pst_out, &h->d_pair_out, &h->d_pair_lists, &h->d_pair_ctr, &h->d_pair_scratch, &h->d_pair_tab, &h->d_pair_npri, &h->d_pri_out, &h->d_pri_npri, &h->d_pri_lists, &h->d_pri_ctr, &h->d_pri_scratch, &h->d_pri_log, &h->d_aln_out, &h->d_aln_n, &h->d_aln_list, &h->d_aln_ctr, &h->d_aln_cigs, &h->d_aln_ops, &h->d_aln_len, &h->d_pf_regs, &h->d_pf_cnt, &h->d_pf_off, &h->d_pf_ids, &h->d_heavy, &h->d_dd_tmp, &h->d_p2_tasks, &h->d_vr_tab, &h->d_vr_ovf, &h->d_intv_n3, &h->d_cigl_list, &h->d_cigl_z, &h->d_cigl_ops, &h->d_cigl_md, &h->d_seq_2b, &h->d_seq_flags, &h->d_cig_ext, &h->d_msw_tasks, &h->d_msw_out, &h->d_msw_pes, &h->d_msw_scratch, &h->d_pack_off, &h->d_regs_packed, &h->d_pack_read, &h->d_cigs, &h->d_seq, &h->d_seq_nib, &h->d_off, &h->d_ctr, &h->d_tmp_intv,
 		&h->d_intv_n, &h->d_intv_off, &h->d_intv, &h->d_seed_n, &h->d_seed_off, &h->d_slot_pos, &h->d_slot_qbeg, &h->d_slot_len, &h->d_slot_rid, &h->d_slot_blob, &h->d_chain_n, &h->d_node_off,
 		&h->d_order, &h->d_bin_cnt, &h->d_seed_w, &h->d_seed_order, &h->d_nodes, &h->d_reg_off, &h->d_reg_cap_r, &h->d_reg_n_raw, &h->d_reg_n, &h->d_regs, &h->d_regs_raw, &h->d_dp_h, &h->d_dp_e, &h->d_minhsp };
 	for (DevBuf *b : all) b->release();
@@ -1793,16 +1795,21 @@ static int primary_run(bwagpu_t *h, const bwagpu_opt_t *opt, RegLists L, i64 log
 	return BWAGPU_OK;
 }
 
+// primary_run's log_need for the last download: a logarithm's argument is at most the longer side of a region (the read, or the read and the gaps its band
+// allows), its seed coverage (at most the read), or the read's number of regions plus one
+static i64 batch_log_need(const bwagpu_t *h, const bwagpu_opt_t *opt)
+{
+	const i64 need = 2 * (i64)h->max_len + 4 * (i64)(opt->w > 0 ? opt->w : 0) + 64;
+	return h->packed_max + 2 > need ? h->packed_max + 2 : need;
+}
+
 extern "C" int bwagpu_batch_primary(bwagpu_t *h, const bwagpu_opt_t *opt, int64_t id0, bwagpu_primary_t **out, int64_t *n_out, int32_t *n_pri, float *kernel_ms)
 {
 	if (!h || !opt || !h->ran || !h->downloaded || !out || !n_out) return BWAGPU_EINVAL;
 	const BusyGuard busy(h->ibuf->busy);
 	HIPCHK(h, hipSetDevice(h->device));
 	const i64 tot = h->packed_tot < 0 ? 0 : h->packed_tot;
-	// a logarithm's argument is at most the longer side of a region (the read, or the read and the gaps its band allows), its seed coverage (at most the read),
-	// or the read's number of regions plus one
-	i64 log_need = 2 * (i64)h->max_len + 4 * (i64)(opt->w > 0 ? opt->w : 0) + 64;
-	if (h->packed_max + 2 > log_need) log_need = h->packed_max + 2;
+	const i64 log_need = batch_log_need(h, opt);
 	*out = nullptr; *n_out = 0;
 	if (tot == 0) {      // no region in the whole batch: nothing to run (and the packed arrays may not exist)
 		ResultBlock<bwagpu_primary_t> res = result_block<bwagpu_primary_t>(0);
@@ -2346,6 +2353,115 @@ extern "C" int bwagpu_pestat_finish(bwagpu_t *h, const bwagpu_opt_t *opt, const 
 	const int rc = pestat_finish(h, opt);
 	(void)hipEventRecord(h->ev[1], h->stream);
 	return rc == BWAGPU_OK ? pestat_fetch(h, pes, info, kernel_ms) : rc;
+}
+
+// ---- the alignment list of every read on the device (dev_alns.h) -------------------------------------------------------------------------------------
+extern "C" void bwagpu_alns_limits(int32_t out[2]) { out[0] = ALN_LANE_MAX; out[1] = ALN_STEP; }
+extern "C" int bwagpu_aln_size(void) { return (int)sizeof(bwagpu_aln_t); }
+
+// The kernels of both entry points on the lists L: the marking (primary_run: its records stay in d_pri_out), then k_alns_lane / k_alns_wave with the CIGAR
+// records, operation array and read lengths of I (I.pri is set here).
+static int alns_run(bwagpu_t *h, const bwagpu_opt_t *opt, const RegLists &L, i64 log_need, AlnIn I, bwagpu_aln_t **alns, int32_t *n_aln, bwagpu_primary_t **pri, int32_t *n_pri, float *kernel_ms)
+{
+	const int n_reads = L.n;
+	const i64 tot = L.tot;
+	if (kernel_ms) *kernel_ms = 0.f;
+	ResultBlock<bwagpu_aln_t> res = result_block<bwagpu_aln_t>((size_t)tot);
+	if (!res) return BWAGPU_ENOMEM;
+	if (n_reads == 0 || tot == 0) {
+		ResultBlock<bwagpu_primary_t> none = result_block<bwagpu_primary_t>(0);
+		if (!none) return BWAGPU_ENOMEM;
+		for (int i = 0; i < n_reads; ++i) { if (n_aln) n_aln[i] = 0; if (n_pri) n_pri[i] = 0; }
+		if (pri) *pri = none.release();
+		*alns = res.release();
+		return BWAGPU_OK;
+	}
+	bwagpu_primary_t *recs_ = nullptr;
+	float ms_pri = 0.f, ms = 0.f;
+	const int rc = primary_run(h, opt, L, log_need, &recs_, n_pri, &ms_pri);
+	if (rc != BWAGPU_OK) return rc;
+	ResultBlock<bwagpu_primary_t> recs(recs_);
+	if (h->d_aln_out.ensure((size_t)tot * sizeof(bwagpu_aln_t)) || h->d_aln_n.ensure((size_t)n_reads * 4) || h->d_aln_list.ensure((size_t)n_reads * 4) || h->d_aln_ctr.ensure(sizeof(unsigned int))) {
+		h->err = "hipMalloc failed (alns)"; return BWAGPU_ENOMEM;
+	}
+	// a mapQ the host side of the marking had to compute (a logarithm outside the table) is not in the device's copy of the records yet
+	bool any = false;
+	for (i64 k = 0; k < tot && !any; ++k) any = (recs[k].flags & 1) != 0;
+	if (any) HIPCHK(h, hipMemcpyAsync(h->d_pri_out.p, recs.get(), (size_t)tot * sizeof(bwagpu_primary_t), hipMemcpyHostToDevice, h->stream));
+	HIPCHK(h, hipMemsetAsync(h->d_aln_ctr.p, 0, sizeof(unsigned int), h->stream));
+	I.pri = h->d_pri_out.as<bwagpu_primary_t>();
+	bwagpu_aln_t *d_out = h->d_aln_out.as<bwagpu_aln_t>();
+	i32 *d_n = h->d_aln_n.as<i32>(), *list = h->d_aln_list.as<i32>();
+	unsigned int *list_n = h->d_aln_ctr.as<unsigned int>();
+	(void)hipEventRecord(h->ev[0], h->stream);
+	int nb = (n_reads + ALN_LANE_BLOCK - 1) / ALN_LANE_BLOCK; if (nb > 256 * 12) nb = 256 * 12;
+	hipLaunchKernelGGL(k_alns_lane, dim3(nb), dim3(ALN_LANE_BLOCK), 0, h->stream, h->ix, *opt, n_reads, L.d_cnt, L.d_off, L.d_regs, I, d_out, d_n, list, list_n);
+	HIPCHK(h, hipGetLastError());
+	if (L.max_cnt > ALN_LANE_MAX) {      // (the list's length stays on the device)
+		hipLaunchKernelGGL(k_alns_wave, dim3(n_reads < 256 * 16 ? n_reads : 256 * 16), dim3(64), 0, h->stream, h->ix, *opt, L.d_cnt, L.d_off, L.d_regs, I, d_out, d_n, list, list_n);
+		HIPCHK(h, hipGetLastError());
+	}
+	(void)hipEventRecord(h->ev[1], h->stream);
+	std::vector<i32> na((size_t)n_reads);
+	HIPCHK(h, hipMemcpyAsync(res.get(), d_out, (size_t)tot * sizeof(bwagpu_aln_t), hipMemcpyDeviceToHost, h->stream));
+	HIPCHK(h, hipMemcpyAsync(na.data(), d_n, (size_t)n_reads * 4, hipMemcpyDeviceToHost, h->stream));
+	HIPCHK(h, wait_stream(h));
+	(void)hipEventElapsedTime(&ms, h->ev[0], h->ev[1]);
+	if (kernel_ms) *kernel_ms = ms_pri + ms;
+	if (n_aln) memcpy(n_aln, na.data(), (size_t)n_reads * 4);
+	if (pri) *pri = recs.release();
+	*alns = res.release();
+	return BWAGPU_OK;
+}
+
+extern "C" int bwagpu_batch_alns(bwagpu_t *h, const bwagpu_opt_t *opt, int64_t id0, bwagpu_aln_t **alns, int64_t *n_alns, int32_t *n_aln, bwagpu_primary_t **pri, int32_t *n_pri, float *kernel_ms)
+{
+	if (!h || !opt || !h->ran || !h->downloaded || h->cig_ext_n < 0 || !alns || !n_alns) return BWAGPU_EINVAL;
+	if (opt->flag & 0x800 /* MEM_F_PRIMARY5 */) return BWAGPU_EINVAL;
+	const BusyGuard busy(h->ibuf->busy);
+	HIPCHK(h, hipSetDevice(h->device));
+	*alns = nullptr; *n_alns = 0; if (pri) *pri = nullptr;
+	const RegLists L = lists_of_batch(h, id0);
+	AlnIn I = {}; I.cigs = h->d_cigs.as<bwagpu_cigar_t>(); I.ops = h->d_cig_ext.as<u32>(); I.n_ops = h->cig_ext_n; I.seq_off = h->d_off.as<i64>();
+	const int rc = alns_run(h, opt, L, batch_log_need(h, opt), I, alns, n_aln, pri, n_pri, kernel_ms);
+	if (rc == BWAGPU_OK) *n_alns = L.tot;
+	return rc;
+}
+
+extern "C" int bwagpu_alns_flat(bwagpu_t *h, const bwagpu_opt_t *opt, int n_reads, const int32_t *counts, const bwagpu_alnreg_t *regs, const int64_t *ids, const int32_t *read_len,
+								const bwagpu_cigar_t *cigs, const uint32_t *ops, int64_t n_ops, bwagpu_aln_t **alns, int32_t *n_aln, bwagpu_primary_t **pri, int32_t *n_pri, float *kernel_ms)
+{
+	if (!h || !opt || n_reads < 0 || !alns || n_ops < 0 || (n_ops > 0 && !ops) || (n_reads > 0 && (!counts || !ids || !read_len))) return BWAGPU_EINVAL;
+	if (opt->flag & 0x800 /* MEM_F_PRIMARY5 */) return BWAGPU_EINVAL;
+	FlatLists F; RegLists L;
+	if (!F.scan(h, (size_t)n_reads, counts, regs, counts)) return BWAGPU_EINVAL;
+	if (F.tot > 0 && !cigs) return BWAGPU_EINVAL;
+	for (int i = 0; i < n_reads; ++i) if (read_len[i] < 0) return BWAGPU_EINVAL;
+	for (i64 k = 0; k < F.tot; ++k) {
+		const bwagpu_cigar_t &c = cigs[k];
+		if (c.n_cigar < -1 || c.n_cigar > 32768) { h->err = "bwagpu_alns_flat: n_cigar outside [-1, 32768]"; return BWAGPU_EINVAL; }
+		if (c.n_cigar > 6) {
+			const u64 at = (u64)c.cigar[1] << 32 | c.cigar[0];
+			if (at > (u64)n_ops || (u64)c.n_cigar > (u64)n_ops - at) { h->err = "bwagpu_alns_flat: a CIGAR record points outside the operation array"; return BWAGPU_EINVAL; }
+		}
+	}
+	const BusyGuard busy(h->ibuf->busy);
+	HIPCHK(h, hipSetDevice(h->device));
+	*alns = nullptr; if (pri) *pri = nullptr;
+	const int rc = F.upload(h, "alns", counts, regs, ids, (size_t)n_reads, L);
+	if (rc != BWAGPU_OK) return rc;
+	AlnIn I = {}; I.n_ops = n_ops;
+	if (F.tot > 0) {
+		if (h->d_aln_cigs.ensure((size_t)F.tot * sizeof(bwagpu_cigar_t)) || h->d_aln_ops.ensure((size_t)(n_ops ? n_ops : 1) * 4) || h->d_aln_len.ensure((size_t)n_reads * 4)) {
+			h->err = "hipMalloc failed (alns)"; return BWAGPU_ENOMEM;
+		}
+		HIPCHK(h, hipMemcpyAsync(h->d_aln_cigs.p, cigs, (size_t)F.tot * sizeof(bwagpu_cigar_t), hipMemcpyHostToDevice, h->stream));
+		if (n_ops) HIPCHK(h, hipMemcpyAsync(h->d_aln_ops.p, ops, (size_t)n_ops * 4, hipMemcpyHostToDevice, h->stream));
+		HIPCHK(h, hipMemcpyAsync(h->d_aln_len.p, read_len, (size_t)n_reads * 4, hipMemcpyHostToDevice, h->stream));
+		HIPCHK(h, wait_stream(h));      // (the caller's arrays are pageable: the copies are done when they return, the wait keeps that independent of the runtime)
+		I.cigs = h->d_aln_cigs.as<bwagpu_cigar_t>(); I.ops = h->d_aln_ops.as<u32>(); I.read_len = h->d_aln_len.as<i32>();
+	}
+	return alns_run(h, opt, L, pri_log_need(counts, regs, n_reads), I, alns, n_aln, pri, n_pri, kernel_ms);
 }
 
 extern "C" int bwagpu_align_flat(bwagpu_t *h, const bwagpu_opt_t *opt, int n, const uint8_t *seqs, const int64_t *off,

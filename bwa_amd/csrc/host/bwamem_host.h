@@ -78,6 +78,7 @@ struct Read {   // == bseq1_t as the finalize code needs it
 	const CigHints *hints = nullptr;
 	const bwagpu_matesw_t *msw = nullptr; int n_msw = 0;   // device-computed mate-rescue alignments of this read (bwagpu_batch_matesw)
 	const bwagpu_primary_t *pri = nullptr;                 // device-computed marking and mapQ of this read's regions (bwagpu_batch_primary): one record per region
+	const bwagpu_aln_t *alns = nullptr;                    // single-end: the device's alignment list of this read (bwagpu_batch_alns), one record per record of `pri`; `hints` then holds the batch's CIGAR records and operation array
 	const bwagpu_pair_t *pair = nullptr;                   // first read of a pair: the device's mem_pair record of the pair as downloaded (bwagpu_batch_pair); both reads then have `pri`
 	const bwagpu_alnreg_t *merged = nullptr; int n_merged = 0;   // this read's list after the device's merge of mate-rescue hits (bwagpu_batch_rescue); `pri` then describes this list
 	const bwagpu_rescue_t *rescue = nullptr;               // first read of a pair: what that merge did with the pair; `pair` is then the record of the merged lists

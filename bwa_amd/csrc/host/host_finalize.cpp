@@ -323,6 +323,27 @@ Aln reg2aln(const bwagpu_opt_t &opt, const RefSeqs &ref, int l_query, const uint
 	return a;
 }
 
+// What reg2aln returns for place k of a read's marked list, from the device's record of it (bwagpu_batch_alns) and the region's CIGAR record, by index: no
+// search for the hint, no mapQ, no contig search.  The record's flag, sub and (printed: the line's; else an XA entry's) mapQ are taken as they are.
+static Aln aln_of_record(const Read &s, int k, bool printed)
+{
+	const bwagpu_aln_t &r = s.alns[k];
+	const bwagpu_cigar_t &c = s.hints->cigs[s.pri[k].src];
+	Aln a;
+	a.pos = r.pos; a.rid = r.rid; a.flag = r.flag; a.is_rev = (r.flags & BWAGPU_ALN_REV) != 0; a.is_alt = (r.flags & BWAGPU_ALN_ALT) != 0;
+	a.mapq = printed ? r.mapq_out : r.mapq; a.NM = r.nm; a.score = r.score; a.sub = r.sub; a.alt_sc = r.alt_sc;
+	if (r.rid < 0) return a;
+	const uint32_t *o = c.n_cigar <= 6 ? c.cigar : s.hints->ops + ((uint64_t)c.cigar[1] << 32 | c.cigar[0]);
+	const int lo = (r.flags & BWAGPU_ALN_DEL5) ? 1 : 0, hi = c.n_cigar - ((r.flags & BWAGPU_ALN_DEL3) ? 1 : 0);
+	a.cigar.reserve((size_t)r.n_cigar);
+	if (r.clip5) a.cigar.push_back((uint32_t)r.clip5 << 4 | 3);
+	a.cigar.insert(a.cigar.end(), o + lo, o + hi);
+	if (r.clip3) a.cigar.push_back((uint32_t)r.clip3 << 4 | 3);
+	if (c.md_len <= 8) { char b[8]; memcpy(b, &c.md, 8); a.md.assign(b, (size_t)c.md_len); }
+	else a.md.assign((const char*)(s.hints->ops + c.md), (size_t)c.md_len);
+	return a;
+}
+
 // ---- XA strings (mem_gen_alt, bwamem_extra.c:118-172) ------------------------------------------------------------------
 static inline int pri_idx(double ratio, const bwagpu_alnreg_t *a, int i)
 {
@@ -332,7 +353,8 @@ static inline int pri_idx(double ratio, const bwagpu_alnreg_t *a, int i)
 }
 
 // returns false when no XA exists for any region (the reference's NULL)
-static bool gen_alt(const bwagpu_opt_t &opt, const RefSeqs &ref, const Regs &av, int l_query, const uint8_t *query, std::vector<std::string> &xa, std::vector<char> &has, const CigHints *hints, const int32_t *dev_mapq = nullptr)
+static bool gen_alt(const bwagpu_opt_t &opt, const RefSeqs &ref, const Regs &av, int l_query, const uint8_t *query, std::vector<std::string> &xa, std::vector<char> &has, const CigHints *hints, const int32_t *dev_mapq = nullptr,
+					const Read *recs = nullptr /* a read with the device's alignment list: a listed region's Aln comes from its record */)
 {
 	int n = (int)av.size(), tot = 0;
 	const bwagpu_alnreg_t *a = av.data();
@@ -348,7 +370,7 @@ static bool gen_alt(const bwagpu_opt_t &opt, const RefSeqs &ref, const Regs &av,
 		int r = pri_idx(opt.XA_drop_ratio, a, i);
 		if (r < 0) continue;
 		if (cnt[r] > opt.max_XA_hits_alt || (!has_alt[r] && cnt[r] > opt.max_XA_hits)) continue;
-		Aln t = reg2aln(opt, ref, l_query, query, &a[i], hints, dev_mapq ? dev_mapq[i] : -1);
+		Aln t = recs && !(recs->alns[i].flags & BWAGPU_ALN_NOCIGAR) ? aln_of_record(*recs, i, false) : reg2aln(opt, ref, l_query, query, &a[i], hints, dev_mapq ? dev_mapq[i] : -1);
 		std::string &s = xa[r];
 		s += ref.ctg[t.rid].name; s += ','; s += "+-"[t.is_rev]; put_int(s, t.pos + 1); s += ',';
 		for (uint32_t c : t.cigar) { put_int(s, c >> 4); s += "MIDSHN"[c & 0xf]; }
@@ -514,8 +536,36 @@ void aln2sam(const bwagpu_opt_t &opt, const RefSeqs &ref, SamText &str, const Re
 }
 
 // ---- all records of one read (mem_reg2sam, bwamem.c:1033-1079) -----------------------------------------------------------
+// reg2sam for a read whose list the device has made (s.alns; av and dev_mapq as apply_primary leaves them): the three tests, the place in `aa`, the
+// supplementary flag and the mapQ cap are the records'; only a region whose CIGAR the device did not compute goes through reg2aln.
+static void reg2sam_alns(const bwagpu_opt_t &opt, const RefSeqs &ref, SamText &out, const Read &s, Regs &av, int extra_flag, const Aln *m, const char *rg_id, const int32_t *dev_mapq)
+{
+	std::vector<std::string> xa; std::vector<char> has;
+	bool have_xa = false;
+	out.reserve(out.size() + 2 * (size_t)s.l_seq + 320);
+	if (!(opt.flag & F_ALL)) have_xa = gen_alt(opt, ref, av, s.l_seq, s.seq, xa, has, s.hints, dev_mapq, &s);
+	std::vector<Aln> aa;
+	const int n = (int)av.size();
+	for (int k = 0; k < n; ++k) {
+		const bwagpu_aln_t &r = s.alns[k];
+		if (r.sel < 0) continue;
+		Aln q;
+		if (r.flags & BWAGPU_ALN_NOCIGAR) { q = reg2aln(opt, ref, s.l_seq, s.seq, &av[k], s.hints, dev_mapq[k]); q.flag = r.flag; q.sub = r.sub; q.mapq = r.mapq_out; }
+		else q = aln_of_record(s, k, true);
+		if (have_xa && has[k]) { q.has_xa = true; q.xa = xa[k]; }
+		q.flag |= extra_flag;
+		aa.push_back(std::move(q));
+	}
+	if (aa.empty()) {
+		std::vector<Aln> one(1, reg2aln(opt, ref, s.l_seq, s.seq, 0));
+		one[0].flag |= extra_flag;
+		aln2sam(opt, ref, out, s, one, 0, m, rg_id);
+	} else for (int k = 0; k < (int)aa.size(); ++k) aln2sam(opt, ref, out, s, aa, k, m, rg_id);
+}
+
 void reg2sam(const bwagpu_opt_t &opt, const RefSeqs &ref, SamText &out, const Read &s, Regs &av, int extra_flag, const Aln *m, const char *rg_id, const int32_t *dev_mapq)
 {
+	if (s.alns && s.pri && dev_mapq && s.hints && s.hints->ops) { reg2sam_alns(opt, ref, out, s, av, extra_flag, m, rg_id, dev_mapq); return; }
 	std::vector<std::string> xa; std::vector<char> has;
 	bool have_xa = false;
 	out.reserve(out.size() + 2 * (size_t)s.l_seq + 320);

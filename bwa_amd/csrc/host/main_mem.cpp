@@ -43,6 +43,8 @@ static int g_device_rescue = 0;   // BWAGPU_CLI_RESCUE=1: paired-end batches tak
 static int g_device_pestat = 0;   // BWAGPU_CLI_PESTAT=1: paired-end batches without -I take mem_pestat's windows from the device (bwagpu_batch_pestat; split over several devices: bwagpu_batch_pestat_hist per shard, summed, bwagpu_pestat_finish; same output)
 static int g_device_pair = 0;     // BWAGPU_CLI_PAIR=1: paired-end batches take the marking and mem_pair of the pairs the rescue loop leaves alone from the device (bwagpu_batch_pair; same output)
 static int g_device_primary = 0;  // BWAGPU_CLI_PRIMARY=1: single-end batches take primary/secondary marking and mapQ from the device (bwagpu_batch_primary; same output)
+static int g_device_alns = 0;     // BWAGPU_CLI_ALNS=1: single-end batches without -5 also take every region's alignment record and the read's list from the device (bwagpu_batch_alns, after the CIGAR call; same output)
+static std::atomic<long> g_n_alns_reads(0);      // ... reads finalized from such records
 static std::atomic<long> g_n_primary_reads(0);   // ... reads finalized from such records (the BWAGPU_CLI_TRACE line at the end of the run)
 
 // ---- options -----------------------------------------------------------------------------------------------------------
@@ -346,6 +348,7 @@ struct Sub {      // one mem_process_seqs call (bwamem.c:1235-1264) on the reads
 	uint32_t *cig_ops = nullptr;              // ... and the operation array its records with more than 6 operations point into
 	bwagpu_matesw_t *msw = nullptr; int64_t n_msw = 0;   // device-side mate-rescue alignments (bwagpu_batch_matesw)
 	bwagpu_primary_t *pri = nullptr;          // device-side marking + mapQ records of the regions, in each read's marked order (bwagpu_batch_primary; single-end, or paired-end with bwagpu_batch_pair)
+	bwagpu_aln_t *alns = nullptr;             // device-side alignment records of the regions, parallel to pri (bwagpu_batch_alns; single-end)
 	bwagpu_pair_t *pairs = nullptr;           // device-side mem_pair records of the pairs as downloaded (bwagpu_batch_pair)
 	bwagpu_alnreg_t *m_all = nullptr; int32_t *m_src = nullptr; std::vector<int32_t> m_counts; bwagpu_rescue_t *rescue = nullptr;   // bwagpu_batch_rescue: the merged lists (read i: m_counts[i] regions), one record per pair; pri / pairs then describe these lists
 	Pestat pes[4]; bool have_pes = false;     // insert-size windows, when they had to be computed before the finalize stage
@@ -409,7 +412,7 @@ static void device_sub(const std::vector<bwagpu_t*> &gpus, Sub &u, const RefSeqs
 	int D = (int)gpus.size();
 	const int units = pe ? n / 2 : n, per = pe ? 2 : 1;
 	if (D > units) D = units > 0 ? units : 1;
-	struct Shard { int lo = 0, hi = 0; std::vector<int64_t> off; bwagpu_alnreg_t *all = nullptr; int64_t tot = 0; bwagpu_cigar_t *cigs = nullptr; uint32_t *ops = nullptr; int64_t n_ops = 0; bwagpu_matesw_t *msw = nullptr; int64_t n_msw = 0; bwagpu_primary_t *pri = nullptr; bwagpu_pair_t *pairs = nullptr; bwagpu_alnreg_t *m_all = nullptr; int32_t *m_src = nullptr; int64_t m_tot = 0; bwagpu_rescue_t *rescue = nullptr; };
+	struct Shard { int lo = 0, hi = 0; std::vector<int64_t> off; bwagpu_alnreg_t *all = nullptr; int64_t tot = 0; bwagpu_cigar_t *cigs = nullptr; uint32_t *ops = nullptr; int64_t n_ops = 0; bwagpu_matesw_t *msw = nullptr; int64_t n_msw = 0; bwagpu_primary_t *pri = nullptr; bwagpu_aln_t *alns = nullptr; bwagpu_pair_t *pairs = nullptr; bwagpu_alnreg_t *m_all = nullptr; int32_t *m_src = nullptr; int64_t m_tot = 0; bwagpu_rescue_t *rescue = nullptr; };
 	std::vector<Shard> sh((size_t)D);
 	for (int d = 0; d < D; ++d) {
 		sh[d].lo = (int)((int64_t)units * d / D) * per; sh[d].hi = d + 1 == D ? n : (int)((int64_t)units * (d + 1) / D) * per;
@@ -527,7 +530,30 @@ static void device_sub(const std::vector<bwagpu_t*> &gpus, Sub &u, const RefSeqs
 	}
 	// mem_mark_primary_se + mem_approx_mapq_se of single-end reads on the device too: read i of the batch has id n_processed + i (bwamem.c:1227).  Paired-end
 	// batches mark after the host has merged the mate-rescue hits (mem_sam_pe), so they keep the host functions.
-	if (g_device_primary && !pe && u.tot > 0) {
+	// ... or, with the CIGAR records resident, the whole alignment list of every read (mem_reg2aln per region, mem_reg2sam's loop per read), which brings the
+	// marking records along.  Not with -5: mem_reorder_primary5 sits between the marking and the list.  Paired-end batches: the CIGARs of the merged lists are not
+	// on the device.
+	const bool dev_alns = g_device_alns && !pe && have_cigs && !(u.opt.flag & F_PRIMARY5);
+	if (dev_alns) {
+		on_devices([&](int d) {
+			Shard &s = sh[d];
+			if (s.tot == 0) return;
+			int64_t na = 0;
+			int rc = bwagpu_batch_alns(gpus[d], &u.opt, u.n_processed + s.lo, &s.alns, &na, nullptr, &s.pri, nullptr, nullptr);
+			if (rc != BWAGPU_OK || na != s.tot) device_fail(gpus[d], rc, "bwagpu_batch_alns returned another number of records than bwagpu_batch_download");
+		});
+		if (D == 1) { u.pri = sh[0].pri; u.alns = sh[0].alns; }
+		else {      // (records name regions by the index within their read: nothing moves with the shard)
+			u.pri = (bwagpu_primary_t*)malloc((size_t)u.tot * sizeof(bwagpu_primary_t)); u.alns = (bwagpu_aln_t*)malloc((size_t)u.tot * sizeof(bwagpu_aln_t));
+			if (!u.pri || !u.alns) { fprintf(stderr, "[E::%s] out of memory\n", "mem_process_seqs"); exit(EXIT_FAILURE); }
+			int64_t k = 0;
+			for (auto &s : sh) {
+				if (s.tot) { memcpy(u.pri + k, s.pri, (size_t)s.tot * sizeof(bwagpu_primary_t)); memcpy(u.alns + k, s.alns, (size_t)s.tot * sizeof(bwagpu_aln_t)); }
+				k += s.tot; bwagpu_free(s.pri); s.pri = nullptr; bwagpu_free(s.alns); s.alns = nullptr;
+			}
+		}
+	}
+	if (!dev_alns && g_device_primary && !pe && u.tot > 0) {
 		on_devices([&](int d) {
 			Shard &s = sh[d];
 			if (s.tot == 0) return;
@@ -659,7 +685,7 @@ static void finalize_sub(const RefSeqs &ref, Work &w, Sub &u, const Pestat *pes0
 		reads[i].comment = copy_comment && q.has_comment ? T + q.comment : nullptr;
 		reads[i].seq = u.flat.data() + u.off[i]; reads[i].qual = q.has_qual ? T + q.qual : nullptr; reads[i].l_seq = q.l_seq;
 		if (u.rescue) { reads[i].merged = u.m_all + moff[i]; reads[i].n_merged = u.m_counts[i]; reads[i].pri = u.pri + moff[i]; if (!(i & 1)) reads[i].rescue = u.rescue + (i >> 1); }
-		else if (u.pri) reads[i].pri = u.pri + roff[i];
+		else if (u.pri) { reads[i].pri = u.pri + roff[i]; if (u.alns) reads[i].alns = u.alns + roff[i]; }
 		if (u.pairs && !(i & 1)) reads[i].pair = u.pairs + (i >> 1);
 	});
 	if (u.opt.flag & F_PE) for (int i = 0; i + 1 < n; i += 2) if (strcmp(reads[i].name, reads[i + 1].name) != 0) { fprintf(stderr, "[mem_sam_pe] paired reads have different names: \"%s\", \"%s\"\n", reads[i].name, reads[i + 1].name); exit(EXIT_FAILURE); }
@@ -675,6 +701,7 @@ static void finalize_sub(const RefSeqs &ref, Work &w, Sub &u, const Pestat *pes0
 	}
 	if (u.rescue) { free(u.rescue); u.rescue = nullptr; free(u.m_all); u.m_all = nullptr; free(u.m_src); u.m_src = nullptr; }
 	if (u.pairs) { free(u.pairs); u.pairs = nullptr; free(u.pri); u.pri = nullptr; }
+	if (u.alns) { g_n_alns_reads += n; bwagpu_free(u.alns); u.alns = nullptr; bwagpu_free(u.pri); u.pri = nullptr; }
 	if (u.pri) { g_n_primary_reads += n; bwagpu_free(u.pri); u.pri = nullptr; }
 	bwagpu_free(u.all); u.all = nullptr; bwagpu_free(u.cigs); u.cigs = nullptr; bwagpu_free(u.cig_ops); u.cig_ops = nullptr; bwagpu_free(u.msw); u.msw = nullptr;
 	if (g_verbose >= 3) fprintf(stderr, "[M::%s] Processed %d reads in %.3f real sec\n", "mem_process_seqs", n, u.t_dev + (now_s() - t0));
@@ -940,6 +967,7 @@ int main(int argc, char *argv[])
 	if (getenv("BWAGPU_CLI_MATESW")) g_device_matesw = atoi(getenv("BWAGPU_CLI_MATESW"));
 	if (getenv("BWAGPU_CLI_CIGARS")) g_device_cigars = atoi(getenv("BWAGPU_CLI_CIGARS"));
 	if (getenv("BWAGPU_CLI_PRIMARY")) g_device_primary = atoi(getenv("BWAGPU_CLI_PRIMARY"));
+	if (getenv("BWAGPU_CLI_ALNS")) g_device_alns = atoi(getenv("BWAGPU_CLI_ALNS"));
 	if (getenv("BWAGPU_CLI_PAIR")) g_device_pair = atoi(getenv("BWAGPU_CLI_PAIR"));
 	if (getenv("BWAGPU_CLI_RESCUE")) g_device_rescue = atoi(getenv("BWAGPU_CLI_RESCUE"));
 	if (getenv("BWAGPU_CLI_PESTAT")) g_device_pestat = atoi(getenv("BWAGPU_CLI_PESTAT"));
@@ -1146,6 +1174,7 @@ int main(int argc, char *argv[])
 	if (g_device_rescue && tl_trace && hostmem::g_pairs_merged_on_device.load() > 0)
 		fprintf(stderr, "[D::main_mem] %ld pairs merged on the device (BWAGPU_CLI_RESCUE), %ld of them with rescue alignments\n", hostmem::g_pairs_merged_on_device.load(), hostmem::g_pairs_merged_aligned.load());
 	if (g_device_pair && tl_trace) fprintf(stderr, "[D::main_mem] %ld pairs paired from device records (BWAGPU_CLI_PAIR)\n", hostmem::g_pairs_from_device.load());
+	if (g_device_alns && tl_trace) fprintf(stderr, "[D::main_mem] %ld reads finalized from device alignment records (BWAGPU_CLI_ALNS)\n", g_n_alns_reads.load());
 	if (g_device_primary && tl_trace) fprintf(stderr, "[D::main_mem] %ld reads finalized from device primary/mapQ records (BWAGPU_CLI_PRIMARY)\n", g_n_primary_reads.load());
 	if (g_verbose >= 3) { const double dt = now_s() - t_start; fprintf(stderr, "[M::%s] %ld reads in %.3f sec after the index was loaded: %.0f reads/s\n", "main_mem", n_reads_total.load(), dt, dt > 0 ? n_reads_total.load() / dt : 0.);
 		fprintf(stderr, "[M::%s] stage busy time: read %.3f s, encode %.3f s, device %.3f s (over %d handles), finalize %.3f s, write %.3f s\n", "main_mem", busy_read, busy_enc, busy_dev_us.load() * 1e-6, n_work, busy_fin, busy_write);

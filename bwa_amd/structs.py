@@ -43,6 +43,12 @@ PRIMARY_DTYPE = np.dtype([("src", "<i4"), ("secondary", "<i4"), ("secondary_all"
                           ("mapq", "<i4"), ("flags", "<i4")])
 assert PRIMARY_DTYPE.itemsize == 32
 
+# bwagpu_aln_t: one region as mem_reg2aln returns it and as mem_reg2sam's loop lists it (bwagpu_batch_alns / bwagpu_alns_flat)
+ALN_DTYPE = np.dtype([("pos", "<i8"), ("rid", "<i4"), ("flag", "<i4"), ("mapq", "<i4"), ("mapq_out", "<i4"), ("nm", "<i4"), ("n_cigar", "<i4"), ("score", "<i4"),
+                      ("sub", "<i4"), ("alt_sc", "<i4"), ("sel", "<i4"), ("clip5", "<i4"), ("clip3", "<i4"), ("flags", "<i4"), ("pad_", "<i4")])
+assert ALN_DTYPE.itemsize == 64
+ALN_NOCIGAR, ALN_REV, ALN_ALT, ALN_DEL5, ALN_DEL3 = 0x1, 0x2, 0x4, 0x8, 0x10      # bits of `flags` (BWAGPU_ALN_*)
+
 # bwagpu_pestat_t == mem_pestat_t (4 bytes of padding before the doubles), bwagpu_pair_t: mem_pair's results for one pair (bwagpu_batch_pair / bwagpu_pair_flat)
 PESTAT_DTYPE = np.dtype({"names": ["low", "high", "failed", "avg", "std"], "formats": ["<i4", "<i4", "<i4", "<f8", "<f8"], "offsets": [0, 4, 8, 16, 24], "itemsize": 32})
 PAIR_DTYPE = np.dtype([("score", "<i4"), ("sub", "<i4"), ("n_sub", "<i4"), ("z", "<i4", (2,)), ("flags", "<i4"), ("n_cand", "<i8")])

@@ -391,6 +391,47 @@ int  bwagpu_pestat_finish(bwagpu_t *h, const bwagpu_opt_t *opt, const uint32_t *
                           bwagpu_pestat_t pes[4], bwagpu_pestat_info_t *info, float *kernel_ms);
 void bwagpu_pestat_limits(int32_t out[2]);   /* MIN_DIR_CNT, largest max_ins served (1 << 22) */
 
+/* The alignment list of a read on the device: per region of the marked list what mem_reg2aln (bwamem.c:1119-1189) returns for it, and per read what the loop
+ * of mem_reg2sam (bwamem.c:1045-1062) makes of those results.  The CIGAR is not recomputed: from a record and the region's bwagpu_cigar_t a caller writes the
+ * final CIGAR (clip5, then the record's operations without the dropped deletion, then clip3), NM, MD, AS, XS and the SA / XA fields. */
+#define BWAGPU_ALN_NOCIGAR 0x1   /* the region's CIGAR record has n_cigar == -1: pos, n_cigar and nm are not final, the caller runs mem_reg2aln for this region */
+#define BWAGPU_ALN_REV     0x2   /* is_rev */
+#define BWAGPU_ALN_ALT     0x4   /* is_alt */
+#define BWAGPU_ALN_DEL5    0x8   /* the CIGAR record's first operation, a deletion, is dropped (pos has moved by its length) */
+#define BWAGPU_ALN_DEL3    0x10  /* the CIGAR record's last operation, a deletion, is dropped */
+typedef struct {
+	int64_t pos;            /* on contig rid; -1 for an unmapped region (rb < 0 || re < 0: rid -1, flag 0x4) */
+	int32_t rid;
+	int32_t flag;           /* 0x100 for a secondary; 0x800 or (MEM_F_NO_MULTI) 0x10000 for every printed non-secondary after the first; the caller ORs its extra_flag */
+	int32_t mapq;           /* mem_reg2aln's (0 for a secondary): what an XA entry of the region prints */
+	int32_t mapq_out;       /* what the region's own line prints: mapq capped by aa[0]'s unless MEM_F_KEEP_SUPP_MAPQ is set or the hit is ALT */
+	int32_t nm;             /* of the CIGAR record */
+	int32_t n_cigar;        /* final: the record's operations without a dropped deletion, plus the clips */
+	int32_t score, sub;     /* sub = max(sub, csub); -1 for a printed secondary */
+	int32_t alt_sc;
+	int32_t sel;            /* place of the region in mem_reg2sam's list `aa`, or -1 where one of its three tests skips the region */
+	int32_t clip5, clip3;   /* by strand; 0: none */
+	int32_t flags;          /* BWAGPU_ALN_* */
+	int32_t pad_;           /* zero */
+} bwagpu_aln_t;             /* 64 bytes */
+/* After bwagpu_batch_download AND bwagpu_batch_cigars of the same batch: the marking kernels of bwagpu_batch_primary on the downloaded lists (read i has id
+ * id0 + i), then one record per downloaded region, in marked order per read (record k of a read belongs to region `src` of its k-th marking record).
+ * n_aln[i] (may be NULL) = aa.n of read i; 0: the caller writes the unmapped record.  pri / n_pri (may be NULL) receive bwagpu_batch_primary's records and
+ * return values; *kernel_ms (may be NULL) the device time of all kernels (HIP events, summed over the segments).  Free *alns and *pri with bwagpu_free.
+ * BWAGPU_EINVAL: before a download, without CIGAR records for this download, MEM_F_PRIMARY5 in opt->flag (mem_reorder_primary5 between marking and
+ * mem_reg2sam is not on the device), NULL h / opt / alns / n_alns. */
+int bwagpu_batch_alns(bwagpu_t *h, const bwagpu_opt_t *opt, int64_t id0, bwagpu_aln_t **alns, int64_t *n_alns, int32_t *n_aln,
+					  bwagpu_primary_t **pri, int32_t *n_pri, float *kernel_ms);
+/* The same kernels on unmarked lists of the caller (as bwagpu_primary_flat: read i has counts[i] regions in regs and id ids[i]) with read_len[i] bases; cigs:
+ * one CIGAR record per region, in the regions' order, pointing into the n_ops entries of ops (the layout bwagpu_batch_cigars / bwagpu_batch_cigar_ops
+ * deliver).  *alns: sum of counts records.  BWAGPU_EINVAL also for a region's rid outside the index, an n_cigar outside [-1, 32768], a reference to
+ * operations outside [0, n_ops) and a negative read_len. */
+int bwagpu_alns_flat(bwagpu_t *h, const bwagpu_opt_t *opt, int n_reads, const int32_t *counts, const bwagpu_alnreg_t *regs, const int64_t *ids, const int32_t *read_len,
+					 const bwagpu_cigar_t *cigs, const uint32_t *ops, int64_t n_ops, bwagpu_aln_t **alns, int32_t *n_aln, bwagpu_primary_t **pri, int32_t *n_pri, float *kernel_ms);
+/* out[0] regions up to which one lane makes a read's list, out[1] regions a wavefront takes per step */
+void bwagpu_alns_limits(int32_t out[2]);
+int  bwagpu_aln_size(void);   /* sizeof(bwagpu_aln_t) as compiled */
+
 /* ---- index construction on the device -------------------------------------------------------- */
 /* The arrays `bwa index` leaves in bwt_t after bwt_bwtgen2/bwt_pac2bwt + bwt_bwtupdate_core + bwt_cal_sa
  * (bwtindex.c:64-120, 150-172; bwt.c:62-84), built from the 2-bit packed forward strand by a suffix sort in HBM
