@@ -16,7 +16,7 @@ try:   # torch bundles its own HIP runtime (libamdhip64); loading it first keeps
 except Exception:  # pragma: no cover
     torch = None
 
-from .structs import ALN_DTYPE, ALNREG_DTYPE, PAIR_DTYPE, PESTAT_DTYPE, PESTAT_INFO_DTYPE, PRIMARY_DTYPE, RESCUE_DTYPE, MemOpt
+from .structs import ALN_DTYPE, ALNREG_DTYPE, PAIR_DTYPE, PESTAT_DTYPE, PESTAT_INFO_DTYPE, PRIMARY_DTYPE, RESCUE_DTYPE, SAMPE_DTYPE, MemOpt, PeOut
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 DEFAULT_LIB = os.path.join(HERE, "csrc", "libbwagpu.so")
@@ -63,6 +63,7 @@ EXPORTS = [
     "bwagpu_batch_primary", "bwagpu_primary_flat", "bwagpu_primary_limits", "bwagpu_batch_pair", "bwagpu_pair_flat", "bwagpu_pair_limits", "bwagpu_batch_rescue", "bwagpu_rescue_flat", "bwagpu_rescue_limits",
     "bwagpu_batch_pestat", "bwagpu_pestat_flat", "bwagpu_batch_pestat_hist", "bwagpu_pestat_finish", "bwagpu_pestat_limits",
     "bwagpu_batch_alns", "bwagpu_alns_flat", "bwagpu_alns_limits", "bwagpu_aln_size",
+    "bwagpu_batch_sampe", "bwagpu_sampe_flat", "bwagpu_sampe_limits", "bwagpu_sampe_size",
     "bwagpu_trim", "bwagpu_set_option", "bwagpu_get_option", "bwagpu_set_default_option", "bwagpu_clear_default_options", "bwagpu_option_name",
 ]
 
@@ -128,6 +129,9 @@ def load_library(path: str | None = None) -> C.CDLL:
     L.bwagpu_batch_alns.argtypes = [C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 6
     L.bwagpu_alns_flat.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 6 + [C.c_int64] + [C.c_void_p] * 5
     L.bwagpu_alns_limits.restype = None
+    L.bwagpu_batch_sampe.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+    L.bwagpu_sampe_flat.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 7
+    L.bwagpu_sampe_limits.restype = None
     L.bwagpu_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_longlong]
     L.bwagpu_get_option.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p]
     L.bwagpu_set_default_option.argtypes = [C.c_char_p, C.c_longlong]
@@ -417,6 +421,42 @@ class BwaGpu:
         out = (C.c_int32 * 4)()
         self.L.bwagpu_rescue_limits(out)
         return dict(zip(("lane_max", "lds_max"), list(out)[:2]))
+
+    def _pe_out(self, n, counts, o):
+        m = int(o.n_regs)
+        return dict(counts=counts, regs=self._take(C.c_void_p(o.regs), m, ALNREG_DTYPE), src=self._take(C.c_void_p(o.src), m, np.dtype("<i4")), rescue=self._take(C.c_void_p(o.rescue), n // 2, RESCUE_DTYPE),
+                    pri=self._take(C.c_void_p(o.pri), m, PRIMARY_DTYPE), n_pri=self._take(C.c_void_p(o.n_pri), n, np.dtype("<i4")), pairs=self._take(C.c_void_p(o.pairs), n // 2, PAIR_DTYPE),
+                    sampe=self._take(C.c_void_p(o.sampe), n // 2, SAMPE_DTYPE), cigs=self._take(C.c_void_p(o.cigs), m, CIGAR_DTYPE), ops=self._take(C.c_void_p(o.ops), int(o.n_ops), np.dtype("<u4")),
+                    alns=self._take(C.c_void_p(o.alns), m, ALN_DTYPE), n_aln=self._take(C.c_void_p(o.n_aln), n, np.dtype("<i4")), kernel_ms=list(o.kernel_ms), ms=float(sum(o.kernel_ms)))
+
+    def sampe(self, opt: MemOpt, pes: np.ndarray, id0: int = 0) -> dict:
+        """bwagpu_batch_sampe: every pair (reads 2p, 2p + 1) of the last download() decided on the device -- rescue(), then the SAMPE_DTYPE record of every pair, the marking
+        records as mem_sam_pe leaves the lists, a CIGAR record and an ALN_DTYPE record per merged region.  -> dict: what rescue() returns (pri patched), sampe, cigs, ops, alns,
+        n_aln, kernel_ms (six segments), ms (their sum)."""
+        pes = np.ascontiguousarray(pes, dtype=PESTAT_DTYPE)
+        assert pes.shape == (4,)
+        counts, o = np.zeros(self._n, dtype=np.int32), PeOut()
+        self._chk(self.L.bwagpu_batch_sampe(self.h, C.byref(opt), pes.ctypes.data, int(id0), counts.ctypes.data, C.byref(o)))
+        return self._pe_out(self._n, counts, o)
+
+    def sampe_flat(self, opt: MemOpt, pes: np.ndarray, seqs: np.ndarray, off: np.ndarray, counts_in: np.ndarray, regs_in: np.ndarray, ids: np.ndarray) -> dict:
+        """bwagpu_sampe_flat: the same kernels on reads and region lists of the caller (the inputs of rescue_flat; ids: one per read)."""
+        pes = np.ascontiguousarray(pes, dtype=PESTAT_DTYPE)
+        seqs = np.ascontiguousarray(seqs, dtype=np.uint8); off = np.ascontiguousarray(off, dtype=np.int64)
+        counts_in = np.ascontiguousarray(counts_in, dtype=np.int32); regs_in = np.ascontiguousarray(regs_in, dtype=ALNREG_DTYPE)
+        ids = np.ascontiguousarray(ids, dtype=np.int64)
+        n = counts_in.shape[0]
+        assert pes.shape == (4,) and n % 2 == 0 and off.shape == (n + 1,) and int(counts_in.sum()) == regs_in.shape[0] and ids.shape == (n,)
+        counts, o = np.zeros(n, dtype=np.int32), PeOut()
+        self._chk(self.L.bwagpu_sampe_flat(self.h, C.byref(opt), pes.ctypes.data, n // 2, seqs.ctypes.data, off.ctypes.data, counts_in.ctypes.data, regs_in.ctypes.data, ids.ctypes.data,
+                                           counts.ctypes.data, C.byref(o)))
+        return self._pe_out(n, counts, o)
+
+    def sampe_limits(self) -> dict:
+        """bwagpu_sampe_limits: the length of a pair's longer list up to which one lane decides the pair, and the places a wavefront takes per step."""
+        out = (C.c_int32 * 2)()
+        self.L.bwagpu_sampe_limits(out)
+        return dict(zip(("lane_max", "step"), list(out)))
 
     def pestat(self, opt: MemOpt):
         """bwagpu_batch_pestat: mem_pestat of the last download() on the device (reads 2p, 2p + 1 are mates).

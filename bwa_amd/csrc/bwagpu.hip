@@ -44,6 +44,7 @@
 #include "dev_rescue.h"
 #include "dev_pestat.h"
 #include "dev_alns.h"
+#include "dev_sampe.h"
 #include "dev_debug.h"
 
 #define BWAGPU_VERSION "bwagpu 0.1 (gfx950)"
@@ -107,6 +108,8 @@ struct bwagpu_s {
 	DevBuf d_msw_tasks, d_msw_out, d_msw_pes, d_msw_scratch;
 	enum { RS_X, RS_TOFF, RS_TIX, RS_ARENA, RS_ASRC, RS_ACNT, RS_POFF, RS_REGS, RS_SRC, RS_OUT, RS_LISTS, RS_CTR, RS_KEYS, RS_STAGE, RS_SEQ, RS_SEQOFF, RS_PAIRIDS, RS_N };
 	DevBuf d_rs[RS_N];      // bwagpu_batch_rescue / bwagpu_rescue_flat (dev_rescue.h): anchors x 4 per read and their prefix sums, the task table, the arena of working lists (regions, src, lengths), the packed merged lists (offsets, regions, src), records, the wavefront forms' pair lists and their lengths, HBM sort keys; bwagpu_rescue_flat's sequences, the pairs' ids
+	enum { SP_OUT, SP_LIST, SP_CTR, SP_READ, SP_CIGS, SP_EXT, SP_N };
+	DevBuf d_sp[SP_N];      // bwagpu_batch_sampe / bwagpu_sampe_flat (dev_sampe.h): the pair records, the wavefront form's pair list and its length, the merged lists' region-to-read map, their CIGAR records and operation array
 	i64 cigl_z_cap = 0;                          // bytes per direction matrix of the long CIGAR tier's scratch (grows with the batches)
 	DevBuf d_cigl_z, d_cigl_ops, d_cigl_md, d_cigl_list;      // scratch of the long-segment CIGAR tier (k_cigar_long): direction matrices, operations, MD strings per workgroup
 	DevBuf d_cig_ext; i64 cig_ext_n = -1;   // operation array of the last bwagpu_batch_cigars (records with 7..64 operations point into it)
@@ -515,6 +518,7 @@ extern "C" void bwagpu_destroy(bwagpu_t *h)
 		&h->d_order, &h->d_bin_cnt, &h->d_seed_w, &h->d_seed_order, &h->d_nodes, &h->d_reg_off, &h->d_reg_cap_r, &h->d_reg_n_raw, &h->d_reg_n, &h->d_regs, &h->d_regs_raw, &h->d_dp_h, &h->d_dp_e, &h->d_minhsp };
 	for (DevBuf *b : all) b->release();
 	for (DevBuf &b : h->d_rs) b.release();
+	for (DevBuf &b : h->d_sp) b.release();
 	for (int i = 0; i < 8; ++i) if (h->ev[i]) (void)hipEventDestroy(h->ev[i]);
 	if (h->ev_wait) (void)hipEventDestroy(h->ev_wait);
 	if (h->stream) (void)hipStreamDestroy(h->stream);
@@ -1425,20 +1429,22 @@ extern "C" int bwagpu_batch_download(bwagpu_t *h, int32_t *counts, bwagpu_alnreg
 	return BWAGPU_OK;
 }
 
-extern "C" int bwagpu_batch_cigars(bwagpu_t *h, const bwagpu_opt_t *opt, bwagpu_cigar_t **out, int64_t *n_out)
+// What the CIGAR kernels read and where they leave their records: tot regions `regs`, region g of read reg_read[g], the reads' lists starting at off[] (the filter's
+// "best region of the read"); the reads' bases seq / seq_off; the records go to *d_cigs and the operation array to *d_ext (grown here).
+struct CigLists {
+	i64 tot; const bwagpu_alnreg_t *regs; const i32 *reg_read; const i64 *off;
+	const u8 *seq; const i64 *seq_off; int n_reads, max_len; i64 n_bases;
+	DevBuf *d_cigs, *d_ext;
+};
+// The kernels of bwagpu_batch_cigars on the regions C describes (tot > 0): the LDS tiers, the long tier, a second attempt when the operation array was too small.
+// res (may be null): the records' host copy; *ext_n: entries of the operation array in use; ms[0] / ms[1]: device time of the kernels and of the copy.
+static int cigars_run(bwagpu_t *h, const bwagpu_opt_t *opt, const CigLists &C, bwagpu_cigar_t *res, i64 *ext_n, float ms[2])
 {
-	if (!h || !opt || !h->ran || h->packed_tot < 0 || !out || !n_out) return BWAGPU_EINVAL;
-	const BusyGuard busy(h->ibuf->busy);
-	if (opt->e_del <= 0 || opt->e_ins <= 0) return BWAGPU_EINVAL;
-	HIPCHK(h, hipSetDevice(h->device));
-	const i64 tot = h->packed_tot;
-	h->phase = 40; h->cig_ext_n = -1;
+	const i64 tot = C.tot;
 	static_assert(sizeof(bwagpu_cigar_t) == 48, "layout");
-	bwagpu_cigar_t *res = (bwagpu_cigar_t*)result_alloc((size_t)(tot ? tot : 1) * sizeof(bwagpu_cigar_t));
-	if (!res) return BWAGPU_ENOMEM;
-	if (tot) {
-		if (h->d_cigs.ensure((size_t)tot * sizeof(bwagpu_cigar_t)) || h->d_ctr.ensure(sizeof(Counters))) { bwagpu_free(res); h->err = "hipMalloc failed (cigars)"; return BWAGPU_ENOMEM; }
-		Batch B = {}; B.seq = h->d_seq.as<u8>(); B.off = h->d_off.as<i64>(); B.n_reads = h->n_reads; B.max_len = h->max_len;
+	{
+		if (C.d_cigs->ensure((size_t)tot * sizeof(bwagpu_cigar_t)) || h->d_ctr.ensure(sizeof(Counters))) { h->err = "hipMalloc failed (cigars)"; return BWAGPU_ENOMEM; }
+		Batch B = {}; B.seq = const_cast<u8*>(C.seq); B.off = const_cast<i64*>(C.seq_off); B.n_reads = C.n_reads; B.max_len = C.max_len;
 		B.ctr = h->d_ctr.as<Counters>(); B.stats = h->stats_on;      // (stats: the fills' DP cells, counted in glb_cells / glb_calls -- the batch's run is over, its counters have been read)
 		unsigned long long *next = &h->d_ctr.as<Counters>()->next_ext, *ext_used = &h->d_ctr.as<Counters>()->cig_ext_used;
 		const int zc[2] = { CIG_Z_SMALL, CIG_Z_BIG };
@@ -1446,7 +1452,7 @@ extern "C" int bwagpu_batch_cigars(bwagpu_t *h, const bwagpu_opt_t *opt, bwagpu_
 		// operation array: sized for a typical batch; one that needs more (gap-rich reads) reports the total it reserved and is
 		// redone once with exactly that much
 		i64 ext_cap = tot * 4 + 65536;
-		if (h->max_len > CIG_MAX_LEN && h->n_bases / 2 + 65536 > ext_cap) ext_cap = h->n_bases / 2 + 65536;   // (long reads: ~0.37 entries per base at 13 % indels -- operations and MD characters)
+		if (C.max_len > CIG_MAX_LEN && C.n_bases / 2 + 65536 > ext_cap) ext_cap = C.n_bases / 2 + 65536;   // (long reads: ~0.37 entries per base at 13 % indels -- operations and MD characters)
 		if (h->cfg.cig_ops_cap > 0) ext_cap = h->cfg.cig_ops_cap;   // (tests of the second attempt)
 		if (ext_cap < 1) ext_cap = 1;
 		// third tier (k_cigar_long): segments, bands and operation counts beyond the LDS tiers' limits; one 64-thread workgroup per region at a time,
@@ -1467,7 +1473,7 @@ extern "C" int bwagpu_batch_cigars(bwagpu_t *h, const bwagpu_opt_t *opt, bwagpu_
 		hipError_t e = hipSuccess;
 		(void)hipEventRecord(h->ev[0], h->stream);
 		for (int attempt = 0; attempt < 2; ++attempt) {
-			if (h->d_cig_ext.ensure((size_t)ext_cap * 4)) { bwagpu_free(res); h->err = "hipMalloc failed (cigars)"; return BWAGPU_ENOMEM; }
+			if (C.d_ext->ensure((size_t)ext_cap * 4)) { h->err = "hipMalloc failed (cigars)"; return BWAGPU_ENOMEM; }
 			e = hipMemsetAsync(ext_used, 0, sizeof(unsigned long long), h->stream);
 			if (e == hipSuccess && h->stats_on) e = hipMemsetAsync(&h->d_ctr.as<Counters>()->glb_calls, 0, 2 * sizeof(unsigned long long), h->stream);      // (glb_calls, glb_cells: adjacent)
 			for (int tier = 0; tier < n_tier && e == hipSuccess; ++tier) {   // narrow bands at high occupancy, then the deferred wide ones
@@ -1480,22 +1486,22 @@ extern "C" int bwagpu_batch_cigars(bwagpu_t *h, const bwagpu_opt_t *opt, bwagpu_
 				const int wpb = tier == 0 ? 4 : 2;                 // waves per workgroup: the wide tier stays below 64 KiB of LDS per group
 				i64 nblk = (tot + wpb - 1) / wpb, cap = 256 * 6;
 				if (tier == 0) hipLaunchKernelGGL(k_cigar<true>, dim3((unsigned)(nblk < cap ? nblk : cap)), dim3(64 * wpb), (size_t)lds_wave * wpb, h->stream, h->ix, *opt, B, tot,
-								   h->d_regs_packed.as<bwagpu_alnreg_t>(), h->d_pack_read.as<i32>(), h->d_cigs.as<bwagpu_cigar_t>(), next, zc[tier], tier,
-								   h->d_cig_ext.as<u32>(), ext_used, ext_cap, h->cigar_filter ? h->d_pack_off.as<i64>() : (const i64*)nullptr);
+								   C.regs, C.reg_read, C.d_cigs->as<bwagpu_cigar_t>(), next, zc[tier], tier,
+								   C.d_ext->as<u32>(), ext_used, ext_cap, h->cigar_filter ? C.off : (const i64*)nullptr);
 				else hipLaunchKernelGGL(k_cigar<false>, dim3((unsigned)(nblk < cap ? nblk : cap)), dim3(64 * wpb), (size_t)lds_wave * wpb, h->stream, h->ix, *opt, B, tot,
-								   h->d_regs_packed.as<bwagpu_alnreg_t>(), h->d_pack_read.as<i32>(), h->d_cigs.as<bwagpu_cigar_t>(), next, zc[tier], tier,
-								   h->d_cig_ext.as<u32>(), ext_used, ext_cap, h->cigar_filter ? h->d_pack_off.as<i64>() : (const i64*)nullptr);
+								   C.regs, C.reg_read, C.d_cigs->as<bwagpu_cigar_t>(), next, zc[tier], tier,
+								   C.d_ext->as<u32>(), ext_used, ext_cap, h->cigar_filter ? C.off : (const i64*)nullptr);
 				e = hipGetLastError();
 			}
 			lap("LDS tiers");
 			if (e == hipSuccess && long_tier) {
 				unsigned long long *plan_d = h->d_ctr.as<Counters>()->cigl_plan, plan[2] = { 0, 0 };
-				if (h->d_cigl_list.ensure((size_t)tot * 4)) { bwagpu_free(res); h->err = "hipMalloc failed (cigars)"; return BWAGPU_ENOMEM; }
+				if (h->d_cigl_list.ensure((size_t)tot * 4)) { h->err = "hipMalloc failed (cigars)"; return BWAGPU_ENOMEM; }
 				e = hipMemsetAsync(plan_d, 0, sizeof plan, h->stream);
 				if (e == hipSuccess) {
 					h->phase = 43;
 					i64 nb = (tot + 255) / 256; if (nb > 2048) nb = 2048;
-					hipLaunchKernelGGL(k_cigar_long_plan, dim3((unsigned)nb), dim3(256), 0, h->stream, h->ix, *opt, tot, h->d_regs_packed.as<bwagpu_alnreg_t>(), h->d_cigs.as<bwagpu_cigar_t>(), plan_d, h->d_cigl_list.as<i32>());
+					hipLaunchKernelGGL(k_cigar_long_plan, dim3((unsigned)nb), dim3(256), 0, h->stream, h->ix, *opt, tot, C.regs, C.d_cigs->as<bwagpu_cigar_t>(), plan_d, h->d_cigl_list.as<i32>());
 					e = hipGetLastError();
 				}
 				if (e == hipSuccess) e = hipMemcpyAsync(plan, plan_d, sizeof plan, hipMemcpyDeviceToHost, h->stream);
@@ -1506,7 +1512,7 @@ extern "C" int bwagpu_batch_cigars(bwagpu_t *h, const bwagpu_opt_t *opt, bwagpu_
 					if (h->cigl_z_cap > z_cap) z_cap = h->cigl_z_cap;
 					i64 n_long = cigl_budget / z_cap; if (n_long > 1024) n_long = 1024; if (n_long > (i64)plan[0]) n_long = (i64)plan[0]; if (n_long < 1) n_long = 1;
 					if (h->d_cigl_z.ensure((size_t)z_cap * n_long) || h->d_cigl_ops.ensure((size_t)n_long * CIGL_MAX_OPS * 4) || h->d_cigl_md.ensure((size_t)n_long * CIGL_MD_CAP)) {
-						bwagpu_free(res); h->err = "hipMalloc failed (cigars)"; return BWAGPU_ENOMEM; }
+						h->err = "hipMalloc failed (cigars)"; return BWAGPU_ENOMEM; }
 					h->cigl_z_cap = z_cap;
 					if (cig_trace) fprintf(stderr, "[bwagpu] cigars: long tier: %llu regions, largest matrix %.1f MB, %lld workgroups x %.1f MB\n", plan[0], plan[1] / 1e6, (long long)n_long, z_cap / 1e6);
 					lap("long tier plan + scratch");
@@ -1514,8 +1520,8 @@ extern "C" int bwagpu_batch_cigars(bwagpu_t *h, const bwagpu_opt_t *opt, bwagpu_
 					if (e == hipSuccess) {
 						h->phase = 44;
 						hipLaunchKernelGGL(k_cigar_long, dim3((unsigned)n_long), dim3(64), (size_t)CIGL_LDS_BYTES, h->stream, h->ix, *opt, B, (i64)plan[0], h->d_cigl_list.as<i32>(),
-										   h->d_regs_packed.as<bwagpu_alnreg_t>(), h->d_pack_read.as<i32>(), h->d_cigs.as<bwagpu_cigar_t>(), next,
-										   h->d_cigl_z.as<u8>(), z_cap, h->d_cigl_ops.as<u32>(), h->d_cigl_md.as<u8>(), h->d_cig_ext.as<u32>(), ext_used, ext_cap);
+										   C.regs, C.reg_read, C.d_cigs->as<bwagpu_cigar_t>(), next,
+										   h->d_cigl_z.as<u8>(), z_cap, h->d_cigl_ops.as<u32>(), h->d_cigl_md.as<u8>(), C.d_ext->as<u32>(), ext_used, ext_cap);
 						e = hipGetLastError();
 					}
 					lap("k_cigar_long");
@@ -1534,12 +1540,34 @@ extern "C" int bwagpu_batch_cigars(bwagpu_t *h, const bwagpu_opt_t *opt, bwagpu_
 			if (e == hipSuccess) e = wait_stream(h);
 			h->stats.n_cig_dp = (i64)cc[0]; h->stats.n_cig_cells = (i64)cc[1];
 		}
-		if (e == hipSuccess) e = hipMemcpyAsync(res, h->d_cigs.p, (size_t)tot * sizeof(bwagpu_cigar_t), hipMemcpyDeviceToHost, h->stream);
+		if (e == hipSuccess && res) e = hipMemcpyAsync(res, C.d_cigs->p, (size_t)tot * sizeof(bwagpu_cigar_t), hipMemcpyDeviceToHost, h->stream);
 		(void)hipEventRecord(h->ev[2], h->stream);
 		if (e == hipSuccess) e = wait_stream(h);
-		if (e != hipSuccess) { bwagpu_free(res); h->cig_ext_n = -1; HIPCHK(h, e); }
-		(void)hipEventElapsedTime(&h->stats.ms_cigar_kernels, h->ev[0], h->ev[1]); (void)hipEventElapsedTime(&h->stats.ms_cigar_copy, h->ev[1], h->ev[2]);     // (kernels: includes the plan's small D2H and, after an overflow, the second attempt)
-		h->cig_ext_n = (i64)used < ext_cap ? (i64)used : ext_cap;
+		HIPCHK(h, e);
+		(void)hipEventElapsedTime(&ms[0], h->ev[0], h->ev[1]); (void)hipEventElapsedTime(&ms[1], h->ev[1], h->ev[2]);     // (kernels: includes the plan's small D2H and, after an overflow, the second attempt)
+		*ext_n = (i64)used < ext_cap ? (i64)used : ext_cap;
+	}
+	return BWAGPU_OK;
+}
+
+extern "C" int bwagpu_batch_cigars(bwagpu_t *h, const bwagpu_opt_t *opt, bwagpu_cigar_t **out, int64_t *n_out)
+{
+	if (!h || !opt || !h->ran || h->packed_tot < 0 || !out || !n_out) return BWAGPU_EINVAL;
+	const BusyGuard busy(h->ibuf->busy);
+	if (opt->e_del <= 0 || opt->e_ins <= 0) return BWAGPU_EINVAL;
+	HIPCHK(h, hipSetDevice(h->device));
+	const i64 tot = h->packed_tot;
+	h->phase = 40; h->cig_ext_n = -1;
+	bwagpu_cigar_t *res = (bwagpu_cigar_t*)result_alloc((size_t)(tot ? tot : 1) * sizeof(bwagpu_cigar_t));
+	if (!res) return BWAGPU_ENOMEM;
+	if (tot) {
+		const CigLists C = { tot, h->d_regs_packed.as<bwagpu_alnreg_t>(), h->d_pack_read.as<i32>(), h->d_pack_off.as<i64>(), h->d_seq.as<u8>(), h->d_off.as<i64>(), h->n_reads, h->max_len, h->n_bases,
+							 &h->d_cigs, &h->d_cig_ext };
+		i64 ext_n = -1; float ms[2] = { 0.f, 0.f };
+		const int rc = cigars_run(h, opt, C, res, &ext_n, ms);
+		if (rc != BWAGPU_OK) { bwagpu_free(res); return rc; }
+		h->stats.ms_cigar_kernels = ms[0]; h->stats.ms_cigar_copy = ms[1];
+		h->cig_ext_n = ext_n;
 	}
 	if (tot == 0) h->cig_ext_n = 0;
 	*out = res; *n_out = tot;
@@ -2041,9 +2069,11 @@ extern "C" void bwagpu_rescue_limits(int32_t out[4]) { out[0] = RESC_LANE_MAX; o
 // The kernels of both entry points on the L.n = 2 n_pairs reads of the lists L (sequences d_seq / d_seqoff): the task kernels, the replay, the packing, then -- for
 // pri / pairs -- the marking and pairing kernels on the packed merged lists.
 static int rescue_run(bwagpu_t *h, const bwagpu_opt_t *opt, const bwagpu_pestat_t pes[4], const RegLists &L, const u8 *d_seq, const i64 *d_seqoff, int32_t *counts, bwagpu_alnreg_t **regs,
-					  int32_t **src, int64_t *n_regs, bwagpu_rescue_t **rescue, bwagpu_primary_t **pri, int32_t *n_pri, bwagpu_pair_t **pairs, float *kernel_ms)
+					  int32_t **src, int64_t *n_regs, bwagpu_rescue_t **rescue, bwagpu_primary_t **pri, int32_t *n_pri, bwagpu_pair_t **pairs, float *kernel_ms,
+					  const bwagpu_opt_t *opt_count = nullptr /* the options k_rescue_count reads, where they differ from opt (sampe_run) */, float *ms_parts = nullptr /* rescue, marking, pairing */)
 {
 	const int n_reads = L.n, np = n_reads / 2;
+	if (!opt_count) opt_count = opt;
 	const i64 tot = L.tot;
 	*regs = nullptr; *src = nullptr; *n_regs = 0; *rescue = nullptr;
 	if (pri) *pri = nullptr;
@@ -2074,7 +2104,7 @@ static int rescue_run(bwagpu_t *h, const bwagpu_opt_t *opt, const bwagpu_pestat_
 		HIPCHK(h, hipMemsetAsync(D[bwagpu_s::RS_CTR].p, 0, 64, h->stream));
 		(void)hipEventRecord(h->ev[2], h->stream);
 		int nb = (np + BLOCK - 1) / BLOCK; if (nb > 8192) nb = 8192;
-		hipLaunchKernelGGL(k_rescue_count, dim3(nb), dim3(BLOCK), 0, h->stream, *opt, n_reads, L.d_cnt, L.d_off, L.d_regs, d_x, d_maxcap);
+		hipLaunchKernelGGL(k_rescue_count, dim3(nb), dim3(BLOCK), 0, h->stream, *opt_count, n_reads, L.d_cnt, L.d_off, L.d_regs, d_x, d_maxcap);
 		HIPCHK(h, hipGetLastError());
 		hipLaunchKernelGGL(k_rescue_scan, dim3(1), dim3(256), 0, h->stream, d_x, n_reads, d_toff);
 		HIPCHK(h, hipGetLastError());
@@ -2189,6 +2219,7 @@ static int rescue_run(bwagpu_t *h, const bwagpu_opt_t *opt, const bwagpu_pestat_
 	if (pairs) *pairs = res_pair.release();
 	if (n_pri) memcpy(n_pri, npri.data(), (size_t)n_reads * 4);
 	if (kernel_ms) *kernel_ms = ms_resc + ms_pri + ms_pair;
+	if (ms_parts) { ms_parts[0] = ms_resc; ms_parts[1] = ms_pri; ms_parts[2] = ms_pair; }
 	return BWAGPU_OK;
 }
 
@@ -2202,6 +2233,30 @@ extern "C" int bwagpu_batch_rescue(bwagpu_t *h, const bwagpu_opt_t *opt, const b
 	return rescue_run(h, opt, pes, lists_of_batch(h, id0), h->d_seq.as<u8>(), h->d_off.as<i64>(), counts, regs, src, n_regs, rescue, pri, n_pri, pairs, kernel_ms);
 }
 
+// What bwagpu_rescue_flat and bwagpu_sampe_flat require of the caller's reads and lists, and their upload: the sequences into RS_SEQ / RS_SEQOFF, the lists through F into L.
+// The caller holds the handle's BusyGuard and has set the device.  (`what` names the call in an error text.)
+static bool flat_pairs_ok(const bwagpu_t *h, int n_pairs, const uint8_t *seqs, const int64_t *off, const int32_t *counts_in, const bwagpu_alnreg_t *regs_in, FlatLists &F)
+{
+	const int n_reads = 2 * n_pairs;
+	for (int i = 0; i < n_reads; ++i) if (off[i + 1] < off[i] || off[i] < 0 || off[i + 1] - off[i] > 0x3fffffff) return false;
+	if (!F.scan(h, (size_t)n_reads, counts_in, regs_in, counts_in)) return false;
+	const i64 n_bases = n_reads ? off[n_reads] : 0;
+	for (i64 k = n_reads ? off[0] : 0; k < n_bases; ++k) if (seqs[k] > 4) return false;
+	return true;
+}
+static int flat_pairs_upload(bwagpu_t *h, const char *what, int n_pairs, const uint8_t *seqs, const int64_t *off, const int32_t *counts_in, const bwagpu_alnreg_t *regs_in, const int64_t *ids, FlatLists &F, RegLists &L)
+{
+	const int n_reads = 2 * n_pairs;
+	const i64 n_bases = n_reads ? off[n_reads] : 0;
+	DevBuf *D = h->d_rs;
+	if (n_reads) {      // the sequences and their offsets (the caller's arrays, in the stream ahead of the lists: upload() waits)
+		if (D[bwagpu_s::RS_SEQ].ensure((size_t)(n_bases ? n_bases : 1)) || D[bwagpu_s::RS_SEQOFF].ensure(((size_t)n_reads + 1) * 8)) { h->err = std::string("hipMalloc failed (") + what + ")"; return BWAGPU_ENOMEM; }
+		if (n_bases) HIPCHK(h, hipMemcpyAsync(D[bwagpu_s::RS_SEQ].p, seqs, (size_t)n_bases, hipMemcpyHostToDevice, h->stream));
+		HIPCHK(h, hipMemcpyAsync(D[bwagpu_s::RS_SEQOFF].p, off, ((size_t)n_reads + 1) * 8, hipMemcpyHostToDevice, h->stream));
+	}
+	return F.upload(h, what, counts_in, regs_in, ids, (size_t)n_reads, L);
+}
+
 extern "C" int bwagpu_rescue_flat(bwagpu_t *h, const bwagpu_opt_t *opt, const bwagpu_pestat_t pes[4], int n_pairs, const uint8_t *seqs, const int64_t *off, const int32_t *counts_in,
 								  const bwagpu_alnreg_t *regs_in, const int64_t *ids, int32_t *counts, bwagpu_alnreg_t **regs, int32_t **src, int64_t *n_regs, bwagpu_rescue_t **rescue,
 								  bwagpu_primary_t **pri, int32_t *n_pri, bwagpu_pair_t **pairs, float *kernel_ms)
@@ -2209,22 +2264,12 @@ extern "C" int bwagpu_rescue_flat(bwagpu_t *h, const bwagpu_opt_t *opt, const bw
 	if (!h || !opt || !pes || n_pairs < 0 || n_pairs > 0x1fffffff || !regs || !src || !n_regs || !rescue) return BWAGPU_EINVAL;
 	if (n_pairs > 0 && (!seqs || !off || !counts_in || !counts || ((pri || pairs) && !ids))) return BWAGPU_EINVAL;
 	if (opt->e_del <= 0 || opt->e_ins <= 0 || (pairs && (opt->flag & 0x800 /* MEM_F_PRIMARY5 */))) return BWAGPU_EINVAL;
-	const int n_reads = 2 * n_pairs;
-	for (int i = 0; i < n_reads; ++i) if (off[i + 1] < off[i] || off[i] < 0 || off[i + 1] - off[i] > 0x3fffffff) return BWAGPU_EINVAL;
 	FlatLists F; RegLists L;
-	if (!F.scan(h, (size_t)n_reads, counts_in, regs_in, counts_in)) return BWAGPU_EINVAL;
-	const i64 n_bases = n_reads ? off[n_reads] : 0;
-	for (i64 k = n_reads ? off[0] : 0; k < n_bases; ++k) if (seqs[k] > 4) return BWAGPU_EINVAL;
+	if (!flat_pairs_ok(h, n_pairs, seqs, off, counts_in, regs_in, F)) return BWAGPU_EINVAL;
 	const BusyGuard busy(h->ibuf->busy);
 	HIPCHK(h, hipSetDevice(h->device));
-	DevBuf *D = h->d_rs;
-	if (n_reads) {      // the sequences and their offsets (the caller's arrays, in the stream ahead of the lists: upload() waits)
-		if (D[bwagpu_s::RS_SEQ].ensure((size_t)(n_bases ? n_bases : 1)) || D[bwagpu_s::RS_SEQOFF].ensure(((size_t)n_reads + 1) * 8)) { h->err = "hipMalloc failed (rescue)"; return BWAGPU_ENOMEM; }
-		if (n_bases) HIPCHK(h, hipMemcpyAsync(D[bwagpu_s::RS_SEQ].p, seqs, (size_t)n_bases, hipMemcpyHostToDevice, h->stream));
-		HIPCHK(h, hipMemcpyAsync(D[bwagpu_s::RS_SEQOFF].p, off, ((size_t)n_reads + 1) * 8, hipMemcpyHostToDevice, h->stream));
-	}
-	const int rc = F.upload(h, "rescue", counts_in, regs_in, ids, (size_t)n_reads, L);
-	return rc != BWAGPU_OK ? rc : rescue_run(h, opt, pes, L, D[bwagpu_s::RS_SEQ].as<u8>(), D[bwagpu_s::RS_SEQOFF].as<i64>(), counts, regs, src, n_regs, rescue, pri, n_pri, pairs, kernel_ms);
+	const int rc = flat_pairs_upload(h, "rescue", n_pairs, seqs, off, counts_in, regs_in, ids, F, L);
+	return rc != BWAGPU_OK ? rc : rescue_run(h, opt, pes, L, h->d_rs[bwagpu_s::RS_SEQ].as<u8>(), h->d_rs[bwagpu_s::RS_SEQOFF].as<i64>(), counts, regs, src, n_regs, rescue, pri, n_pri, pairs, kernel_ms);
 }
 
 // ---- insert-size statistics on the device (dev_pestat.h) ------------------------------------------------------------------------------------------
@@ -2462,6 +2507,160 @@ extern "C" int bwagpu_alns_flat(bwagpu_t *h, const bwagpu_opt_t *opt, int n_read
 		I.cigs = h->d_aln_cigs.as<bwagpu_cigar_t>(); I.ops = h->d_aln_ops.as<u32>(); I.read_len = h->d_aln_len.as<i32>();
 	}
 	return alns_run(h, opt, L, pri_log_need(counts, regs, n_reads), I, alns, n_aln, pri, n_pri, kernel_ms);
+}
+
+// ---- a read pair decided on the device (dev_sampe.h) ----------------------------------------------------------------------------------------------------
+extern "C" void bwagpu_sampe_limits(int32_t out[2]) { out[0] = SAMPE_LANE_MAX; out[1] = SAMPE_STEP; }
+extern "C" int bwagpu_sampe_size(void) { return (int)sizeof(bwagpu_sampe_t); }
+
+// The kernels of both entry points on the L.n = 2 n_pairs reads of the lists L (sequences d_seq / d_seqoff, the longest of max_len bases, n_bases in all):
+// rescue_run with marking and pairing; the decision kernels on its resident records; the CIGAR kernels on the merged lists; the alignment lists from the patched
+// marking records.  Host waits: rescue_run's, cigars_run's, one for the final copies.
+static int sampe_run(bwagpu_t *h, const bwagpu_opt_t *opt, const bwagpu_pestat_t pes[4], const RegLists &L, const u8 *d_seq, const i64 *d_seqoff, int max_len, i64 n_bases, int32_t *counts,
+					 bwagpu_pe_out_t *out)
+{
+	const int n_reads = L.n, np = n_reads / 2;
+	// MEM_F_NO_RESCUE is 0x20 (bwamem.h:44); k_rescue_count reads bit 0x8 for it, so this call hands it the bit where the reference would look
+	bwagpu_opt_t oc = *opt; oc.flag = (opt->flag & ~0x8) | ((opt->flag & 0x20) ? 0x8 : 0);
+	ResultBlock<int32_t> res_npri = result_block<int32_t>((size_t)n_reads), res_naln = result_block<int32_t>((size_t)n_reads);
+	ResultBlock<bwagpu_sampe_t> res_s = result_block<bwagpu_sampe_t>((size_t)np);
+	if (!res_npri || !res_naln || !res_s) return BWAGPU_ENOMEM;
+	bwagpu_alnreg_t *regs_ = nullptr; int32_t *src_ = nullptr; int64_t mtot = 0; bwagpu_rescue_t *resc_ = nullptr; bwagpu_primary_t *pri_ = nullptr; bwagpu_pair_t *pairs_ = nullptr;
+	float ms[6] = { 0.f, 0.f, 0.f, 0.f, 0.f, 0.f };
+	const int rc = rescue_run(h, opt, pes, L, d_seq, d_seqoff, counts, &regs_, &src_, &mtot, &resc_, &pri_, res_npri.get(), &pairs_, nullptr, &oc, ms);
+	if (rc != BWAGPU_OK) return rc;
+	ResultBlock<bwagpu_alnreg_t> res_regs(regs_); ResultBlock<int32_t> res_src(src_); ResultBlock<bwagpu_rescue_t> res_resc(resc_); ResultBlock<bwagpu_primary_t> res_pri(pri_);
+	ResultBlock<bwagpu_pair_t> res_pairs(pairs_);
+	ResultBlock<bwagpu_cigar_t> res_cigs = result_block<bwagpu_cigar_t>((size_t)mtot);
+	ResultBlock<bwagpu_aln_t> res_alns = result_block<bwagpu_aln_t>((size_t)mtot);
+	ResultBlock<uint32_t> res_ops;
+	if (!res_cigs || !res_alns) return BWAGPU_ENOMEM;
+	i64 ext_n = 0;
+	if (mtot == 0) {      // no region in the whole batch: every pair prints two unmapped records (and the device arrays may not exist)
+		for (int p = 0; p < np; ++p) {
+			bwagpu_sampe_t &s = res_s[p];
+			memset(&s, 0, sizeof s);
+			s.path = 1; s.why = (opt->flag & 0x4 /* MEM_F_NOPAIRING */) ? 1 : 2; s.extra_flag = 1; s.z[0] = s.z[1] = -1; s.alt[0] = s.alt[1] = -1;
+		}
+		for (int i = 0; i < n_reads; ++i) res_naln[i] = 0;
+		res_ops = result_block<uint32_t>(0);
+		if (!res_ops) return BWAGPU_ENOMEM;
+	} else {
+		// records the host side of the marking or of the pairing computed are not in the device's copies yet
+		bool any_pri = false, any_pair = false;
+		for (i64 k = 0; k < mtot && !any_pri; ++k) any_pri = (res_pri[k].flags & 1) != 0;
+		for (int p = 0; p < np && !any_pair; ++p) any_pair = (res_pairs[p].flags & 1) != 0;
+		if (any_pri) HIPCHK(h, hipMemcpyAsync(h->d_pri_out.p, res_pri.get(), (size_t)mtot * sizeof(bwagpu_primary_t), hipMemcpyHostToDevice, h->stream));
+		if (any_pair) HIPCHK(h, hipMemcpyAsync(h->d_pair_out.p, res_pairs.get(), (size_t)np * sizeof(bwagpu_pair_t), hipMemcpyHostToDevice, h->stream));
+		DevBuf *S = h->d_sp, *D = h->d_rs;
+		if (S[bwagpu_s::SP_OUT].ensure((size_t)np * sizeof(bwagpu_sampe_t)) || S[bwagpu_s::SP_LIST].ensure((size_t)np * 4) || S[bwagpu_s::SP_CTR].ensure(sizeof(unsigned int)) ||
+			S[bwagpu_s::SP_READ].ensure((size_t)mtot * 4)) { h->err = "hipMalloc failed (sampe)"; return BWAGPU_ENOMEM; }
+		int max_cnt = 0;
+		for (int i = 0; i < n_reads; ++i) max_cnt = std::max(max_cnt, counts[i]);
+		SampeWin Wn;
+		for (int d = 0; d < 4; ++d) { Wn.low[d] = pes[d].low; Wn.high[d] = pes[d].high; Wn.failed[d] = pes[d].failed; }
+		i64 log_n = h->pri_log_dev;      // the marking's table, as the marking of this call used it
+		if (h->cfg.pri_log_cap > 0 && h->cfg.pri_log_cap < log_n) log_n = h->cfg.pri_log_cap;
+		const PriLogTab lg = { h->d_pri_log.as<double>(), (int)log_n };
+		SampeIn I;
+		I.cnt = D[bwagpu_s::RS_ACNT].as<i32>(); I.off = D[bwagpu_s::RS_POFF].as<i64>(); I.regs = D[bwagpu_s::RS_REGS].as<bwagpu_alnreg_t>();
+		I.pri = h->d_pri_out.as<bwagpu_primary_t>(); I.npri = h->d_pri_npri.as<i32>(); I.pairs = h->d_pair_out.as<bwagpu_pair_t>(); I.resc = D[bwagpu_s::RS_OUT].as<bwagpu_rescue_t>();
+		bwagpu_sampe_t *d_s = S[bwagpu_s::SP_OUT].as<bwagpu_sampe_t>();
+		i32 *list = S[bwagpu_s::SP_LIST].as<i32>();
+		unsigned int *list_n = S[bwagpu_s::SP_CTR].as<unsigned int>();
+		HIPCHK(h, hipMemsetAsync(list_n, 0, sizeof(unsigned int), h->stream));
+		(void)hipEventRecord(h->ev[3], h->stream);
+		int nb = (np + SAMPE_LANE_BLOCK - 1) / SAMPE_LANE_BLOCK; if (nb > 256 * 12) nb = 256 * 12;
+		hipLaunchKernelGGL(k_sampe_lane, dim3(nb), dim3(SAMPE_LANE_BLOCK), 0, h->stream, h->ix, *opt, Wn, lg, I, np, d_s, list, list_n);
+		HIPCHK(h, hipGetLastError());
+		if (max_cnt > SAMPE_LANE_MAX) {      // (the list's length stays on the device)
+			hipLaunchKernelGGL(k_sampe_wave, dim3(np < 256 * 16 ? np : 256 * 16), dim3(64), 0, h->stream, h->ix, *opt, Wn, lg, I, d_s, list, list_n);
+			HIPCHK(h, hipGetLastError());
+		}
+		(void)hipEventRecord(h->ev[4], h->stream);
+		nb = (n_reads + 3) / 4; if (nb > 8192) nb = 8192;
+		hipLaunchKernelGGL(k_sampe_reg_read, dim3(nb), dim3(BLOCK), 0, h->stream, n_reads, I.cnt, I.off, S[bwagpu_s::SP_READ].as<i32>());
+		HIPCHK(h, hipGetLastError());
+		HIPCHK(h, hipMemcpyAsync(res_s.get(), d_s, (size_t)np * sizeof(bwagpu_sampe_t), hipMemcpyDeviceToHost, h->stream));      // (there after cigars_run's first wait)
+		// CIGAR records of every merged region
+		const CigLists C = { mtot, I.regs, S[bwagpu_s::SP_READ].as<i32>(), I.off, d_seq, d_seqoff, n_reads, max_len, n_bases, &S[bwagpu_s::SP_CIGS], &S[bwagpu_s::SP_EXT] };
+		float msc[2] = { 0.f, 0.f };
+		const int rcc = cigars_run(h, opt, C, res_cigs.get(), &ext_n, msc);
+		if (rcc != BWAGPU_OK) return rcc;
+		ms[4] = msc[0];
+		(void)hipEventElapsedTime(&ms[3], h->ev[3], h->ev[4]);
+		res_ops = result_block<uint32_t>((size_t)ext_n);
+		if (!res_ops) return BWAGPU_ENOMEM;
+		// pairs that met a logarithm outside the table: the same statements with the host's log(), on the call's own copies; their records go back to the device
+		std::vector<i64> hoff;
+		for (int p = 0; p < np; ++p) {
+			bwagpu_sampe_t &s = res_s[p];
+			if (!(s.path == 0 && s.extra_flag == 0 && (s.flags & 2))) continue;
+			if (hoff.empty()) { hoff.resize((size_t)n_reads + 1); hoff[0] = 0; for (int i = 0; i < n_reads; ++i) hoff[(size_t)i + 1] = hoff[(size_t)i] + counts[i]; }
+			const int r0 = 2 * p, r1 = r0 + 1;
+			const i64 o0 = hoff[(size_t)r0], o1 = hoff[(size_t)r1];
+			sampe_host_pair0(*opt, res_regs.get() + o0, res_pri.get() + o0, counts[r0], res_npri[r0], res_regs.get() + o1, res_pri.get() + o1, counts[r1], res_npri[r1], res_pairs[p], s);
+			HIPCHK(h, hipMemcpyAsync(I.pri + o0, res_pri.get() + o0, (size_t)(counts[r0] + counts[r1]) * sizeof(bwagpu_primary_t), hipMemcpyHostToDevice, h->stream));
+			HIPCHK(h, hipMemcpyAsync(d_s + p, &s, sizeof s, hipMemcpyHostToDevice, h->stream));
+		}
+		// the alignment lists
+		if (h->d_aln_out.ensure((size_t)mtot * sizeof(bwagpu_aln_t)) || h->d_aln_n.ensure((size_t)n_reads * 4) || h->d_aln_list.ensure((size_t)n_reads * 4) || h->d_aln_ctr.ensure(sizeof(unsigned int))) {
+			h->err = "hipMalloc failed (sampe)"; return BWAGPU_ENOMEM;
+		}
+		AlnIn A = {}; A.pri = I.pri; A.cigs = S[bwagpu_s::SP_CIGS].as<bwagpu_cigar_t>(); A.ops = S[bwagpu_s::SP_EXT].as<u32>(); A.n_ops = ext_n; A.seq_off = d_seqoff;
+		bwagpu_aln_t *d_out = h->d_aln_out.as<bwagpu_aln_t>();
+		i32 *d_n = h->d_aln_n.as<i32>(), *alist = h->d_aln_list.as<i32>();
+		unsigned int *alist_n = h->d_aln_ctr.as<unsigned int>();
+		HIPCHK(h, hipMemsetAsync(alist_n, 0, sizeof(unsigned int), h->stream));
+		(void)hipEventRecord(h->ev[5], h->stream);
+		nb = (n_reads + ALN_LANE_BLOCK - 1) / ALN_LANE_BLOCK; if (nb > 256 * 12) nb = 256 * 12;
+		hipLaunchKernelGGL(k_alns_pe_lane, dim3(nb), dim3(ALN_LANE_BLOCK), 0, h->stream, h->ix, *opt, n_reads, I.cnt, I.off, I.regs, A, d_s, d_out, d_n, alist, alist_n);
+		HIPCHK(h, hipGetLastError());
+		if (max_cnt > ALN_LANE_MAX) {
+			hipLaunchKernelGGL(k_alns_pe_wave, dim3(n_reads < 256 * 16 ? n_reads : 256 * 16), dim3(64), 0, h->stream, h->ix, *opt, I.cnt, I.off, I.regs, A, d_s, d_out, d_n, alist, alist_n);
+			HIPCHK(h, hipGetLastError());
+		}
+		(void)hipEventRecord(h->ev[6], h->stream);
+		HIPCHK(h, hipMemcpyAsync(res_alns.get(), d_out, (size_t)mtot * sizeof(bwagpu_aln_t), hipMemcpyDeviceToHost, h->stream));
+		HIPCHK(h, hipMemcpyAsync(res_naln.get(), d_n, (size_t)n_reads * 4, hipMemcpyDeviceToHost, h->stream));
+		HIPCHK(h, hipMemcpyAsync(res_pri.get(), I.pri, (size_t)mtot * sizeof(bwagpu_primary_t), hipMemcpyDeviceToHost, h->stream));      // (as the decision kernels left them)
+		if (ext_n) HIPCHK(h, hipMemcpyAsync(res_ops.get(), S[bwagpu_s::SP_EXT].p, (size_t)ext_n * 4, hipMemcpyDeviceToHost, h->stream));
+		HIPCHK(h, wait_stream(h));
+		(void)hipEventElapsedTime(&ms[5], h->ev[5], h->ev[6]);
+		for (int p = 0; p < np; ++p) if (res_s[p].path == 1) { res_s[p].n_aa[0] = res_naln[2 * (size_t)p]; res_s[p].n_aa[1] = res_naln[2 * (size_t)p + 1]; }
+	}
+	out->regs = res_regs.release(); out->src = res_src.release(); out->n_regs = mtot; out->rescue = res_resc.release(); out->pri = res_pri.release(); out->n_pri = res_npri.release();
+	out->pairs = res_pairs.release(); out->sampe = res_s.release(); out->cigs = res_cigs.release(); out->ops = res_ops.release(); out->n_ops = ext_n; out->alns = res_alns.release();
+	out->n_aln = res_naln.release();
+	memcpy(out->kernel_ms, ms, sizeof ms);
+	return BWAGPU_OK;
+}
+
+extern "C" int bwagpu_batch_sampe(bwagpu_t *h, const bwagpu_opt_t *opt, const bwagpu_pestat_t pes[4], int64_t id0, int32_t *counts, bwagpu_pe_out_t *out)
+{
+	if (out) memset(out, 0, sizeof *out);
+	if (!h || !opt || !pes || !h->ran || !h->downloaded || !out || (h->n_reads > 0 && !counts)) return BWAGPU_EINVAL;
+	if ((h->n_reads & 1) || (id0 & 1) || opt->e_del <= 0 || opt->e_ins <= 0 || (opt->flag & 0x800 /* MEM_F_PRIMARY5 */)) return BWAGPU_EINVAL;
+	const BusyGuard busy(h->ibuf->busy);
+	HIPCHK(h, hipSetDevice(h->device));
+	return sampe_run(h, opt, pes, lists_of_batch(h, id0), h->d_seq.as<u8>(), h->d_off.as<i64>(), h->max_len, h->n_bases, counts, out);
+}
+
+extern "C" int bwagpu_sampe_flat(bwagpu_t *h, const bwagpu_opt_t *opt, const bwagpu_pestat_t pes[4], int n_pairs, const uint8_t *seqs, const int64_t *off, const int32_t *counts_in,
+								 const bwagpu_alnreg_t *regs_in, const int64_t *ids, int32_t *counts, bwagpu_pe_out_t *out)
+{
+	if (out) memset(out, 0, sizeof *out);
+	if (!h || !opt || !pes || n_pairs < 0 || n_pairs > 0x1fffffff || !out) return BWAGPU_EINVAL;
+	if (n_pairs > 0 && (!seqs || !off || !counts_in || !counts || !ids)) return BWAGPU_EINVAL;
+	if (opt->e_del <= 0 || opt->e_ins <= 0 || (opt->flag & 0x800 /* MEM_F_PRIMARY5 */)) return BWAGPU_EINVAL;
+	FlatLists F; RegLists L;
+	if (!flat_pairs_ok(h, n_pairs, seqs, off, counts_in, regs_in, F)) return BWAGPU_EINVAL;
+	int max_len = 0;
+	for (int i = 0; i < 2 * n_pairs; ++i) max_len = std::max(max_len, (int)(off[i + 1] - off[i]));
+	const BusyGuard busy(h->ibuf->busy);
+	HIPCHK(h, hipSetDevice(h->device));
+	const int rc = flat_pairs_upload(h, "sampe", n_pairs, seqs, off, counts_in, regs_in, ids, F, L);
+	return rc != BWAGPU_OK ? rc : sampe_run(h, opt, pes, L, h->d_rs[bwagpu_s::RS_SEQ].as<u8>(), h->d_rs[bwagpu_s::RS_SEQOFF].as<i64>(), max_len, n_pairs ? off[2 * n_pairs] - off[0] : 0, counts, out);
 }
 
 extern "C" int bwagpu_align_flat(bwagpu_t *h, const bwagpu_opt_t *opt, int n, const uint8_t *seqs, const int64_t *off,

@@ -382,6 +382,21 @@ static bool gen_alt(const bwagpu_opt_t &opt, const RefSeqs &ref, const Regs &av,
 	return true;
 }
 
+// For sam_pe on a pair the device has decided (bwagpu_batch_sampe: s.alns, s.pri and s.hints describe the merged list; av and dev_mapq as apply_primary leaves
+// them): the XA strings with every listed region's Aln from its record, and the Aln of place k (printed: the line's mapQ, else mem_reg2aln's).
+bool gen_alt_for_pe_recs(const bwagpu_opt_t &opt, const RefSeqs &ref, const Regs &av, const Read &s, std::vector<std::string> &xa, std::vector<char> &has, const int32_t *dev_mapq)
+{
+	return gen_alt(opt, ref, av, s.l_seq, s.seq, xa, has, s.hints, dev_mapq, &s);
+}
+Aln aln_for_pe_rec(const bwagpu_opt_t &opt, const RefSeqs &ref, const Read &s, const Regs &av, int k, bool printed, const int32_t *dev_mapq)
+{
+	const bwagpu_aln_t &r = s.alns[k];
+	if (!(r.flags & BWAGPU_ALN_NOCIGAR)) return aln_of_record(s, k, printed);
+	Aln q = reg2aln(opt, ref, s.l_seq, s.seq, &av[k], s.hints, dev_mapq[k]);      // (the device did not align the region: a hit below T, or one beyond the CIGAR kernels' limits)
+	q.flag = r.flag; q.sub = r.sub; q.mapq = printed ? r.mapq_out : r.mapq;
+	return q;
+}
+
 bool gen_alt_for_pe(const bwagpu_opt_t &opt, const RefSeqs &ref, const Regs &av, int l_query, const uint8_t *query, std::vector<std::string> &xa, std::vector<char> &has, const CigHints *hints)
 {
 	return gen_alt(opt, ref, av, l_query, query, xa, has, hints);

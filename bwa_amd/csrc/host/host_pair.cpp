@@ -283,7 +283,7 @@ int64_t host_matesw_records(const bwagpu_opt_t &opt, const RefSeqs &ref, int n, 
 	return nout;
 }
 
-std::atomic<long> g_pairs_from_device(0), g_pairs_merged_on_device(0), g_pairs_merged_aligned(0);
+std::atomic<long> g_pairs_from_device(0), g_pairs_merged_on_device(0), g_pairs_merged_aligned(0), g_pairs_from_sampe(0);
 
 // ---- pairing (mem_pair, bwamem_pair.c:208-274) --------------------------------------------------------------------------------
 static int pair_ends(const bwagpu_opt_t &opt, const RefSeqs &ref, const Pestat pes[4], const Regs a[2], int id, int *sub, int *n_sub, int z[2], const int n_pri[2])
@@ -344,6 +344,8 @@ static int pair_ends(const bwagpu_opt_t &opt, const RefSeqs &ref, const Pestat p
 
 // from host_finalize.cpp
 bool gen_alt_for_pe(const bwagpu_opt_t &opt, const RefSeqs &ref, const Regs &av, int l_query, const uint8_t *query, std::vector<std::string> &xa, std::vector<char> &has, const CigHints *hints);
+bool gen_alt_for_pe_recs(const bwagpu_opt_t &opt, const RefSeqs &ref, const Regs &av, const Read &s, std::vector<std::string> &xa, std::vector<char> &has, const int32_t *dev_mapq);
+Aln aln_for_pe_rec(const bwagpu_opt_t &opt, const RefSeqs &ref, const Read &s, const Regs &av, int k, bool printed, const int32_t *dev_mapq);
 
 static inline int raw_mapq(int diff, int a) { return (int)(6.02 * diff / a + .499); }
 
@@ -374,11 +376,11 @@ int sam_pe(const bwagpu_opt_t &opt, const RefSeqs &ref, const Pestat pes[4], uin
 	}
 	// The device's records of the pair (bwagpu_batch_pair) describe the lists as downloaded: they stand for the marking and for pair_ends when the rescue loop
 	// has aligned nothing (no hit was added), no reordering comes between the two (F_PRIMARY5) and the record is the device's own (unflagged).
+	thread_local std::vector<int32_t> mq[2];
 	const bwagpu_pair_t *dev = (merged || n == 0) && s[0].pair && s[0].pri && s[1].pri && !(opt.flag & F_PRIMARY5) && !(s[0].pair->flags & 1) ? s[0].pair : nullptr;
 	if (dev) {
-		thread_local std::vector<int32_t> mq;
 		for (int i = 0; i < 2; ++i) {
-			apply_primary(a[i], s[i].pri, (int64_t)(id << 1 | (uint64_t)i), mq);
+			apply_primary(a[i], s[i].pri, (int64_t)(id << 1 | (uint64_t)i), mq[i]);
 			n_pri[i] = 0;
 			for (size_t j = 0; j < a[i].size(); ++j) n_pri[i] += a[i][j].is_alt == 0;
 		}
@@ -386,6 +388,39 @@ int sam_pe(const bwagpu_opt_t &opt, const RefSeqs &ref, const Pestat pes[4], uin
 	} else {
 		n_pri[0] = mark_primary_se(opt, a[0], (int64_t)(id << 1 | 0));
 		n_pri[1] = mark_primary_se(opt, a[1], (int64_t)(id << 1 | 1));
+	}
+	// The device's decision of the pair (bwagpu_batch_sampe): the marking records just applied are the lists as mem_sam_pe leaves them (:335-336, :350-359), and
+	// h, g and the lists of no_pairing come from the records of the merged lists by index.  A pair the device declined runs the code below unchanged.
+	const bwagpu_sampe_t *sp = merged && dev && s[0].sampe && !(s[0].sampe->flags & 1) && s[0].alns && s[1].alns && s[0].hints && s[1].hints && s[0].hints->ops && s[1].hints->ops ? s[0].sampe : nullptr;
+	if (sp) {
+		++g_pairs_from_sampe;
+		extra_flag = sp->extra_flag;
+		if (sp->path == 0) {
+			std::vector<std::string> xa[2]; std::vector<char> has[2]; bool have[2] = {false, false};
+			if (!(opt.flag & F_ALL)) for (int i = 0; i < 2; ++i) have[i] = gen_alt_for_pe_recs(opt, ref, a[i], s[i], xa[i], has[i], mq[i].data());
+			std::vector<Aln> aa[2];
+			for (int i = 0; i < 2; ++i) {
+				const int zi = sp->z[i], gi = sp->alt[i];
+				h[i] = aln_for_pe_rec(opt, ref, s[i], a[i], zi, true, mq[i].data());
+				h[i].mapq = sp->q_se[i];
+				h[i].flag |= 0x40 << i | extra_flag;
+				if (have[i] && has[i][zi]) { h[i].has_xa = true; h[i].xa = xa[i][zi]; }
+				aa[i].push_back(h[i]);
+				if (gi >= 0) {
+					Aln g = aln_for_pe_rec(opt, ref, s[i], a[i], gi, true, mq[i].data());
+					g.flag |= 0x800 | 0x40 << i | extra_flag;
+					if (have[i] && has[i][gi]) { g.has_xa = true; g.xa = xa[i][gi]; }
+					aa[i].push_back(g);
+				}
+			}
+			for (int i = 0; i < (int)aa[0].size(); ++i) aln2sam(opt, ref, out0, s[0], aa[0], i, &h[1], rg_id);
+			for (int i = 0; i < (int)aa[1].size(); ++i) aln2sam(opt, ref, out1, s[1], aa[1], i, &h[0], rg_id);
+			return n;
+		}
+		for (int i = 0; i < 2; ++i) h[i] = sp->z[i] >= 0 ? aln_for_pe_rec(opt, ref, s[i], a[i], sp->z[i], false, mq[i].data()) : reg2aln(opt, ref, s[i].l_seq, s[i].seq, 0);
+		reg2sam(opt, ref, out0, s[0], a[0], 0x41 | extra_flag, &h[1], rg_id, mq[0].data());
+		reg2sam(opt, ref, out1, s[1], a[1], 0x81 | extra_flag, &h[0], rg_id, mq[1].data());
+		return n;
 	}
 	if (opt.flag & F_PRIMARY5) { reorder_primary5(opt.T, a[0]); reorder_primary5(opt.T, a[1]); }
 	bool no_pairing = (opt.flag & F_NOPAIRING) != 0;

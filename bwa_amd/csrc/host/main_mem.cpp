@@ -43,6 +43,7 @@ static int g_device_rescue = 0;   // BWAGPU_CLI_RESCUE=1: paired-end batches tak
 static int g_device_pestat = 0;   // BWAGPU_CLI_PESTAT=1: paired-end batches without -I take mem_pestat's windows from the device (bwagpu_batch_pestat; split over several devices: bwagpu_batch_pestat_hist per shard, summed, bwagpu_pestat_finish; same output)
 static int g_device_pair = 0;     // BWAGPU_CLI_PAIR=1: paired-end batches take the marking and mem_pair of the pairs the rescue loop leaves alone from the device (bwagpu_batch_pair; same output)
 static int g_device_primary = 0;  // BWAGPU_CLI_PRIMARY=1: single-end batches take primary/secondary marking and mapQ from the device (bwagpu_batch_primary; same output)
+static int g_device_sampe = 0;    // BWAGPU_CLI_SAMPE=1: paired-end batches without -5 take the whole of mem_sam_pe up to the text from the device (bwagpu_batch_sampe, in place of bwagpu_batch_cigars and bwagpu_batch_rescue; conditions: BWAGPU_CLI_RESCUE's, device CIGARs on; same output)
 static int g_device_alns = 0;     // BWAGPU_CLI_ALNS=1: single-end batches without -5 also take every region's alignment record and the read's list from the device (bwagpu_batch_alns, after the CIGAR call; same output)
 static std::atomic<long> g_n_alns_reads(0);      // ... reads finalized from such records
 static std::atomic<long> g_n_primary_reads(0);   // ... reads finalized from such records (the BWAGPU_CLI_TRACE line at the end of the run)
@@ -350,7 +351,9 @@ struct Sub {      // one mem_process_seqs call (bwamem.c:1235-1264) on the reads
 	bwagpu_primary_t *pri = nullptr;          // device-side marking + mapQ records of the regions, in each read's marked order (bwagpu_batch_primary; single-end, or paired-end with bwagpu_batch_pair)
 	bwagpu_aln_t *alns = nullptr;             // device-side alignment records of the regions, parallel to pri (bwagpu_batch_alns; single-end)
 	bwagpu_pair_t *pairs = nullptr;           // device-side mem_pair records of the pairs as downloaded (bwagpu_batch_pair)
-	bwagpu_alnreg_t *m_all = nullptr; int32_t *m_src = nullptr; std::vector<int32_t> m_counts; bwagpu_rescue_t *rescue = nullptr;   // bwagpu_batch_rescue: the merged lists (read i: m_counts[i] regions), one record per pair; pri / pairs then describe these lists
+	bwagpu_alnreg_t *m_all = nullptr; int32_t *m_src = nullptr; std::vector<int32_t> m_counts; bwagpu_rescue_t *rescue = nullptr;
+	bwagpu_sampe_t *sampe = nullptr; bwagpu_cigar_t *m_cigs = nullptr; uint32_t *m_ops = nullptr; bwagpu_aln_t *m_alns = nullptr;   // bwagpu_batch_sampe: the pairs' records, and CIGAR records (with their operation array) and alignment records of the merged lists
+	// bwagpu_batch_rescue: the merged lists (read i: m_counts[i] regions), one record per pair; pri / pairs then describe these lists
 	Pestat pes[4]; bool have_pes = false;     // insert-size windows, when they had to be computed before the finalize stage
 	double t_dev = 0;
 };
@@ -412,7 +415,7 @@ static void device_sub(const std::vector<bwagpu_t*> &gpus, Sub &u, const RefSeqs
 	int D = (int)gpus.size();
 	const int units = pe ? n / 2 : n, per = pe ? 2 : 1;
 	if (D > units) D = units > 0 ? units : 1;
-	struct Shard { int lo = 0, hi = 0; std::vector<int64_t> off; bwagpu_alnreg_t *all = nullptr; int64_t tot = 0; bwagpu_cigar_t *cigs = nullptr; uint32_t *ops = nullptr; int64_t n_ops = 0; bwagpu_matesw_t *msw = nullptr; int64_t n_msw = 0; bwagpu_primary_t *pri = nullptr; bwagpu_aln_t *alns = nullptr; bwagpu_pair_t *pairs = nullptr; bwagpu_alnreg_t *m_all = nullptr; int32_t *m_src = nullptr; int64_t m_tot = 0; bwagpu_rescue_t *rescue = nullptr; };
+	struct Shard { int lo = 0, hi = 0; std::vector<int64_t> off; bwagpu_alnreg_t *all = nullptr; int64_t tot = 0; bwagpu_cigar_t *cigs = nullptr; uint32_t *ops = nullptr; int64_t n_ops = 0; bwagpu_matesw_t *msw = nullptr; int64_t n_msw = 0; bwagpu_primary_t *pri = nullptr; bwagpu_aln_t *alns = nullptr; bwagpu_pair_t *pairs = nullptr; bwagpu_alnreg_t *m_all = nullptr; int32_t *m_src = nullptr; int64_t m_tot = 0; bwagpu_rescue_t *rescue = nullptr; bwagpu_pe_out_t pe = {}; };
 	std::vector<Shard> sh((size_t)D);
 	for (int d = 0; d < D; ++d) {
 		sh[d].lo = (int)((int64_t)units * d / D) * per; sh[d].hi = d + 1 == D ? n : (int)((int64_t)units * (d + 1) / D) * per;
@@ -496,7 +499,10 @@ static void device_sub(const std::vector<bwagpu_t*> &gpus, Sub &u, const RefSeqs
 		});
 		u.have_pes = true;
 	}
-	const bool have_cigs = g_device_cigars && u.tot > 0;
+	// BWAGPU_CLI_SAMPE: the whole of mem_sam_pe up to the text in one call per shard further down, CIGAR records of the merged lists included -- it stands for the CIGAR
+	// call on the download's lists too (a pair the device declines has the download's lists as its merged lists, so its records are there as well)
+	const bool dev_sampe = g_device_sampe && g_device_cigars && pe && u.have_pes && !(u.opt.flag & (F_PRIMARY5 | F_NOPAIRING)) && !(u.n_processed & 1) && u.tot > 0;
+	const bool have_cigs = g_device_cigars && u.tot > 0 && !dev_sampe;
 	if (have_cigs) on_devices([&](int d) {       // the DP of mem_reg2aln, NM and MD on the device as well; the host keeps the text
 		Shard &s = sh[d];
 		if (s.tot == 0) return;
@@ -574,7 +580,7 @@ static void device_sub(const std::vector<bwagpu_t*> &gpus, Sub &u, const RefSeqs
 	// mem_pair of the pairs as downloaded, and the marking of their ends, on the device too: the windows are known here.  Read i of the batch has id
 	// n_processed + i (mem_sam_pe: id << 1 | r with id = (n_processed + i) >> 1); a shard starts at an even read.
 	// The merge of mate-rescue hits, the marking of the merged lists and mem_pair on those records in one call, under the same conditions: it stands for both blocks below.
-	const bool dev_rescue = g_device_rescue && pe && u.have_pes && !(u.opt.flag & (F_PRIMARY5 | F_NOPAIRING)) && !(u.n_processed & 1) && u.tot > 0;
+	const bool dev_rescue = (g_device_rescue || dev_sampe) && pe && u.have_pes && !(u.opt.flag & (F_PRIMARY5 | F_NOPAIRING)) && !(u.n_processed & 1) && u.tot > 0;
 	if (dev_rescue) {
 		bwagpu_pestat_t dp[4];
 		for (int d = 0; d < 4; ++d) { memset(&dp[d], 0, sizeof dp[d]); dp[d].low = u.pes[d].low; dp[d].high = u.pes[d].high; dp[d].failed = u.pes[d].failed; dp[d].avg = u.pes[d].avg; dp[d].std = u.pes[d].std; }
@@ -582,7 +588,12 @@ static void device_sub(const std::vector<bwagpu_t*> &gpus, Sub &u, const RefSeqs
 		on_devices([&](int d) {
 			Shard &s = sh[d];
 			if (s.tot == 0) return;      // (no region: the merged lists are empty too)
-			int rc = bwagpu_batch_rescue(gpus[d], &u.opt, dp, u.n_processed + s.lo, u.m_counts.data() + s.lo, &s.m_all, &s.m_src, &s.m_tot, &s.rescue, &s.pri, nullptr, &s.pairs, nullptr);
+			int rc;
+			if (dev_sampe) {      // the same arrays and more: the pairs' decisions, CIGAR and alignment records of the merged lists
+				rc = bwagpu_batch_sampe(gpus[d], &u.opt, dp, u.n_processed + s.lo, u.m_counts.data() + s.lo, &s.pe);
+				s.m_all = s.pe.regs; s.m_src = s.pe.src; s.m_tot = s.pe.n_regs; s.rescue = s.pe.rescue; s.pri = s.pe.pri; s.pairs = s.pe.pairs;
+				bwagpu_free(s.pe.n_pri); bwagpu_free(s.pe.n_aln); s.pe.n_pri = s.pe.n_aln = nullptr;
+			} else rc = bwagpu_batch_rescue(gpus[d], &u.opt, dp, u.n_processed + s.lo, u.m_counts.data() + s.lo, &s.m_all, &s.m_src, &s.m_tot, &s.rescue, &s.pri, nullptr, &s.pairs, nullptr);
 			if (rc != BWAGPU_OK) device_fail(gpus[d], rc);
 		});
 		int64_t mt = 0; for (auto &s : sh) mt += s.m_tot;
@@ -592,6 +603,27 @@ static void device_sub(const std::vector<bwagpu_t*> &gpus, Sub &u, const RefSeqs
 		u.pairs = (bwagpu_pair_t*)malloc((size_t)(n / 2 + 1) * sizeof(bwagpu_pair_t));
 		u.rescue = (bwagpu_rescue_t*)malloc((size_t)(n / 2 + 1) * sizeof(bwagpu_rescue_t));
 		if (!u.m_all || !u.m_src || !u.pri || !u.pairs || !u.rescue) { fprintf(stderr, "[E::%s] out of memory\n", "mem_process_seqs"); exit(EXIT_FAILURE); }
+		if (dev_sampe) {
+			int64_t mo = 0; for (auto &s : sh) mo += s.pe.n_ops;
+			u.sampe = (bwagpu_sampe_t*)calloc((size_t)(n / 2 + 1), sizeof(bwagpu_sampe_t));
+			u.m_cigs = (bwagpu_cigar_t*)malloc((size_t)(mt ? mt : 1) * sizeof(bwagpu_cigar_t)); u.m_alns = (bwagpu_aln_t*)malloc((size_t)(mt ? mt : 1) * sizeof(bwagpu_aln_t));
+			u.m_ops = (uint32_t*)malloc((size_t)(mo ? mo : 1) * 4);
+			if (!u.sampe || !u.m_cigs || !u.m_alns || !u.m_ops) { fprintf(stderr, "[E::%s] out of memory\n", "mem_process_seqs"); exit(EXIT_FAILURE); }
+			int64_t km = 0, ko = 0;
+			for (auto &s : sh) {      // (a shard without regions: its pairs keep the zeroed record with flags bit 0 set below, and take the host route)
+				if (s.tot == 0) { for (int p = s.lo / 2; p < s.hi / 2; ++p) { u.sampe[p].path = -1; u.sampe[p].flags = 1; } continue; }
+				memcpy(u.sampe + s.lo / 2, s.pe.sampe, (size_t)((s.hi - s.lo) / 2) * sizeof(bwagpu_sampe_t));
+				if (s.m_tot) { memcpy(u.m_cigs + km, s.pe.cigs, (size_t)s.m_tot * sizeof(bwagpu_cigar_t)); memcpy(u.m_alns + km, s.pe.alns, (size_t)s.m_tot * sizeof(bwagpu_aln_t)); }
+				if (s.pe.n_ops) memcpy(u.m_ops + ko, s.pe.ops, (size_t)s.pe.n_ops * 4);
+				if (ko) for (int64_t i = 0; i < s.m_tot; ++i) {      // (the operation arrays are laid end to end: a shard's references move by what precedes it)
+					bwagpu_cigar_t &c = u.m_cigs[km + i];
+					if (c.n_cigar > 6) { const uint64_t at = ((uint64_t)c.cigar[1] << 32 | c.cigar[0]) + (uint64_t)ko; c.cigar[0] = (uint32_t)at; c.cigar[1] = (uint32_t)(at >> 32); }
+					if (c.n_cigar >= 0 && c.md_len > 8) c.md += (uint64_t)ko;
+				}
+				km += s.m_tot; ko += s.pe.n_ops;
+				bwagpu_free(s.pe.sampe); bwagpu_free(s.pe.cigs); bwagpu_free(s.pe.ops); bwagpu_free(s.pe.alns); s.pe.sampe = nullptr; s.pe.cigs = nullptr; s.pe.ops = nullptr; s.pe.alns = nullptr;
+			}
+		}
 		int64_t k = 0;
 		for (auto &s : sh) {      // (records name regions and anchors by indices within their read: nothing moves with the shard)
 			const size_t np = (size_t)((s.hi - s.lo) / 2);
@@ -659,14 +691,14 @@ static void finalize_sub(const RefSeqs &ref, Work &w, Sub &u, const Pestat *pes0
 {
 	const double t0 = now_s();
 	const int n = (int)u.idx.size();
-	std::vector<Read> reads((size_t)n); std::vector<CigHints> hints(u.cigs ? (size_t)n : 0);
+	std::vector<Read> reads((size_t)n); std::vector<CigHints> hints(u.cigs || u.sampe ? (size_t)n : 0);
 	std::vector<int64_t> roff((size_t)n + 1, 0);
 	for (int i = 0; i < n; ++i) roff[i + 1] = roff[i] + u.counts[i];
 	std::vector<int64_t> moff;
 	std::vector<bwagpu_cigar_t> m_cigs;      // the CIGAR records in the merged lists' order: they follow `src`; a rescued hit has none (the host aligns it)
 	if (u.rescue) {
 		moff.assign((size_t)n + 1, 0); for (int i = 0; i < n; ++i) moff[i + 1] = moff[i] + u.m_counts[i];
-		if (u.cigs) {
+		if (u.cigs && !u.sampe) {
 			m_cigs.resize((size_t)moff[n]);
 			parallel_for(u.opt.n_threads, n, [&](long i) {
 				for (int64_t k = moff[i]; k < moff[i + 1]; ++k) {
@@ -679,7 +711,8 @@ static void finalize_sub(const RefSeqs &ref, Work &w, Sub &u, const Pestat *pes0
 	parallel_for(u.opt.n_threads, n, [&](long i) {
 		const Seq &q = w.in.seqs[u.idx[i]];
 		const char *T = w.in.T(q);
-		if (u.cigs && u.rescue) { hints[i].regs = u.m_all + moff[i]; hints[i].cigs = m_cigs.data() + moff[i]; hints[i].n = u.m_counts[i]; hints[i].ops = u.cig_ops; reads[i].hints = &hints[i]; }
+		if (u.sampe) { hints[i].regs = u.m_all + moff[i]; hints[i].cigs = u.m_cigs + moff[i]; hints[i].n = u.m_counts[i]; hints[i].ops = u.m_ops; reads[i].hints = &hints[i]; reads[i].alns = u.m_alns + moff[i]; if (!(i & 1)) reads[i].sampe = u.sampe + (i >> 1); }
+		else if (u.cigs && u.rescue) { hints[i].regs = u.m_all + moff[i]; hints[i].cigs = m_cigs.data() + moff[i]; hints[i].n = u.m_counts[i]; hints[i].ops = u.cig_ops; reads[i].hints = &hints[i]; }
 		else if (u.cigs) { hints[i].regs = u.all + roff[i]; hints[i].cigs = u.cigs + roff[i]; hints[i].n = u.counts[i]; hints[i].ops = u.cig_ops; reads[i].hints = &hints[i]; }
 		reads[i].name = T + q.name;
 		reads[i].comment = copy_comment && q.has_comment ? T + q.comment : nullptr;
@@ -699,6 +732,7 @@ static void finalize_sub(const RefSeqs &ref, Work &w, Sub &u, const Pestat *pes0
 		finalize_batch(u.opt, ref, u.n_processed, n, reads.data(), u.all, roff.data(), pes, u.opt.n_threads, rg_id, sam, g_verbose >= 3);
 		for (int i = 0; i < n; ++i) w.out[u.idx[i]].swap(sam[i]);
 	}
+	if (u.sampe) { free(u.sampe); u.sampe = nullptr; free(u.m_cigs); u.m_cigs = nullptr; free(u.m_ops); u.m_ops = nullptr; free(u.m_alns); u.m_alns = nullptr; }
 	if (u.rescue) { free(u.rescue); u.rescue = nullptr; free(u.m_all); u.m_all = nullptr; free(u.m_src); u.m_src = nullptr; }
 	if (u.pairs) { free(u.pairs); u.pairs = nullptr; free(u.pri); u.pri = nullptr; }
 	if (u.alns) { g_n_alns_reads += n; bwagpu_free(u.alns); u.alns = nullptr; bwagpu_free(u.pri); u.pri = nullptr; }
@@ -970,6 +1004,7 @@ int main(int argc, char *argv[])
 	if (getenv("BWAGPU_CLI_ALNS")) g_device_alns = atoi(getenv("BWAGPU_CLI_ALNS"));
 	if (getenv("BWAGPU_CLI_PAIR")) g_device_pair = atoi(getenv("BWAGPU_CLI_PAIR"));
 	if (getenv("BWAGPU_CLI_RESCUE")) g_device_rescue = atoi(getenv("BWAGPU_CLI_RESCUE"));
+	if (getenv("BWAGPU_CLI_SAMPE")) g_device_sampe = atoi(getenv("BWAGPU_CLI_SAMPE"));
 	if (getenv("BWAGPU_CLI_PESTAT")) g_device_pestat = atoi(getenv("BWAGPU_CLI_PESTAT"));
 	int n_dev = getenv("BWAGPU_CLI_STREAMS") ? atoi(getenv("BWAGPU_CLI_STREAMS")) : 3;      // batches in flight on the device
 	if (n_dev < 1) n_dev = 1;
@@ -1174,6 +1209,7 @@ int main(int argc, char *argv[])
 	if (g_device_rescue && tl_trace && hostmem::g_pairs_merged_on_device.load() > 0)
 		fprintf(stderr, "[D::main_mem] %ld pairs merged on the device (BWAGPU_CLI_RESCUE), %ld of them with rescue alignments\n", hostmem::g_pairs_merged_on_device.load(), hostmem::g_pairs_merged_aligned.load());
 	if (g_device_pair && tl_trace) fprintf(stderr, "[D::main_mem] %ld pairs paired from device records (BWAGPU_CLI_PAIR)\n", hostmem::g_pairs_from_device.load());
+	if (g_device_sampe && tl_trace) fprintf(stderr, "[D::main_mem] %ld pairs finished from the device's pair records (BWAGPU_CLI_SAMPE)\n", hostmem::g_pairs_from_sampe.load());
 	if (g_device_alns && tl_trace) fprintf(stderr, "[D::main_mem] %ld reads finalized from device alignment records (BWAGPU_CLI_ALNS)\n", g_n_alns_reads.load());
 	if (g_device_primary && tl_trace) fprintf(stderr, "[D::main_mem] %ld reads finalized from device primary/mapQ records (BWAGPU_CLI_PRIMARY)\n", g_n_primary_reads.load());
 	if (g_verbose >= 3) { const double dt = now_s() - t_start; fprintf(stderr, "[M::%s] %ld reads in %.3f sec after the index was loaded: %.0f reads/s\n", "main_mem", n_reads_total.load(), dt, dt > 0 ? n_reads_total.load() / dt : 0.);

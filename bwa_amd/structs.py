@@ -56,6 +56,16 @@ assert PESTAT_DTYPE.itemsize == 32 and PAIR_DTYPE.itemsize == 32
 # bwagpu_rescue_t: what the merge of mate-rescue hits did with one pair (bwagpu_batch_rescue / bwagpu_rescue_flat)
 RESCUE_DTYPE = np.dtype([("n_aligned", "<i4"), ("n_inline", "<i4"), ("flags", "<i4"), ("pad_", "<i4")])
 assert RESCUE_DTYPE.itemsize == 16
+# bwagpu_sampe_t: a read pair as mem_sam_pe decides it (bwagpu_batch_sampe / bwagpu_sampe_flat); PeOut: bwagpu_pe_out_t, what those calls return
+SAMPE_DTYPE = np.dtype([("path", "<i4"), ("why", "<i4"), ("extra_flag", "<i4"), ("z", "<i4", (2,)), ("q_se", "<i4", (2,)), ("alt", "<i4", (2,)), ("n_aa", "<i4", (2,)),
+                        ("q_pe", "<i4"), ("paired", "<i4"), ("flags", "<i4"), ("pad_", "<i4", (2,))])
+assert SAMPE_DTYPE.itemsize == 64
+
+
+class PeOut(C.Structure):
+    _fields_ = [("regs", C.c_void_p), ("src", C.c_void_p), ("n_regs", C.c_int64), ("rescue", C.c_void_p), ("pri", C.c_void_p), ("n_pri", C.c_void_p), ("pairs", C.c_void_p),
+                ("sampe", C.c_void_p), ("cigs", C.c_void_p), ("ops", C.c_void_p), ("n_ops", C.c_int64), ("alns", C.c_void_p), ("n_aln", C.c_void_p), ("kernel_ms", C.c_float * 6)]
+
 
 INTV_DTYPE = np.dtype([("x0", "<u8"), ("x1", "<u8"), ("x2", "<u8"), ("info", "<u8")])
 SEED_DTYPE = np.dtype([("rbeg", "<i8"), ("qbeg", "<i4"), ("len", "<i4"), ("score", "<i4"), ("_pad", "<i4")])

@@ -432,6 +432,53 @@ int bwagpu_alns_flat(bwagpu_t *h, const bwagpu_opt_t *opt, int n_reads, const in
 void bwagpu_alns_limits(int32_t out[2]);
 int  bwagpu_aln_size(void);   /* sizeof(bwagpu_aln_t) as compiled */
 
+/* A read pair decided on the device: everything mem_sam_pe (bwamem_pair.c:276-419) does behind mem_pair except the text.  The merge of the mate-rescue hits,
+ * the marking and the pairing are bwagpu_batch_rescue's; then one record per pair says which of the two ways out the pair takes and what it prints, the marking
+ * records are patched as mem_sam_pe patches the lists (:335-336, :350-359), every merged region gets its CIGAR record (bwagpu_batch_cigars' kernels) and its
+ * bwagpu_aln_t.  What is left to the caller is the CIGAR / MD / XA text and mem_aln2sam. */
+typedef struct {
+	int32_t path;           /* 0: printed by :311-394 (the pair is taken from the lists by z / alt); 1: by no_pairing, :397-418 (two mem_reg2sam lists); -1: not decided (flags bit 0) */
+	int32_t why;            /* path 1: the reason, in the reference's order of evaluation -- 1: MEM_F_NOPAIRING; 2: an end has n_pri == 0; 4: mem_pair returned <= 0;
+	                         * 8 / 16: is_multi[0] / is_multi[1] (these two may come together; a later reason is not looked for once an earlier one holds) */
+	int32_t extra_flag;     /* 1 or 3: the reference's variable on either path */
+	int32_t z[2];           /* path 0: place of h[i] in end i's marked list (0 where the unpaired alignment is preferred, :346); path 1: `which` of :399-404, -1: the unmapped record */
+	int32_t q_se[2];        /* path 0: h[i].mapq as :337-348 leave it; path 1: mem_reg2aln's mapq of `which` (0: unmapped) -- what the mate's MQ tag prints */
+	int32_t alt[2];         /* path 0: place of g[i] (n_pri[i]) where :371-377 print it, else -1; path 1: -1 */
+	int32_t n_aa[2];        /* lines the end prints.  path 0: 1 or 2; path 1: aa.n of mem_reg2sam's loop, 0 = the unmapped line */
+	int32_t q_pe;           /* after :329; 0 on path 1 */
+	int32_t paired;         /* path 0: 1 where o > score_un (:331) */
+	int32_t flags;          /* bit 0: bwagpu_batch_rescue declined the pair (its flags & 1): every other field but path is zero, the caller runs mem_sam_pe itself on the download's lists;
+	                         * bit 1: the host side of the call computed this record or the pair record it was made from (a logarithm outside the handle's table, a distance outside the pairing table); it is right either way */
+	int32_t pad_[2];        /* zero */
+} bwagpu_sampe_t;          /* 64 bytes */
+/* What the two calls below return.  Every array is freed with bwagpu_free; after a failure all of them are NULL. */
+typedef struct {
+	bwagpu_alnreg_t *regs; int32_t *src; int64_t n_regs;   /* the merged lists, as bwagpu_batch_rescue returns them */
+	bwagpu_rescue_t *rescue;                                /* n / 2 */
+	bwagpu_primary_t *pri;                                  /* n_regs marking records of the merged lists AS mem_sam_pe LEAVES THE LISTS: bwagpu_batch_rescue's except for the chosen hit's
+	                                                         * sub, secondary = -2 and mapq (recomputed from the new sub) where :335-336 fired, and the switched group's secondary_all (:350-359) */
+	int32_t *n_pri;                                         /* n */
+	bwagpu_pair_t *pairs;                                   /* n / 2 */
+	bwagpu_sampe_t *sampe;                                  /* n / 2 */
+	bwagpu_cigar_t *cigs;                                   /* one per merged region, in the merged lists' order */
+	uint32_t *ops; int64_t n_ops;                           /* the operation array of cigs */
+	bwagpu_aln_t *alns;                                     /* one per merged region, in marked order.  An end of a path-1 pair: as bwagpu_batch_alns (the caller ORs 0x40 << i | extra_flag).  An end of a
+	                                                         * path-0 pair: sel = 0 at place z[i] with mapq_out = q_se[i], sel = 1 and flag |= 0x800 at alt[i], sel = -1 elsewhere; sub as mem_reg2aln leaves it */
+	int32_t *n_aln;                                         /* n: lines per read (= sampe's n_aa) */
+	float kernel_ms[6];                                     /* device time (HIP events, summed per segment) of rescue, marking, pairing, decision, CIGAR and alignment-list kernels.  [4] is what bwagpu_batch_cigars reports as ms_cigar_kernels:
+	                                                         * one span over its tiers, which contains the long tier's sizing copy with its host wait and, after an overflow of the operation array, the second attempt */
+} bwagpu_pe_out_t;
+/* After bwagpu_batch_download of a batch whose reads 2p, 2p + 1 are mates (read i has id id0 + i, id0 even); needs no bwagpu_batch_cigars call and leaves the records of an earlier
+ * one (and what bwagpu_batch_alns makes of them) alone.  counts[i]: the length of read i's merged list.  BWAGPU_EINVAL: bwagpu_batch_rescue's cases, MEM_F_PRIMARY5 in opt->flag, a NULL out.
+ * MEM_F_NO_RESCUE in opt->flag (bwamem.h:44) is honoured as the reference honours it: the lists pass unchanged. */
+int  bwagpu_batch_sampe(bwagpu_t *h, const bwagpu_opt_t *opt, const bwagpu_pestat_t pes[4], int64_t id0, int32_t *counts, bwagpu_pe_out_t *out);
+/* The same kernels on reads and lists of the caller: the inputs of bwagpu_rescue_flat, ids required. */
+int  bwagpu_sampe_flat(bwagpu_t *h, const bwagpu_opt_t *opt, const bwagpu_pestat_t pes[4], int n_pairs, const uint8_t *seqs, const int64_t *off,
+		const int32_t *counts_in, const bwagpu_alnreg_t *regs_in, const int64_t *ids, int32_t *counts, bwagpu_pe_out_t *out);
+/* out[0] regions of a pair's longer list up to which one lane decides the pair (the marking kernel's value), out[1] places a wavefront takes per step */
+void bwagpu_sampe_limits(int32_t out[2]);
+int  bwagpu_sampe_size(void);   /* sizeof(bwagpu_sampe_t) as compiled */
+
 /* ---- index construction on the device -------------------------------------------------------- */
 /* The arrays `bwa index` leaves in bwt_t after bwt_bwtgen2/bwt_pac2bwt + bwt_bwtupdate_core + bwt_cal_sa
  * (bwtindex.c:64-120, 150-172; bwt.c:62-84), built from the 2-bit packed forward strand by a suffix sort in HBM
