@@ -16,7 +16,7 @@ try:   # torch bundles its own HIP runtime (libamdhip64); loading it first keeps
 except Exception:  # pragma: no cover
     torch = None
 
-from .structs import ALN_DTYPE, ALNREG_DTYPE, PAIR_DTYPE, PESTAT_DTYPE, PESTAT_INFO_DTYPE, PRIMARY_DTYPE, RESCUE_DTYPE, SAMPE_DTYPE, MemOpt, PeOut
+from .structs import ALN_DTYPE, ALNREG_DTYPE, PAIR_DTYPE, PESTAT_DTYPE, PESTAT_INFO_DTYPE, PRIMARY_DTYPE, RESCUE_DTYPE, SAMPE_DTYPE, MemOpt, PeOut, SamIn, SamOut
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 DEFAULT_LIB = os.path.join(HERE, "csrc", "libbwagpu.so")
@@ -64,6 +64,7 @@ EXPORTS = [
     "bwagpu_batch_pestat", "bwagpu_pestat_flat", "bwagpu_batch_pestat_hist", "bwagpu_pestat_finish", "bwagpu_pestat_limits",
     "bwagpu_batch_alns", "bwagpu_alns_flat", "bwagpu_alns_limits", "bwagpu_aln_size",
     "bwagpu_batch_sampe", "bwagpu_sampe_flat", "bwagpu_sampe_limits", "bwagpu_sampe_size",
+    "bwagpu_set_contig_names", "bwagpu_batch_sam", "bwagpu_sam_flat", "bwagpu_sam_limits",
     "bwagpu_trim", "bwagpu_set_option", "bwagpu_get_option", "bwagpu_set_default_option", "bwagpu_clear_default_options", "bwagpu_option_name",
 ]
 
@@ -132,6 +133,10 @@ def load_library(path: str | None = None) -> C.CDLL:
     L.bwagpu_batch_sampe.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
     L.bwagpu_sampe_flat.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 7
     L.bwagpu_sampe_limits.restype = None
+    L.bwagpu_set_contig_names.argtypes = [C.c_void_p] * 5
+    L.bwagpu_batch_sam.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+    L.bwagpu_sam_flat.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 7 + [C.c_int64, C.c_void_p, C.c_void_p]
+    L.bwagpu_sam_limits.restype = None
     L.bwagpu_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_longlong]
     L.bwagpu_get_option.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p]
     L.bwagpu_set_default_option.argtypes = [C.c_char_p, C.c_longlong]
@@ -146,6 +151,14 @@ def option_names(L: C.CDLL) -> list:
     while L.bwagpu_option_name(i, C.byref(p)) == 0:
         out.append(p.value.decode()); i += 1
     return out
+
+
+def _ragged_bytes(items):
+    """(the items back to back, int64 offsets[len + 1])"""
+    off = np.zeros(len(items) + 1, dtype=np.int64)
+    if items:
+        off[1:] = np.cumsum([len(x) for x in items])
+    return b"".join(items), off
 
 
 import threading
@@ -347,6 +360,58 @@ class BwaGpu:
         out = (C.c_int32 * 2)()
         self.L.bwagpu_alns_limits(out)
         return dict(zip(("lane_max", "step"), list(out)))
+
+    # -- SAM text on the device (single-end) ------------------------------------------------------------------
+    def set_contig_names(self, names, annos=None):
+        """bwagpu_set_contig_names: the contigs' names (and annotations) of a handle that was not created from index files; str or bytes, one per contig."""
+        enc = lambda xs: [x.encode() if isinstance(x, str) else bytes(x) for x in xs]
+        nb, no = _ragged_bytes(enc(names))
+        ab, ao = _ragged_bytes(enc(annos)) if annos is not None else (None, None)
+        self._chk(self.L.bwagpu_set_contig_names(self.h, nb, no.ctypes.data, ab, None if ao is None else ao.ctypes.data))
+
+    def _sam_call(self, n, names, quals, comments, rg_id, extra_flag, call):
+        enc = lambda xs: [x.encode() if isinstance(x, str) else bytes(x) for x in xs]
+        nb, no = _ragged_bytes(enc(names))
+        assert no.shape[0] == n + 1
+        cb, co = _ragged_bytes(enc(comments)) if comments is not None else (None, None)
+        keep = (nb, no, cb, co, quals, rg_id.encode() if isinstance(rg_id, str) else rg_id)
+        sin = SamIn(C.cast(C.c_char_p(nb), C.c_void_p), no.ctypes.data, C.cast(C.c_char_p(quals), C.c_void_p) if quals is not None else None,
+                    C.cast(C.c_char_p(cb), C.c_void_p) if cb is not None else None, co.ctypes.data if co is not None else None, keep[5], int(extra_flag))
+        out = SamOut()
+        self._chk(call(C.byref(sin), C.byref(out)))
+        text = C.string_at(out.text, out.n_text)
+        self.L.bwagpu_free(out.text)
+        res = dict(text=text, off=self._take(out.off, n + 1, np.dtype("<i8")), flags=self._take(out.flags, n, np.dtype("<i4")),
+                   n_lines=self._take(out.n_lines, n, np.dtype("<i4")), n_declined=int(out.n_declined), kernel_ms=tuple(out.kernel_ms))
+        del keep
+        return res
+
+    def sam(self, opt: MemOpt, id0, names, quals=None, comments=None, rg_id=None, extra_flag=0):
+        """bwagpu_batch_sam: after download() and cigars(), the SAM text of every read of the batch, written on the device; read i has id id0 + i and the name
+        names[i].  quals: bytes, one per base in the reads' order, or None ('*'); comments: one per read ('' prints nothing) or None.
+        -> dict(text: bytes, off int64[n + 1]: read i's lines are text[off[i]:off[i + 1]], flags int32[n]: bit 0 = declined (no bytes, the caller formats the
+        read), n_lines int32[n], n_declined, kernel_ms: (marking + alignment lists, sizing + prefix sum, writing))"""
+        return self._sam_call(self._n, names, quals, comments, rg_id, extra_flag, lambda i, o: self.L.bwagpu_batch_sam(self.h, C.byref(opt), int(id0), i, o))
+
+    def sam_flat(self, opt: MemOpt, seqs, off, counts, regs, ids, cigs, ops, names, quals=None, comments=None, rg_id=None, extra_flag=0):
+        """bwagpu_sam_flat: the same kernels on reads (nt4 with n + 1 offsets), unmarked lists, ids, CIGAR records and operation array of the caller -> as sam()."""
+        seqs = np.ascontiguousarray(seqs, dtype=np.uint8)
+        off = np.ascontiguousarray(off, dtype=np.int64)
+        counts = np.ascontiguousarray(counts, dtype=np.int32)
+        regs = np.ascontiguousarray(regs, dtype=ALNREG_DTYPE)
+        ids = np.ascontiguousarray(ids, dtype=np.int64)
+        cigs = np.ascontiguousarray(cigs, dtype=CIGAR_DTYPE)
+        ops = np.ascontiguousarray(ops, dtype=np.uint32)
+        assert counts.shape == ids.shape == (off.shape[0] - 1,) and int(counts.sum()) == regs.shape[0] == cigs.shape[0]
+        return self._sam_call(counts.shape[0], names, quals, comments, rg_id, extra_flag,
+                              lambda i, o: self.L.bwagpu_sam_flat(self.h, C.byref(opt), counts.shape[0], seqs.ctypes.data, off.ctypes.data, counts.ctypes.data, regs.ctypes.data,
+                                                                  ids.ctypes.data, cigs.ctypes.data, ops.ctypes.data if ops.shape[0] else None, ops.shape[0], i, o))
+
+    def sam_limits(self) -> dict:
+        """bwagpu_sam_limits: bytes of a wavefront's staging area (a longer line is flushed in its middle), places of a marked list it takes per step."""
+        out = (C.c_int32 * 2)()
+        self.L.bwagpu_sam_limits(out)
+        return dict(zip(("staging", "step"), list(out)))
 
     def pair(self, opt: MemOpt, pes: np.ndarray, id0: int = 0):
         """bwagpu_batch_pair: marking, then mem_pair of every pair (reads 2p, 2p + 1) of the last download() on the device; pes = PESTAT_DTYPE[4], read i has

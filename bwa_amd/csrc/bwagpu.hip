@@ -45,6 +45,7 @@
 #include "dev_pestat.h"
 #include "dev_alns.h"
 #include "dev_sampe.h"
+#include "dev_samtext.h"
 #include "dev_debug.h"
 
 #define BWAGPU_VERSION "bwagpu 0.1 (gfx950)"
@@ -84,6 +85,9 @@ struct bwagpu_s {
 		// cloned handle should not have to learn them again); written and read under `m`
 		std::mutex m; double need_slot = 0, need_node = 0, need_reg = 0; int need_mem = 0;
 		long batches = 0, mem_events = 0;      // batches run on this index; those that had to be redone with longer interval lists (see the end of bwagpu_batch_run)
+		// contig names and annotations (bwagpu_set_contig_names; from .ann): one blob, names first, and n_seqs + 1 offsets into it for either; the same in HBM
+		// (offsets: names', then annotations').  Set before the handles on this index format text.
+		std::string ctg_text; std::vector<i64> ctg_name_off, ctg_anno_off; DevBuf d_ctg_text, d_ctg_toff; bool have_names = false;
 	};
 	IndexBufs *ibuf = nullptr;      // shared by bwagpu_clone()d handles
 	i64 l_pac = 0; int n_seqs = 0; u64 seq_len = 0; int sa_intv = 0;
@@ -103,6 +107,8 @@ struct bwagpu_s {
 	std::vector<double> pair_tab; bwagpu_pestat_t pair_tab_pes[4] = {}; i64 pair_tab_cap = -1; i32 pair_toff[4] = {}, pair_tlen[4] = {}; bool pair_tab_dev = false;   // the table as last filled: for these windows and this capacity; resident in d_pair_tab
 	DevBuf d_pst_hist, d_pst_out;                                                         // bwagpu_batch_pestat and its kin (dev_pestat.h): the histogram of insert sizes, four windows and the info record (PstOut) -- resident for the next device-side consumer
 	DevBuf d_aln_out, d_aln_n, d_aln_list, d_aln_ctr, d_aln_cigs, d_aln_ops, d_aln_len;                  // bwagpu_batch_alns / bwagpu_alns_flat (dev_alns.h): records, aa.n per read, the wavefront form's read list and its length; bwagpu_alns_flat's CIGAR records, operation array and read lengths
+	enum { ST_NAMES, ST_NAMEOFF, ST_QUAL, ST_COMM, ST_COMMOFF, ST_RG, ST_SEQ, ST_SEQOFF, ST_SIZE, ST_TOFF, ST_FLAGS, ST_LINES, ST_TEXT, ST_N };
+	DevBuf d_st[ST_N];      // bwagpu_batch_sam / bwagpu_sam_flat (dev_samtext.h): the reads' names, qualities, comments with their offsets, -R's id, bwagpu_sam_flat's reads; bytes per read, their prefix sums, flag words, lines per read, the text
 	DevBuf d_pf_regs, d_pf_cnt, d_pf_off, d_pf_ids;                                       // ... and the uploaded lists of the *_flat calls (FlatLists)
 	std::vector<double> pri_log; i64 pri_log_dev = 0;                                      // log((double)k) by the host's libm for k < size; entries resident in d_pri_log
 	DevBuf d_msw_tasks, d_msw_out, d_msw_pes, d_msw_scratch;
@@ -509,7 +515,7 @@ extern "C" void bwagpu_destroy(bwagpu_t *h)
 	struct LastOut { ~LastOut() { if (--g_live_handles == 0) g_results.trim(); } } last_out;      // (after the handle's own buffers are gone)
 	for (void *&p_ : h->reserved) { if (p_) bwagpu_free(p_); p_ = nullptr; }
 	if (h->ibuf && --h->ibuf->refs == 0) {
-		DevBuf *ib[] = { &h->ibuf->d_bwt, &h->ibuf->d_sa, &h->ibuf->d_pac, &h->ibuf->d_ctg_off, &h->ibuf->d_ctg_len, &h->ibuf->d_ctg_alt, &h->ibuf->d_ptab, &h->ibuf->d_occ32, &h->ibuf->d_occ_sb };
+		DevBuf *ib[] = { &h->ibuf->d_bwt, &h->ibuf->d_sa, &h->ibuf->d_pac, &h->ibuf->d_ctg_off, &h->ibuf->d_ctg_len, &h->ibuf->d_ctg_alt, &h->ibuf->d_ptab, &h->ibuf->d_occ32, &h->ibuf->d_occ_sb, &h->ibuf->d_ctg_text, &h->ibuf->d_ctg_toff };
 		for (DevBuf *b : ib) b->release();
 		delete h->ibuf;
 	}
@@ -519,6 +525,7 @@ extern "C" void bwagpu_destroy(bwagpu_t *h)
 	for (DevBuf *b : all) b->release();
 	for (DevBuf &b : h->d_rs) b.release();
 	for (DevBuf &b : h->d_sp) b.release();
+	for (DevBuf &b : h->d_st) b.release();
 	for (int i = 0; i < 8; ++i) if (h->ev[i]) (void)hipEventDestroy(h->ev[i]);
 	if (h->ev_wait) (void)hipEventDestroy(h->ev_wait);
 	if (h->stream) (void)hipStreamDestroy(h->stream);
@@ -564,12 +571,14 @@ extern "C" int bwagpu_create_from_files(bwagpu_t **out, const char *prefix, int 
 	long long xx; int n_seqs; unsigned seed;
 	if (fscanf(fa, "%lld%d%u", &xx, &n_seqs, &seed) != 3 || n_seqs <= 0) { fclose(fa); return BWAGPU_EIO; }
 	d.l_pac = xx; d.n_seqs = n_seqs;
-	std::vector<i64> coff(n_seqs); std::vector<i32> clen(n_seqs), calt(n_seqs, 0); std::vector<std::string> names(n_seqs);
+	std::vector<i64> coff(n_seqs); std::vector<i32> clen(n_seqs), calt(n_seqs, 0); std::vector<std::string> names(n_seqs), annos(n_seqs);
 	for (int i = 0; i < n_seqs; ++i) {
 		char name[8192]; unsigned gi; int c, n_ambs, len;
 		if (fscanf(fa, "%u%8191s", &gi, name) != 2) { fclose(fa); return BWAGPU_EIO; }
 		names[i] = name;
-		while ((c = fgetc(fa)) != '\n' && c != EOF) {}
+		std::string rest;
+		while ((c = fgetc(fa)) != '\n' && c != EOF) if (rest.size() < 8190) rest += (char)c;
+		if (rest.size() > 1 && rest != " (null)") annos[i] = rest.substr(1);      // bntseq.c:128-129
 		if (fscanf(fa, "%lld%d%d", &xx, &len, &n_ambs) != 3) { fclose(fa); return BWAGPU_EIO; }
 		coff[i] = xx; clen[i] = len;
 	}
@@ -588,7 +597,42 @@ extern "C" int bwagpu_create_from_files(bwagpu_t **out, const char *prefix, int 
 	if ((i64)fp.size() < d.l_pac / 4 + 1) return BWAGPU_EIO;
 	d.pac = (const u8*)fp.data();
 	d.ctg_offset = coff.data(); d.ctg_len = clen.data(); d.ctg_is_alt = calt.data();
-	return bwagpu_create(out, &d, device);
+	const int rc = bwagpu_create(out, &d, device);
+	if (rc != BWAGPU_OK) return rc;
+	std::string nb, ab; std::vector<i64> no(1, 0), ao(1, 0);
+	for (int i = 0; i < n_seqs; ++i) { nb += names[i]; no.push_back((i64)nb.size()); ab += annos[i]; ao.push_back((i64)ab.size()); }
+	const int rn = bwagpu_set_contig_names(*out, nb.data(), no.data(), ab.data(), ao.data());
+	if (rn != BWAGPU_OK) { bwagpu_destroy(*out); *out = nullptr; }
+	return rn;
+}
+
+// The host's copy of the contigs' names and annotations into h's HBM (h->ibuf->m is held)
+static int ctg_names_upload(bwagpu_t *h)
+{
+	bwagpu_s::IndexBufs &B = *h->ibuf;
+	std::vector<i64> toff(B.ctg_name_off);
+	toff.insert(toff.end(), B.ctg_anno_off.begin(), B.ctg_anno_off.end());
+	if (int rc = upload(h, B.d_ctg_text, B.ctg_text.data(), B.ctg_text.size())) return rc;
+	return upload(h, B.d_ctg_toff, toff.data(), toff.size() * 8);
+}
+
+extern "C" int bwagpu_set_contig_names(bwagpu_t *h, const char *names, const int64_t *name_off, const char *annos, const int64_t *anno_off)
+{
+	if (!h || !names || !name_off || (annos && !anno_off)) return BWAGPU_EINVAL;
+	const int n = h->n_seqs;
+	for (int i = 0; i < n; ++i)
+		if (name_off[0] < 0 || name_off[i] > name_off[i + 1] || (annos && (anno_off[0] < 0 || anno_off[i] > anno_off[i + 1]))) { h->err = "bwagpu_set_contig_names: offsets that do not ascend"; return BWAGPU_EINVAL; }
+	HIPCHK(h, hipSetDevice(h->device));
+	bwagpu_s::IndexBufs &B = *h->ibuf;
+	std::lock_guard<std::mutex> l(B.m);
+	B.ctg_text.assign(names + name_off[0], names + name_off[n]);
+	B.ctg_name_off.resize((size_t)n + 1); B.ctg_anno_off.resize((size_t)n + 1);
+	const i64 nn = (i64)B.ctg_text.size();
+	for (int i = 0; i <= n; ++i) { B.ctg_name_off[i] = name_off[i] - name_off[0]; B.ctg_anno_off[i] = nn + (annos ? anno_off[i] - anno_off[0] : 0); }
+	if (annos) B.ctg_text.append(annos + anno_off[0], annos + anno_off[n]);
+	const int rc = ctg_names_upload(h);
+	B.have_names = rc == BWAGPU_OK;
+	return rc;
 }
 
 // A second handle on the same device that shares the index already resident in HBM (no copy) but has its own stream and
@@ -651,6 +695,15 @@ static int clone_to_device_impl(bwagpu_t *src, int device, bwagpu_t **out)
 	h->bwt_size = src->bwt_size; h->n_sa = src->n_sa;
 	h->h_ctg_off = src->h_ctg_off; h->h_ctg_len = src->h_ctg_len; h->h_ctg_alt = src->h_ctg_alt;
 	h->stats_on = src->stats_on; h->taps_on = src->taps_on; h->cigar_filter = src->cigar_filter;
+	{
+		std::lock_guard<std::mutex> ls(src->ibuf->m);
+		if (src->ibuf->have_names) {
+			std::lock_guard<std::mutex> ld(h->ibuf->m);
+			h->ibuf->ctg_text = src->ibuf->ctg_text; h->ibuf->ctg_name_off = src->ibuf->ctg_name_off; h->ibuf->ctg_anno_off = src->ibuf->ctg_anno_off;
+			if (int rc = ctg_names_upload(h)) { bwagpu_destroy(h); return rc; }
+			h->ibuf->have_names = true;
+		}
+	}
 	*out = h;
 	return BWAGPU_OK;
 }
@@ -1745,16 +1798,22 @@ extern "C" int bwagpu_batch_matesw(bwagpu_t *h, const bwagpu_opt_t *opt, const b
 extern "C" void bwagpu_primary_limits(int32_t out[4]) { out[0] = PRI_LANE_MAX; out[1] = PRI_LDS_SMALL; out[2] = PRI_LDS_BIG; out[3] = PRI_SCAN; }
 
 static const i64 PRI_LOG_MAX = (i64)1 << 22;      // entries the table of logarithms is grown to at most (32 MB); arguments beyond it are the host's
+// the marking records whose mapQ needs the host's logarithm (flags bit 0), counted: a caller that leaves the records on the device asks this instead of reading them
+__global__ void __launch_bounds__(256) k_primary_misses(const bwagpu_primary_t *recs, i64 tot, unsigned int *n_miss)
+{
+	for (i64 k = (i64)blockIdx.x * blockDim.x + threadIdx.x; k < tot; k += (i64)gridDim.x * blockDim.x) if (recs[k].flags & 1) atomicAdd(n_miss, 1u);
+}
 // The kernels of both entry points on the lists L (its largest count sizes the HBM form): records to a result block (*out), return values to n_pri.
-// log_need = the largest argument of a logarithm to expect.
-static int primary_run(bwagpu_t *h, const bwagpu_opt_t *opt, RegLists L, i64 log_need, bwagpu_primary_t **out, int32_t *n_pri, float *kernel_ms)
+// log_need = the largest argument of a logarithm to expect.  resident: the records are wanted in d_pri_out only (out may be null) -- they come to the host
+// only if one of them needs the host's logarithm (k_primary_misses counts those), and go back completed.
+static int primary_run(bwagpu_t *h, const bwagpu_opt_t *opt, RegLists L, i64 log_need, bwagpu_primary_t **out, int32_t *n_pri, float *kernel_ms, bool resident = false)
 {
 	const int n_reads = L.n, max_cnt = L.max_cnt;
 	const i64 tot = L.tot;
 	if (kernel_ms) *kernel_ms = 0.f;
-	ResultBlock<bwagpu_primary_t> res = result_block<bwagpu_primary_t>((size_t)tot);
+	ResultBlock<bwagpu_primary_t> res = result_block<bwagpu_primary_t>(resident ? 0 : (size_t)tot);
 	if (!res) return BWAGPU_ENOMEM;
-	if (n_reads == 0) { *out = res.release(); return BWAGPU_OK; }
+	if (n_reads == 0) { if (out) *out = res.release(); return BWAGPU_OK; }
 	// the table of logarithms: the host's log() of every integer a mapQ of this batch can ask for (option pri_log_cap: a table of exactly that many entries, for tests)
 	i64 log_n = log_need + 1 < 4096 ? 4096 : log_need + 1;
 	if (log_n > PRI_LOG_MAX) log_n = PRI_LOG_MAX;
@@ -1794,15 +1853,28 @@ static int primary_run(bwagpu_t *h, const bwagpu_opt_t *opt, RegLists L, i64 log
 		hipLaunchKernelGGL(k_primary_wave<0>, dim3(n_hbm), dim3(64), 0, h->stream, *opt, L.d_cnt, L.d_off, L.d_regs, L.d_ids, L.id0, lg, d_out, d_npri, lists + (size_t)2 * n_reads, list_n + 2, h->d_pri_scratch.as<u64>(), max_cnt);
 		e = hipGetLastError();
 	}
+	if (e == hipSuccess && resident && tot) {      // (list_n[3]: no list of the wavefront forms)
+		hipLaunchKernelGGL(k_primary_misses, dim3((unsigned)((tot + 255) / 256 < 1024 ? (tot + 255) / 256 : 1024)), dim3(256), 0, h->stream, d_out, tot, list_n + 3);
+		e = hipGetLastError();
+	}
 	(void)hipEventRecord(h->ev[1], h->stream);
 	std::vector<i32> np((size_t)n_reads);
-	if (e == hipSuccess && tot) e = hipMemcpyAsync(res.get(), d_out, (size_t)tot * sizeof(bwagpu_primary_t), hipMemcpyDeviceToHost, h->stream);
+	unsigned int n_miss = 0;
+	if (e == hipSuccess && tot && !resident) e = hipMemcpyAsync(res.get(), d_out, (size_t)tot * sizeof(bwagpu_primary_t), hipMemcpyDeviceToHost, h->stream);
+	if (e == hipSuccess && resident) e = hipMemcpyAsync(&n_miss, list_n + 3, sizeof n_miss, hipMemcpyDeviceToHost, h->stream);
 	if (e == hipSuccess) e = hipMemcpyAsync(np.data(), d_npri, (size_t)n_reads * 4, hipMemcpyDeviceToHost, h->stream);
 	if (e == hipSuccess) e = wait_stream(h);
 	HIPCHK(h, e);
 	if (kernel_ms) (void)hipEventElapsedTime(kernel_ms, h->ev[0], h->ev[1]);
 	for (int i = 0; i < n_reads; ++i) if (np[i] < 0) { h->err = "internal: a read outgrew the marking kernel's working arrays"; return BWAGPU_EHIP; }
 	if (n_pri) memcpy(n_pri, np.data(), (size_t)n_reads * 4);
+	if (resident) {
+		if (n_miss == 0) return BWAGPU_OK;
+		res = result_block<bwagpu_primary_t>((size_t)tot);
+		if (!res) return BWAGPU_ENOMEM;
+		HIPCHK(h, hipMemcpyAsync(res.get(), d_out, (size_t)tot * sizeof(bwagpu_primary_t), hipMemcpyDeviceToHost, h->stream));
+		HIPCHK(h, wait_stream(h));
+	}
 	// records whose mapQ needed a logarithm outside the table: the same function with the host's log()
 	bool any = false;
 	for (i64 k = 0; k < tot && !any; ++k) any = (res[k].flags & 1) != 0;
@@ -1818,6 +1890,11 @@ static int primary_run(bwagpu_t *h, const bwagpu_opt_t *opt, RegLists L, i64 log
 			}
 			base += L.h_cnt[i];
 		}
+	}
+	if (resident) {
+		HIPCHK(h, hipMemcpyAsync(d_out, res.get(), (size_t)tot * sizeof(bwagpu_primary_t), hipMemcpyHostToDevice, h->stream));
+		HIPCHK(h, wait_stream(h));      // (the block goes back to the pool when this returns)
+		return BWAGPU_OK;
 	}
 	*out = res.release();
 	return BWAGPU_OK;
@@ -2405,14 +2482,17 @@ extern "C" void bwagpu_alns_limits(int32_t out[2]) { out[0] = ALN_LANE_MAX; out[
 extern "C" int bwagpu_aln_size(void) { return (int)sizeof(bwagpu_aln_t); }
 
 // The kernels of both entry points on the lists L: the marking (primary_run: its records stay in d_pri_out), then k_alns_lane / k_alns_wave with the CIGAR
-// records, operation array and read lengths of I (I.pri is set here).
-static int alns_run(bwagpu_t *h, const bwagpu_opt_t *opt, const RegLists &L, i64 log_need, AlnIn I, bwagpu_aln_t **alns, int32_t *n_aln, bwagpu_primary_t **pri, int32_t *n_pri, float *kernel_ms)
+// records, operation array and read lengths of I (I.pri is set here).  resident (a caller that wants text, sam_run): the records of both stages stay in
+// d_aln_out / d_pri_out and nothing comes to the host; the kernels of this stage run between ev[0] and ev[1], *kernel_ms is the marking's time alone.
+static int alns_run(bwagpu_t *h, const bwagpu_opt_t *opt, const RegLists &L, i64 log_need, AlnIn I, bwagpu_aln_t **alns, int32_t *n_aln, bwagpu_primary_t **pri, int32_t *n_pri, float *kernel_ms,
+					bool resident = false)
 {
 	const int n_reads = L.n;
 	const i64 tot = L.tot;
 	if (kernel_ms) *kernel_ms = 0.f;
-	ResultBlock<bwagpu_aln_t> res = result_block<bwagpu_aln_t>((size_t)tot);
+	ResultBlock<bwagpu_aln_t> res = result_block<bwagpu_aln_t>(resident ? 0 : (size_t)tot);
 	if (!res) return BWAGPU_ENOMEM;
+	if (resident && (n_reads == 0 || tot == 0)) return BWAGPU_OK;
 	if (n_reads == 0 || tot == 0) {
 		ResultBlock<bwagpu_primary_t> none = result_block<bwagpu_primary_t>(0);
 		if (!none) return BWAGPU_ENOMEM;
@@ -2423,7 +2503,7 @@ static int alns_run(bwagpu_t *h, const bwagpu_opt_t *opt, const RegLists &L, i64
 	}
 	bwagpu_primary_t *recs_ = nullptr;
 	float ms_pri = 0.f, ms = 0.f;
-	const int rc = primary_run(h, opt, L, log_need, &recs_, n_pri, &ms_pri);
+	const int rc = primary_run(h, opt, L, log_need, &recs_, n_pri, &ms_pri, resident);
 	if (rc != BWAGPU_OK) return rc;
 	ResultBlock<bwagpu_primary_t> recs(recs_);
 	if (h->d_aln_out.ensure((size_t)tot * sizeof(bwagpu_aln_t)) || h->d_aln_n.ensure((size_t)n_reads * 4) || h->d_aln_list.ensure((size_t)n_reads * 4) || h->d_aln_ctr.ensure(sizeof(unsigned int))) {
@@ -2431,7 +2511,7 @@ static int alns_run(bwagpu_t *h, const bwagpu_opt_t *opt, const RegLists &L, i64
 	}
 	// a mapQ the host side of the marking had to compute (a logarithm outside the table) is not in the device's copy of the records yet
 	bool any = false;
-	for (i64 k = 0; k < tot && !any; ++k) any = (recs[k].flags & 1) != 0;
+	for (i64 k = 0; !resident && k < tot && !any; ++k) any = (recs[k].flags & 1) != 0;
 	if (any) HIPCHK(h, hipMemcpyAsync(h->d_pri_out.p, recs.get(), (size_t)tot * sizeof(bwagpu_primary_t), hipMemcpyHostToDevice, h->stream));
 	HIPCHK(h, hipMemsetAsync(h->d_aln_ctr.p, 0, sizeof(unsigned int), h->stream));
 	I.pri = h->d_pri_out.as<bwagpu_primary_t>();
@@ -2447,6 +2527,7 @@ static int alns_run(bwagpu_t *h, const bwagpu_opt_t *opt, const RegLists &L, i64
 		HIPCHK(h, hipGetLastError());
 	}
 	(void)hipEventRecord(h->ev[1], h->stream);
+	if (resident) { if (kernel_ms) *kernel_ms = ms_pri; return BWAGPU_OK; }
 	std::vector<i32> na((size_t)n_reads);
 	HIPCHK(h, hipMemcpyAsync(res.get(), d_out, (size_t)tot * sizeof(bwagpu_aln_t), hipMemcpyDeviceToHost, h->stream));
 	HIPCHK(h, hipMemcpyAsync(na.data(), d_n, (size_t)n_reads * 4, hipMemcpyDeviceToHost, h->stream));
@@ -2507,6 +2588,158 @@ extern "C" int bwagpu_alns_flat(bwagpu_t *h, const bwagpu_opt_t *opt, int n_read
 		I.cigs = h->d_aln_cigs.as<bwagpu_cigar_t>(); I.ops = h->d_aln_ops.as<u32>(); I.read_len = h->d_aln_len.as<i32>();
 	}
 	return alns_run(h, opt, L, pri_log_need(counts, regs, n_reads), I, alns, n_aln, pri, n_pri, kernel_ms);
+}
+
+// ---- single-end SAM text on the device (dev_samtext.h) ------------------------------------------------------------------------------------------------
+extern "C" void bwagpu_sam_limits(int32_t out[2]) { out[0] = SAM_STAGE; out[1] = SAM_STEP; }
+
+// what both entry points require of the caller's names, comments and of the handle
+static int sam_in_check(bwagpu_t *h, int n_reads, const bwagpu_sam_in_t *in, const char *what)
+{
+	if (!h->ibuf->have_names) { h->err = std::string(what) + ": the handle has no contig names (bwagpu_set_contig_names)"; return BWAGPU_EINVAL; }
+	if (n_reads > 0 && (!in->names || !in->name_off || (in->comments && !in->comment_off))) return BWAGPU_EINVAL;
+	for (int i = 0; i < n_reads; ++i)
+		if (in->name_off[0] < 0 || in->name_off[i] > in->name_off[i + 1] || (in->comments && (in->comment_off[0] < 0 || in->comment_off[i] > in->comment_off[i + 1]))) {
+			h->err = std::string(what) + ": offsets that do not ascend"; return BWAGPU_EINVAL;
+		}
+	return BWAGPU_OK;
+}
+
+// The kernels of both entry points on the lists L of reads d_seq / d_seqoff (n_bases in all): alns_run with its records left on the device, then the two
+// passes of the formatter.  Host waits: the marking's, one for the total size, one for the final copies.
+static int sam_run(bwagpu_t *h, const bwagpu_opt_t *opt, const RegLists &L, i64 log_need, AlnIn I, const u8 *d_seq, const i64 *d_seqoff, i64 n_bases, const bwagpu_sam_in_t *in, bwagpu_sam_out_t *out)
+{
+	const int n = L.n;
+	ResultBlock<i64> off = result_block<i64>((size_t)n + 1);
+	ResultBlock<i32> flags = result_block<i32>((size_t)n), lines = result_block<i32>((size_t)n);
+	if (!off || !flags || !lines) return BWAGPU_ENOMEM;
+	if (n == 0) {
+		ResultBlock<char> text = result_block<char>(0);
+		if (!text) return BWAGPU_ENOMEM;
+		off[0] = 0;
+		out->text = text.release(); out->off = off.release(); out->flags = flags.release(); out->n_lines = lines.release();
+		return BWAGPU_OK;
+	}
+	// the reads' names, qualities and comments, -R's id
+	DevBuf *B = h->d_st;
+	const size_t n_names = (size_t)in->name_off[n], n_comm = in->comments ? (size_t)in->comment_off[n] : 0, n_rg = in->rg_id ? strlen(in->rg_id) : 0;
+	if (B[bwagpu_s::ST_NAMES].ensure(n_names + 1) || B[bwagpu_s::ST_NAMEOFF].ensure(((size_t)n + 1) * 8) || (in->quals && B[bwagpu_s::ST_QUAL].ensure((size_t)n_bases + 1)) ||
+		(in->comments && (B[bwagpu_s::ST_COMM].ensure(n_comm + 1) || B[bwagpu_s::ST_COMMOFF].ensure(((size_t)n + 1) * 8))) || B[bwagpu_s::ST_RG].ensure(n_rg + 1) ||
+		B[bwagpu_s::ST_SIZE].ensure((size_t)n * 4) || B[bwagpu_s::ST_TOFF].ensure(((size_t)n + 1) * 8) || B[bwagpu_s::ST_FLAGS].ensure((size_t)n * 4) || B[bwagpu_s::ST_LINES].ensure((size_t)n * 4)) {
+		h->err = "hipMalloc failed (sam)"; return BWAGPU_ENOMEM;
+	}
+	if (n_names) HIPCHK(h, hipMemcpyAsync(B[bwagpu_s::ST_NAMES].p, in->names, n_names, hipMemcpyHostToDevice, h->stream));
+	HIPCHK(h, hipMemcpyAsync(B[bwagpu_s::ST_NAMEOFF].p, in->name_off, ((size_t)n + 1) * 8, hipMemcpyHostToDevice, h->stream));
+	if (in->quals && n_bases) HIPCHK(h, hipMemcpyAsync(B[bwagpu_s::ST_QUAL].p, in->quals, (size_t)n_bases, hipMemcpyHostToDevice, h->stream));
+	if (in->comments) {
+		if (n_comm) HIPCHK(h, hipMemcpyAsync(B[bwagpu_s::ST_COMM].p, in->comments, n_comm, hipMemcpyHostToDevice, h->stream));
+		HIPCHK(h, hipMemcpyAsync(B[bwagpu_s::ST_COMMOFF].p, in->comment_off, ((size_t)n + 1) * 8, hipMemcpyHostToDevice, h->stream));
+	}
+	if (n_rg) HIPCHK(h, hipMemcpyAsync(B[bwagpu_s::ST_RG].p, in->rg_id, n_rg, hipMemcpyHostToDevice, h->stream));
+	float ms_pri = 0.f;
+	const int rc = alns_run(h, opt, L, log_need, I, nullptr, nullptr, nullptr, nullptr, &ms_pri, true);
+	if (rc != BWAGPU_OK) return rc;
+	SamIn S = {};
+	S.alns = h->d_aln_out.as<bwagpu_aln_t>(); S.pri = h->d_pri_out.as<bwagpu_primary_t>(); S.cigs = I.cigs; S.ops = I.ops;
+	S.seq = d_seq; S.seq_off = d_seqoff;
+	S.names = B[bwagpu_s::ST_NAMES].as<char>(); S.name_off = B[bwagpu_s::ST_NAMEOFF].as<i64>();
+	S.quals = in->quals ? B[bwagpu_s::ST_QUAL].as<char>() : nullptr;
+	S.comments = in->comments ? B[bwagpu_s::ST_COMM].as<char>() : nullptr; S.comment_off = in->comments ? B[bwagpu_s::ST_COMMOFF].as<i64>() : nullptr;
+	S.rg = B[bwagpu_s::ST_RG].as<char>(); S.rg_len = (int)n_rg;
+	S.ctg_text = h->ibuf->d_ctg_text.as<char>(); S.ctg_name_off = h->ibuf->d_ctg_toff.as<i64>(); S.ctg_anno_off = S.ctg_name_off + h->n_seqs + 1;
+	S.extra_flag = in->extra_flag;
+	i32 *d_size = B[bwagpu_s::ST_SIZE].as<i32>(), *d_flags = B[bwagpu_s::ST_FLAGS].as<i32>(), *d_lines = B[bwagpu_s::ST_LINES].as<i32>();
+	i64 *d_toff = B[bwagpu_s::ST_TOFF].as<i64>();
+	const int nb = n < 256 * 16 ? n : 256 * 16;
+	(void)hipEventRecord(h->ev[2], h->stream);
+	hipLaunchKernelGGL(k_sam_size, dim3(nb), dim3(64), 0, h->stream, *opt, n, L.d_cnt, L.d_off, S, d_size, d_flags, d_lines);
+	HIPCHK(h, hipGetLastError());
+	hipLaunchKernelGGL(k_rescue_scan, dim3(1), dim3(256), 0, h->stream, d_size, n, d_toff);
+	HIPCHK(h, hipGetLastError());
+	(void)hipEventRecord(h->ev[3], h->stream);
+	i64 total = 0;
+	HIPCHK(h, hipMemcpyAsync(&total, d_toff + n, 8, hipMemcpyDeviceToHost, h->stream));
+	HIPCHK(h, wait_stream(h));
+	if (total < 0) { h->err = "internal: a negative text size"; return BWAGPU_EHIP; }
+	ResultBlock<char> text = result_block<char>((size_t)total);
+	if (!text) return BWAGPU_ENOMEM;
+	if (B[bwagpu_s::ST_TEXT].ensure((size_t)total + 1)) { h->err = "hipMalloc failed (sam)"; return BWAGPU_ENOMEM; }
+	(void)hipEventRecord(h->ev[4], h->stream);
+	hipLaunchKernelGGL(k_sam_write, dim3(nb), dim3(64), 0, h->stream, *opt, n, L.d_cnt, L.d_off, S, d_toff, d_flags, B[bwagpu_s::ST_TEXT].as<char>());
+	HIPCHK(h, hipGetLastError());
+	(void)hipEventRecord(h->ev[5], h->stream);
+	if (total) HIPCHK(h, hipMemcpyAsync(text.get(), B[bwagpu_s::ST_TEXT].p, (size_t)total, hipMemcpyDeviceToHost, h->stream));
+	HIPCHK(h, hipMemcpyAsync(off.get(), d_toff, ((size_t)n + 1) * 8, hipMemcpyDeviceToHost, h->stream));
+	HIPCHK(h, hipMemcpyAsync(flags.get(), d_flags, (size_t)n * 4, hipMemcpyDeviceToHost, h->stream));
+	HIPCHK(h, hipMemcpyAsync(lines.get(), d_lines, (size_t)n * 4, hipMemcpyDeviceToHost, h->stream));
+	HIPCHK(h, wait_stream(h));
+	float ms = 0.f;
+	if (L.tot > 0) (void)hipEventElapsedTime(&ms, h->ev[0], h->ev[1]);
+	out->kernel_ms[0] = ms_pri + ms;
+	(void)hipEventElapsedTime(&out->kernel_ms[1], h->ev[2], h->ev[3]);
+	(void)hipEventElapsedTime(&out->kernel_ms[2], h->ev[4], h->ev[5]);
+	for (int i = 0; i < n; ++i) out->n_declined += flags[i] & 1;
+	out->n_text = total;
+	out->text = text.release(); out->off = off.release(); out->flags = flags.release(); out->n_lines = lines.release();
+	return BWAGPU_OK;
+}
+
+extern "C" int bwagpu_batch_sam(bwagpu_t *h, const bwagpu_opt_t *opt, int64_t id0, const bwagpu_sam_in_t *in, bwagpu_sam_out_t *out)
+{
+	if (!h || !opt || !h->ran || !h->downloaded || h->cig_ext_n < 0 || !in || !out) return BWAGPU_EINVAL;
+	if (opt->flag & 0x800 /* MEM_F_PRIMARY5 */) return BWAGPU_EINVAL;
+	memset(out, 0, sizeof *out);
+	if (int rc = sam_in_check(h, h->n_reads, in, "bwagpu_batch_sam")) return rc;
+	const BusyGuard busy(h->ibuf->busy);
+	HIPCHK(h, hipSetDevice(h->device));
+	const RegLists L = lists_of_batch(h, id0);
+	AlnIn I = {}; I.cigs = h->d_cigs.as<bwagpu_cigar_t>(); I.ops = h->d_cig_ext.as<u32>(); I.n_ops = h->cig_ext_n; I.seq_off = h->d_off.as<i64>();
+	return sam_run(h, opt, L, batch_log_need(h, opt), I, h->d_seq.as<u8>(), h->d_off.as<i64>(), h->n_bases, in, out);
+}
+
+extern "C" int bwagpu_sam_flat(bwagpu_t *h, const bwagpu_opt_t *opt, int n_reads, const uint8_t *seqs, const int64_t *seq_off, const int32_t *counts, const bwagpu_alnreg_t *regs,
+							   const int64_t *ids, const bwagpu_cigar_t *cigs, const uint32_t *ops, int64_t n_ops, const bwagpu_sam_in_t *in, bwagpu_sam_out_t *out)
+{
+	if (!h || !opt || n_reads < 0 || !in || !out || n_ops < 0 || (n_ops > 0 && !ops) || (n_reads > 0 && (!counts || !ids || !seq_off))) return BWAGPU_EINVAL;
+	if (opt->flag & 0x800 /* MEM_F_PRIMARY5 */) return BWAGPU_EINVAL;
+	memset(out, 0, sizeof *out);
+	if (int rc = sam_in_check(h, n_reads, in, "bwagpu_sam_flat")) return rc;
+	FlatLists F; RegLists L;
+	if (!F.scan(h, (size_t)n_reads, counts, regs, counts)) return BWAGPU_EINVAL;
+	if (F.tot > 0 && !cigs) return BWAGPU_EINVAL;
+	for (int i = 0; i < n_reads; ++i)
+		if (seq_off[0] != 0 || seq_off[i + 1] < seq_off[i] || seq_off[i + 1] - seq_off[i] > 0x3fffffff) { h->err = "bwagpu_sam_flat: offsets that do not ascend"; return BWAGPU_EINVAL; }
+	const i64 n_bases = n_reads ? seq_off[n_reads] : 0;
+	if (n_bases > 0 && !seqs) return BWAGPU_EINVAL;
+	for (i64 k = 0; k < F.tot; ++k) {
+		const bwagpu_cigar_t &c = cigs[k];
+		if (c.n_cigar < -1 || c.n_cigar > 32768) { h->err = "bwagpu_sam_flat: n_cigar outside [-1, 32768]"; return BWAGPU_EINVAL; }
+		if (c.n_cigar > 6) {
+			const u64 at = (u64)c.cigar[1] << 32 | c.cigar[0];
+			if (at > (u64)n_ops || (u64)c.n_cigar > (u64)n_ops - at) { h->err = "bwagpu_sam_flat: a CIGAR record points outside the operation array"; return BWAGPU_EINVAL; }
+		}
+		if (c.n_cigar >= 0 && (c.md_len < 0 || (c.md_len > 8 && (c.md > (u64)n_ops || ((u64)c.md_len + 3) / 4 > (u64)n_ops - c.md)))) {
+			h->err = "bwagpu_sam_flat: an MD string outside the operation array"; return BWAGPU_EINVAL;
+		}
+	}
+	const BusyGuard busy(h->ibuf->busy);
+	HIPCHK(h, hipSetDevice(h->device));
+	const int rc = F.upload(h, "sam", counts, regs, ids, (size_t)n_reads, L);
+	if (rc != BWAGPU_OK) return rc;
+	AlnIn I = {}; I.n_ops = n_ops;
+	DevBuf &d_seq = h->d_st[bwagpu_s::ST_SEQ], &d_seqoff = h->d_st[bwagpu_s::ST_SEQOFF];
+	if (n_reads > 0) {
+		if (h->d_aln_cigs.ensure((size_t)(F.tot ? F.tot : 1) * sizeof(bwagpu_cigar_t)) || h->d_aln_ops.ensure((size_t)(n_ops ? n_ops : 1) * 4) || d_seq.ensure((size_t)n_bases + 1) || d_seqoff.ensure(((size_t)n_reads + 1) * 8)) {
+			h->err = "hipMalloc failed (sam)"; return BWAGPU_ENOMEM;
+		}
+		if (F.tot) HIPCHK(h, hipMemcpyAsync(h->d_aln_cigs.p, cigs, (size_t)F.tot * sizeof(bwagpu_cigar_t), hipMemcpyHostToDevice, h->stream));
+		if (n_ops) HIPCHK(h, hipMemcpyAsync(h->d_aln_ops.p, ops, (size_t)n_ops * 4, hipMemcpyHostToDevice, h->stream));
+		if (n_bases) HIPCHK(h, hipMemcpyAsync(d_seq.p, seqs, (size_t)n_bases, hipMemcpyHostToDevice, h->stream));
+		HIPCHK(h, hipMemcpyAsync(d_seqoff.p, seq_off, ((size_t)n_reads + 1) * 8, hipMemcpyHostToDevice, h->stream));
+		HIPCHK(h, wait_stream(h));      // (the caller's arrays are pageable, as in bwagpu_alns_flat)
+		I.cigs = h->d_aln_cigs.as<bwagpu_cigar_t>(); I.ops = h->d_aln_ops.as<u32>(); I.seq_off = d_seqoff.as<i64>();
+	}
+	return sam_run(h, opt, L, pri_log_need(counts, regs, n_reads), I, d_seq.as<u8>(), d_seqoff.as<i64>(), n_bases, in, out);
 }
 
 // ---- a read pair decided on the device (dev_sampe.h) ----------------------------------------------------------------------------------------------------

@@ -43,6 +43,7 @@ void finalize_batch(const bwagpu_opt_t &opt, const RefSeqs &ref, int64_t n_proce
 		});
 	} else {
 		parallel_for(n_threads, n, [&](long i) {
+			if (reads[i].dev_text) { sam[i].assign(reads[i].dev_text, (size_t)reads[i].n_dev_text); return; }      // (the device's text: bwagpu_batch_sam)
 			thread_local Regs a;
 			a.assign(all + roff[i], all + roff[i + 1]);
 			thread_local std::vector<int32_t> mq;
@@ -88,6 +89,7 @@ void finalize_batch_chunks(const bwagpu_opt_t &opt, const RefSeqs &ref, int64_t 
 				}
 			} else {
 				for (int i = lo; i < hi; ++i) {
+					if (reads[i].dev_text) { buf.append(reads[i].dev_text, (size_t)reads[i].n_dev_text); continue; }      // (the device's text: bwagpu_batch_sam)
 					a[0].assign(all + roff[i], all + roff[i + 1]);
 					const int32_t *dq = mark_se(opt, a[0], reads[i], n_processed + i, mq);
 					reg2sam(opt, ref, buf, reads[i], a[0], 0, 0, rg_id, dq);
@@ -106,9 +108,10 @@ void finalize_batch_chunks(const bwagpu_opt_t &opt, const RefSeqs &ref, int64_t 
 				}
 			} else {
 				for (int i = lo; i < hi; ++i) {
+					out[0].clear();
+					if (reads[i].dev_text) { out[0].append(reads[i].dev_text, (size_t)reads[i].n_dev_text); put(dst, out[0]); continue; }
 					a[0].assign(all + roff[i], all + roff[i + 1]);
 					const int32_t *dq = mark_se(opt, a[0], reads[i], n_processed + i, mq);
-					out[0].clear();
 					reg2sam(opt, ref, out[0], reads[i], a[0], 0, 0, rg_id, dq);
 					put(dst, out[0]);
 				}

@@ -46,6 +46,9 @@ static int g_device_primary = 0;  // BWAGPU_CLI_PRIMARY=1: single-end batches ta
 static int g_device_sampe = 0;    // BWAGPU_CLI_SAMPE=1: paired-end batches without -5 take the whole of mem_sam_pe up to the text from the device (bwagpu_batch_sampe, in place of bwagpu_batch_cigars and bwagpu_batch_rescue; conditions: BWAGPU_CLI_RESCUE's, device CIGARs on; same output)
 static int g_device_alns = 0;     // BWAGPU_CLI_ALNS=1: single-end batches without -5 also take every region's alignment record and the read's list from the device (bwagpu_batch_alns, after the CIGAR call; same output)
 static std::atomic<long> g_n_alns_reads(0);      // ... reads finalized from such records
+static int g_device_samtext = 0;  // BWAGPU_CLI_SAMTEXT=1: single-end batches without -5 take their SAM text from the device (bwagpu_batch_sam, after the CIGAR call, in place of bwagpu_batch_alns / bwagpu_batch_primary; device CIGARs on; same output); a read the device declines goes through the host formatter
+static std::atomic<long> g_n_samtext_reads(0);   // ... reads written from such text
+static std::string g_dev_rg_id; static bool g_dev_copy_comment = false;      // -R's id and -C for that call (set before the stages start)
 static std::atomic<long> g_n_primary_reads(0);   // ... reads finalized from such records (the BWAGPU_CLI_TRACE line at the end of the run)
 
 // ---- options -----------------------------------------------------------------------------------------------------------
@@ -355,6 +358,7 @@ struct Sub {      // one mem_process_seqs call (bwamem.c:1235-1264) on the reads
 	bwagpu_sampe_t *sampe = nullptr; bwagpu_cigar_t *m_cigs = nullptr; uint32_t *m_ops = nullptr; bwagpu_aln_t *m_alns = nullptr;   // bwagpu_batch_sampe: the pairs' records, and CIGAR records (with their operation array) and alignment records of the merged lists
 	// bwagpu_batch_rescue: the merged lists (read i: m_counts[i] regions), one record per pair; pri / pairs then describe these lists
 	Pestat pes[4]; bool have_pes = false;     // insert-size windows, when they had to be computed before the finalize stage
+	std::vector<bwagpu_sam_out_t> sam; std::vector<int> sam_lo;   // bwagpu_batch_sam: the text of every shard (a shard that was not formatted has a null text) and the shards' first reads
 	double t_dev = 0;
 };
 struct Work { long no = 0; Batch in; std::vector<Sub> subs; std::vector<std::string> out; bool by_read = false; /* SAM text in output order: one string per chunk of reads, or (by_read, smart pairing) per read */ };
@@ -404,7 +408,7 @@ static void device_fail(bwagpu_t *gpu, int rc, const char *what = nullptr)
 // mate-rescue alignments -- on its range, and the results are concatenated in read order.  The one step that needs the whole
 // batch, mem_pestat (bwamem.c:1258), runs on the host over the gathered regions between the two device phases, so the SAM is the
 // single-device SAM whatever the number of devices.
-static void device_sub(const std::vector<bwagpu_t*> &gpus, Sub &u, const RefSeqs &ref, const Pestat *pes0)
+static void device_sub(const std::vector<bwagpu_t*> &gpus, Sub &u, const RefSeqs &ref, const Pestat *pes0, const Batch *in = nullptr /* the reads' records: names, qualities and comments for bwagpu_batch_sam */)
 {
 	std::unique_lock<std::mutex> serial(g_dev_mutex, std::defer_lock);
 	if (g_dev_serialize) serial.lock();
@@ -539,7 +543,37 @@ static void device_sub(const std::vector<bwagpu_t*> &gpus, Sub &u, const RefSeqs
 	// ... or, with the CIGAR records resident, the whole alignment list of every read (mem_reg2aln per region, mem_reg2sam's loop per read), which brings the
 	// marking records along.  Not with -5: mem_reorder_primary5 sits between the marking and the list.  Paired-end batches: the CIGARs of the merged lists are not
 	// on the device.
-	const bool dev_alns = g_device_alns && !pe && have_cigs && !(u.opt.flag & F_PRIMARY5);
+	// ... or the text itself: one call per shard formats every read of the shard from the resident records; neither the alignment nor the marking records come to the host
+	const bool dev_samtext = g_device_samtext && !pe && have_cigs && in && !(u.opt.flag & F_PRIMARY5);
+	if (dev_samtext) {
+		u.sam.assign((size_t)D, bwagpu_sam_out_t()); u.sam_lo.assign((size_t)D, 0);
+		on_devices([&](int d) {
+			Shard &s = sh[d];
+			u.sam_lo[(size_t)d] = s.lo;
+			memset(&u.sam[(size_t)d], 0, sizeof(bwagpu_sam_out_t));
+			if (s.tot == 0) return;      // (no CIGAR call for this shard: its reads print the unmapped record on the host)
+			const int m = s.hi - s.lo;
+			int n_qual = 0;
+			for (int i = s.lo; i < s.hi; ++i) n_qual += in->seqs[u.idx[i]].has_qual;
+			if (n_qual != 0 && n_qual != m) return;      // (qualities for some reads only: the host formatter)
+			std::string names, quals, comments; std::vector<int64_t> name_off(1, 0), comment_off(1, 0);
+			for (int i = s.lo; i < s.hi; ++i) {
+				const Seq &q = in->seqs[u.idx[i]];
+				const char *T = in->T(q);
+				names += T + q.name; name_off.push_back((int64_t)names.size());
+				if (n_qual) quals.append(T + q.qual, (size_t)q.l_seq);
+				if (g_dev_copy_comment && q.has_comment) comments += T + q.comment;
+				comment_off.push_back((int64_t)comments.size());
+			}
+			bwagpu_sam_in_t si; memset(&si, 0, sizeof si);
+			si.names = names.data(); si.name_off = name_off.data(); si.quals = n_qual ? quals.data() : nullptr;
+			if (g_dev_copy_comment) { si.comments = comments.data(); si.comment_off = comment_off.data(); }
+			si.rg_id = g_dev_rg_id.c_str();
+			const int rc = bwagpu_batch_sam(gpus[d], &u.opt, u.n_processed + s.lo, &si, &u.sam[(size_t)d]);
+			if (rc != BWAGPU_OK) device_fail(gpus[d], rc);
+		});
+	}
+	const bool dev_alns = !dev_samtext && g_device_alns && !pe && have_cigs && !(u.opt.flag & F_PRIMARY5);
 	if (dev_alns) {
 		on_devices([&](int d) {
 			Shard &s = sh[d];
@@ -559,7 +593,7 @@ static void device_sub(const std::vector<bwagpu_t*> &gpus, Sub &u, const RefSeqs
 			}
 		}
 	}
-	if (!dev_alns && g_device_primary && !pe && u.tot > 0) {
+	if (!dev_alns && !dev_samtext && g_device_primary && !pe && u.tot > 0) {
 		on_devices([&](int d) {
 			Shard &s = sh[d];
 			if (s.tot == 0) return;
@@ -719,6 +753,13 @@ static void finalize_sub(const RefSeqs &ref, Work &w, Sub &u, const Pestat *pes0
 		reads[i].seq = u.flat.data() + u.off[i]; reads[i].qual = q.has_qual ? T + q.qual : nullptr; reads[i].l_seq = q.l_seq;
 		if (u.rescue) { reads[i].merged = u.m_all + moff[i]; reads[i].n_merged = u.m_counts[i]; reads[i].pri = u.pri + moff[i]; if (!(i & 1)) reads[i].rescue = u.rescue + (i >> 1); }
 		else if (u.pri) { reads[i].pri = u.pri + roff[i]; if (u.alns) reads[i].alns = u.alns + roff[i]; }
+		if (!u.sam.empty()) {      // the read's slice of its shard's text; a declined read keeps the host formatter
+			size_t d = u.sam.size() - 1;
+			while (d > 0 && u.sam_lo[d] > i) --d;
+			const bwagpu_sam_out_t &o = u.sam[d];
+			const long k = i - u.sam_lo[d];
+			if (o.text && !(o.flags[k] & 1)) { reads[i].dev_text = o.text + o.off[k]; reads[i].n_dev_text = o.off[k + 1] - o.off[k]; }
+		}
 		if (u.pairs && !(i & 1)) reads[i].pair = u.pairs + (i >> 1);
 	});
 	if (u.opt.flag & F_PE) for (int i = 0; i + 1 < n; i += 2) if (strcmp(reads[i].name, reads[i + 1].name) != 0) { fprintf(stderr, "[mem_sam_pe] paired reads have different names: \"%s\", \"%s\"\n", reads[i].name, reads[i + 1].name); exit(EXIT_FAILURE); }
@@ -735,6 +776,13 @@ static void finalize_sub(const RefSeqs &ref, Work &w, Sub &u, const Pestat *pes0
 	if (u.sampe) { free(u.sampe); u.sampe = nullptr; free(u.m_cigs); u.m_cigs = nullptr; free(u.m_ops); u.m_ops = nullptr; free(u.m_alns); u.m_alns = nullptr; }
 	if (u.rescue) { free(u.rescue); u.rescue = nullptr; free(u.m_all); u.m_all = nullptr; free(u.m_src); u.m_src = nullptr; }
 	if (u.pairs) { free(u.pairs); u.pairs = nullptr; free(u.pri); u.pri = nullptr; }
+	if (!u.sam.empty()) {
+		long k = 0;
+		for (int i = 0; i < n; ++i) k += reads[i].dev_text != nullptr;
+		g_n_samtext_reads += k;
+		for (bwagpu_sam_out_t &o : u.sam) { bwagpu_free(o.text); bwagpu_free(o.off); bwagpu_free(o.flags); bwagpu_free(o.n_lines); }
+		u.sam.clear(); u.sam_lo.clear();
+	}
 	if (u.alns) { g_n_alns_reads += n; bwagpu_free(u.alns); u.alns = nullptr; bwagpu_free(u.pri); u.pri = nullptr; }
 	if (u.pri) { g_n_primary_reads += n; bwagpu_free(u.pri); u.pri = nullptr; }
 	bwagpu_free(u.all); u.all = nullptr; bwagpu_free(u.cigs); u.cigs = nullptr; bwagpu_free(u.cig_ops); u.cig_ops = nullptr; bwagpu_free(u.msw); u.msw = nullptr;
@@ -909,6 +957,10 @@ int main(int argc, char *argv[])
 		d.ctg_offset = off.data(); d.ctg_len = len.data(); d.ctg_is_alt = alt.data();
 		int rc = bwagpu_create(&gpu, &d, device);
 		if (rc != BWAGPU_OK) { fprintf(stderr, "[E::%s] %s\n", "main_mem", bwagpu_strerror(rc)); return 1; }
+		std::string names, annos; std::vector<int64_t> name_off(1, 0), anno_off(1, 0);      // (for the text the device writes: BWAGPU_CLI_SAMTEXT)
+		for (const Contig &c : ref.ctg) { names += c.name; name_off.push_back((int64_t)names.size()); annos += c.anno; anno_off.push_back((int64_t)annos.size()); }
+		rc = bwagpu_set_contig_names(gpu, names.data(), name_off.data(), annos.data(), anno_off.data());
+		if (rc != BWAGPU_OK) { fprintf(stderr, "[E::%s] %s\n", "main_mem", bwagpu_strerror(rc)); return 1; }
 	}
 	bwagpu_set_taps(gpu, 0);
 	bwagpu_set_cigar_filter(gpu, getenv("BWAGPU_CLI_CIGAR_FILTER") ? atoi(getenv("BWAGPU_CLI_CIGAR_FILTER")) : 1);   // (clones inherit it)
@@ -1002,6 +1054,8 @@ int main(int argc, char *argv[])
 	if (getenv("BWAGPU_CLI_CIGARS")) g_device_cigars = atoi(getenv("BWAGPU_CLI_CIGARS"));
 	if (getenv("BWAGPU_CLI_PRIMARY")) g_device_primary = atoi(getenv("BWAGPU_CLI_PRIMARY"));
 	if (getenv("BWAGPU_CLI_ALNS")) g_device_alns = atoi(getenv("BWAGPU_CLI_ALNS"));
+	if (getenv("BWAGPU_CLI_SAMTEXT")) g_device_samtext = atoi(getenv("BWAGPU_CLI_SAMTEXT"));
+	g_dev_rg_id = rg_id; g_dev_copy_comment = copy_comment != 0;
 	if (getenv("BWAGPU_CLI_PAIR")) g_device_pair = atoi(getenv("BWAGPU_CLI_PAIR"));
 	if (getenv("BWAGPU_CLI_RESCUE")) g_device_rescue = atoi(getenv("BWAGPU_CLI_RESCUE"));
 	if (getenv("BWAGPU_CLI_SAMPE")) g_device_sampe = atoi(getenv("BWAGPU_CLI_SAMPE"));
@@ -1157,7 +1211,7 @@ int main(int argc, char *argv[])
 			if (d < 16) dev_no[d] = (int)w->no;
 			++progress;
 			const double td = now_s();
-			for (Sub &u : w->subs) { device_sub(workers[(size_t)d], u, ref, pes0); ++progress; busy_dev_us += (long)(u.t_dev * 1e6); }
+			for (Sub &u : w->subs) { device_sub(workers[(size_t)d], u, ref, pes0, &w->in); ++progress; busy_dev_us += (long)(u.t_dev * 1e6); }
 			if (tl_trace) fprintf(stderr, "[D::timeline] batch %ld device %.3f .. %.3f (slot %d)\n", w->no, td - t_start, now_s() - t_start, d);
 			std::lock_guard<std::mutex> l(dm);
 			const long no = w->no;
@@ -1210,6 +1264,7 @@ int main(int argc, char *argv[])
 		fprintf(stderr, "[D::main_mem] %ld pairs merged on the device (BWAGPU_CLI_RESCUE), %ld of them with rescue alignments\n", hostmem::g_pairs_merged_on_device.load(), hostmem::g_pairs_merged_aligned.load());
 	if (g_device_pair && tl_trace) fprintf(stderr, "[D::main_mem] %ld pairs paired from device records (BWAGPU_CLI_PAIR)\n", hostmem::g_pairs_from_device.load());
 	if (g_device_sampe && tl_trace) fprintf(stderr, "[D::main_mem] %ld pairs finished from the device's pair records (BWAGPU_CLI_SAMPE)\n", hostmem::g_pairs_from_sampe.load());
+	if (g_device_samtext && tl_trace) fprintf(stderr, "[D::main_mem] %ld reads written from device SAM text (BWAGPU_CLI_SAMTEXT)\n", g_n_samtext_reads.load());
 	if (g_device_alns && tl_trace) fprintf(stderr, "[D::main_mem] %ld reads finalized from device alignment records (BWAGPU_CLI_ALNS)\n", g_n_alns_reads.load());
 	if (g_device_primary && tl_trace) fprintf(stderr, "[D::main_mem] %ld reads finalized from device primary/mapQ records (BWAGPU_CLI_PRIMARY)\n", g_n_primary_reads.load());
 	if (g_verbose >= 3) { const double dt = now_s() - t_start; fprintf(stderr, "[M::%s] %ld reads in %.3f sec after the index was loaded: %.0f reads/s\n", "main_mem", n_reads_total.load(), dt, dt > 0 ? n_reads_total.load() / dt : 0.);

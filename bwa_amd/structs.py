@@ -134,3 +134,17 @@ def pacbio_opt() -> MemOpt:
     o.min_chain_weight = 40
     fill_scmat(o)
     return o
+
+
+# bwagpu_sam_in_t / bwagpu_sam_out_t: bwagpu_batch_sam / bwagpu_sam_flat (SAM text written on the device)
+class SamIn(C.Structure):
+    _fields_ = [("names", C.c_void_p), ("name_off", C.c_void_p), ("quals", C.c_void_p), ("comments", C.c_void_p), ("comment_off", C.c_void_p), ("rg_id", C.c_char_p),
+                ("extra_flag", C.c_int32)]
+
+
+class SamOut(C.Structure):
+    _fields_ = [("text", C.c_void_p), ("n_text", C.c_int64), ("off", C.c_void_p), ("flags", C.c_void_p), ("n_lines", C.c_void_p), ("n_declined", C.c_int64),
+                ("kernel_ms", C.c_float * 3)]
+
+
+assert C.sizeof(SamIn) == 56 and C.sizeof(SamOut) == 64

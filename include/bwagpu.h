@@ -432,6 +432,39 @@ int bwagpu_alns_flat(bwagpu_t *h, const bwagpu_opt_t *opt, int n_reads, const in
 void bwagpu_alns_limits(int32_t out[2]);
 int  bwagpu_aln_size(void);   /* sizeof(bwagpu_aln_t) as compiled */
 
+/* The SAM text of single-end reads on the device: mem_aln2sam (bwamem.c:851-976) of every record mem_reg2sam lists for a read (m == NULL), the XA / XB strings
+ * of mem_gen_alt included, written by one kernel straight from the resident alignment, marking and CIGAR records.  The handle needs the contigs' names:
+ * bwagpu_create_from_files takes them (and the annotations) from .ann; a caller of bwagpu_create sets them once, before it clones the handle. */
+/* names / annos: the bytes of all names / annotations back to back, without terminators; contig i's are [name_off[i], name_off[i + 1]), n_seqs + 1 ascending
+ * offsets each.  annos may be NULL (no annotations: no XR tag).  bwagpu_clone shares them, bwagpu_clone_to_device copies them. */
+int bwagpu_set_contig_names(bwagpu_t *h, const char *names, const int64_t *name_off, const char *annos, const int64_t *anno_off);
+typedef struct {
+	const char *names;    const int64_t *name_off;     /* n_reads + 1 ascending offsets; no terminators */
+	const char *quals;                                  /* NULL: '*'; else one byte per base at the reads' own offsets */
+	const char *comments; const int64_t *comment_off;   /* NULL: none; an empty comment prints nothing (bseq_read leaves it NULL) */
+	const char *rg_id;                                  /* NULL or "": none */
+	int32_t extra_flag;
+} bwagpu_sam_in_t;
+typedef struct {
+	char *text;           int64_t n_text;               /* the batch's text: the lines of read i are text[off[i] .. off[i + 1]), in read order */
+	int64_t *off;                                       /* n_reads + 1 */
+	int32_t *flags;                                     /* per read; bit 0: declined -- no bytes, the caller formats the read */
+	int32_t *n_lines;     int64_t n_declined;           /* lines per read (0 for a declined one) */
+	float kernel_ms[3];                                 /* device time: marking + alignment lists, sizing + prefix sum, writing */
+} bwagpu_sam_out_t;                                     /* text, off, flags and n_lines are freed with bwagpu_free, each */
+/* After bwagpu_batch_download and bwagpu_batch_cigars of the same batch (bwagpu_batch_alns' preconditions): the kernels of bwagpu_batch_alns, whose records
+ * stay on the device, then two passes of one formatter -- bytes per read, a prefix sum, the text.  Read i has id id0 + i.  A read is declined when a region it
+ * prints, or one it lists in a printed XA, has no CIGAR record (BWAGPU_ALN_NOCIGAR); nothing else is.  A read without regions prints the unmapped record.
+ * Host waits: those of the marking, one for the total size, one for the final copy.  BWAGPU_EINVAL: bwagpu_batch_alns' cases, a handle without contig names
+ * (see bwagpu_last_error), NULL in / out / names / name_off, comments without comment_off, offsets that do not ascend. */
+int bwagpu_batch_sam(bwagpu_t *h, const bwagpu_opt_t *opt, int64_t id0, const bwagpu_sam_in_t *in, bwagpu_sam_out_t *out);
+/* The same on reads (nt4, n_reads + 1 offsets: `quals` follows them), lists, ids, CIGAR records and operation array of the caller: bwagpu_alns_flat's
+ * arguments and checks, and an MD string outside the operation array is BWAGPU_EINVAL too. */
+int bwagpu_sam_flat(bwagpu_t *h, const bwagpu_opt_t *opt, int n_reads, const uint8_t *seqs, const int64_t *seq_off, const int32_t *counts, const bwagpu_alnreg_t *regs,
+					const int64_t *ids, const bwagpu_cigar_t *cigs, const uint32_t *ops, int64_t n_ops, const bwagpu_sam_in_t *in, bwagpu_sam_out_t *out);
+/* out[0] bytes of a wavefront's staging area (a longer line is flushed in its middle), out[1] places of a marked list a wavefront takes per step */
+void bwagpu_sam_limits(int32_t out[2]);
+
 /* A read pair decided on the device: everything mem_sam_pe (bwamem_pair.c:276-419) does behind mem_pair except the text.  The merge of the mate-rescue hits,
  * the marking and the pairing are bwagpu_batch_rescue's; then one record per pair says which of the two ways out the pair takes and what it prints, the marking
  * records are patched as mem_sam_pe patches the lists (:335-336, :350-359), every merged region gets its CIGAR record (bwagpu_batch_cigars' kernels) and its
