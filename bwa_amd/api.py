@@ -137,6 +137,9 @@ def load_library(path: str | None = None) -> C.CDLL:
     L.bwagpu_batch_sam.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
     L.bwagpu_sam_flat.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 7 + [C.c_int64, C.c_void_p, C.c_void_p]
     L.bwagpu_sam_limits.restype = None
+    L.bwagpu_batch_sam_pe.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 4
+    L.bwagpu_sam_pe_flat.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 9
+    L.bwagpu_sam_pe_limits.restype = None
     L.bwagpu_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_longlong]
     L.bwagpu_get_option.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p]
     L.bwagpu_set_default_option.argtypes = [C.c_char_p, C.c_longlong]
@@ -522,6 +525,43 @@ class BwaGpu:
         out = (C.c_int32 * 2)()
         self.L.bwagpu_sampe_limits(out)
         return dict(zip(("lane_max", "step"), list(out)))
+
+    # -- SAM text on the device (paired-end) ------------------------------------------------------------------
+    def sam_pe(self, opt: MemOpt, pes: np.ndarray, id0, names, quals=None, comments=None, rg_id=None, extra_flag=0, want_records=False) -> dict:
+        """bwagpu_batch_sam_pe: after download(), sampe()'s kernels and then the SAM text of every read of the batch (reads 2p, 2p + 1 are mates and carry one
+        name), written on the device from the records those kernels left there.  names, quals, comments: one per READ, as in sam().  A pair is declined as a whole
+        (bit 0 of both reads' flag words).  -> the dictionary of sam() (kernel_ms[0]: the sum of sampe()'s six segments), and with want_records the dictionary of
+        sampe() under "pe"; without, no alignment or marking record comes to the host."""
+        pes = np.ascontiguousarray(pes, dtype=PESTAT_DTYPE)
+        assert pes.shape == (4,)
+        counts, o = np.zeros(self._n, dtype=np.int32), PeOut()
+        res = self._sam_call(self._n, names, quals, comments, rg_id, extra_flag,
+                             lambda i, so: self.L.bwagpu_batch_sam_pe(self.h, C.byref(opt), pes.ctypes.data, int(id0), i, counts.ctypes.data, C.byref(o) if want_records else None, so))
+        if want_records:
+            res["pe"] = self._pe_out(self._n, counts, o)
+        return res
+
+    def sam_pe_flat(self, opt: MemOpt, pes: np.ndarray, seqs, off, counts_in, regs_in, ids, names, quals=None, comments=None, rg_id=None, extra_flag=0, want_records=False) -> dict:
+        """bwagpu_sam_pe_flat: the same kernels on reads and region lists of the caller (the inputs of sampe_flat) -> as sam_pe()."""
+        pes = np.ascontiguousarray(pes, dtype=PESTAT_DTYPE)
+        seqs = np.ascontiguousarray(seqs, dtype=np.uint8); off = np.ascontiguousarray(off, dtype=np.int64)
+        counts_in = np.ascontiguousarray(counts_in, dtype=np.int32); regs_in = np.ascontiguousarray(regs_in, dtype=ALNREG_DTYPE)
+        ids = np.ascontiguousarray(ids, dtype=np.int64)
+        n = counts_in.shape[0]
+        assert pes.shape == (4,) and n % 2 == 0 and off.shape == (n + 1,) and int(counts_in.sum()) == regs_in.shape[0] and ids.shape == (n,)
+        counts, o = np.zeros(n, dtype=np.int32), PeOut()
+        res = self._sam_call(n, names, quals, comments, rg_id, extra_flag,
+                             lambda i, so: self.L.bwagpu_sam_pe_flat(self.h, C.byref(opt), pes.ctypes.data, n // 2, seqs.ctypes.data, off.ctypes.data, counts_in.ctypes.data, regs_in.ctypes.data,
+                                                                     ids.ctypes.data, i, counts.ctypes.data, C.byref(o) if want_records else None, so))
+        if want_records:
+            res["pe"] = self._pe_out(n, counts, o)
+        return res
+
+    def sam_pe_limits(self) -> dict:
+        """bwagpu_sam_pe_limits: as sam_limits()."""
+        out = (C.c_int32 * 2)()
+        self.L.bwagpu_sam_pe_limits(out)
+        return dict(zip(("staging", "step"), list(out)))
 
     def pestat(self, opt: MemOpt):
         """bwagpu_batch_pestat: mem_pestat of the last download() on the device (reads 2p, 2p + 1 are mates).

@@ -46,6 +46,7 @@
 #include "dev_alns.h"
 #include "dev_sampe.h"
 #include "dev_samtext.h"
+#include "dev_samtext_pe.h"
 #include "dev_debug.h"
 
 #define BWAGPU_VERSION "bwagpu 0.1 (gfx950)"
@@ -2605,22 +2606,22 @@ static int sam_in_check(bwagpu_t *h, int n_reads, const bwagpu_sam_in_t *in, con
 	return BWAGPU_OK;
 }
 
-// The kernels of both entry points on the lists L of reads d_seq / d_seqoff (n_bases in all): alns_run with its records left on the device, then the two
-// passes of the formatter.  Host waits: the marking's, one for the total size, one for the final copies.
-static int sam_run(bwagpu_t *h, const bwagpu_opt_t *opt, const RegLists &L, i64 log_need, AlnIn I, const u8 *d_seq, const i64 *d_seqoff, i64 n_bases, const bwagpu_sam_in_t *in, bwagpu_sam_out_t *out)
+// the text of a call without reads
+static int sam_none(bwagpu_sam_out_t *out)
 {
-	const int n = L.n;
-	ResultBlock<i64> off = result_block<i64>((size_t)n + 1);
-	ResultBlock<i32> flags = result_block<i32>((size_t)n), lines = result_block<i32>((size_t)n);
-	if (!off || !flags || !lines) return BWAGPU_ENOMEM;
-	if (n == 0) {
-		ResultBlock<char> text = result_block<char>(0);
-		if (!text) return BWAGPU_ENOMEM;
-		off[0] = 0;
-		out->text = text.release(); out->off = off.release(); out->flags = flags.release(); out->n_lines = lines.release();
-		return BWAGPU_OK;
-	}
-	// the reads' names, qualities and comments, -R's id
+	ResultBlock<i64> off = result_block<i64>(1);
+	ResultBlock<i32> flags = result_block<i32>(0), lines = result_block<i32>(0);
+	ResultBlock<char> text = result_block<char>(0);
+	if (!off || !flags || !lines || !text) return BWAGPU_ENOMEM;
+	off[0] = 0;
+	out->text = text.release(); out->off = off.release(); out->flags = flags.release(); out->n_lines = lines.release();
+	return BWAGPU_OK;
+}
+
+// The names, qualities and comments of n > 0 reads (n_bases bases in all) and -R's id go to the device; S gets them and the handle's contig names.  Also sizes
+// the per-read arrays of sam_passes.
+static int sam_upload(bwagpu_t *h, int n, i64 n_bases, const bwagpu_sam_in_t *in, SamIn &S)
+{
 	DevBuf *B = h->d_st;
 	const size_t n_names = (size_t)in->name_off[n], n_comm = in->comments ? (size_t)in->comment_off[n] : 0, n_rg = in->rg_id ? strlen(in->rg_id) : 0;
 	if (B[bwagpu_s::ST_NAMES].ensure(n_names + 1) || B[bwagpu_s::ST_NAMEOFF].ensure(((size_t)n + 1) * 8) || (in->quals && B[bwagpu_s::ST_QUAL].ensure((size_t)n_bases + 1)) ||
@@ -2636,27 +2637,34 @@ static int sam_run(bwagpu_t *h, const bwagpu_opt_t *opt, const RegLists &L, i64 
 		HIPCHK(h, hipMemcpyAsync(B[bwagpu_s::ST_COMMOFF].p, in->comment_off, ((size_t)n + 1) * 8, hipMemcpyHostToDevice, h->stream));
 	}
 	if (n_rg) HIPCHK(h, hipMemcpyAsync(B[bwagpu_s::ST_RG].p, in->rg_id, n_rg, hipMemcpyHostToDevice, h->stream));
-	float ms_pri = 0.f;
-	const int rc = alns_run(h, opt, L, log_need, I, nullptr, nullptr, nullptr, nullptr, &ms_pri, true);
-	if (rc != BWAGPU_OK) return rc;
-	SamIn S = {};
-	S.alns = h->d_aln_out.as<bwagpu_aln_t>(); S.pri = h->d_pri_out.as<bwagpu_primary_t>(); S.cigs = I.cigs; S.ops = I.ops;
-	S.seq = d_seq; S.seq_off = d_seqoff;
 	S.names = B[bwagpu_s::ST_NAMES].as<char>(); S.name_off = B[bwagpu_s::ST_NAMEOFF].as<i64>();
 	S.quals = in->quals ? B[bwagpu_s::ST_QUAL].as<char>() : nullptr;
 	S.comments = in->comments ? B[bwagpu_s::ST_COMM].as<char>() : nullptr; S.comment_off = in->comments ? B[bwagpu_s::ST_COMMOFF].as<i64>() : nullptr;
 	S.rg = B[bwagpu_s::ST_RG].as<char>(); S.rg_len = (int)n_rg;
 	S.ctg_text = h->ibuf->d_ctg_text.as<char>(); S.ctg_name_off = h->ibuf->d_ctg_toff.as<i64>(); S.ctg_anno_off = S.ctg_name_off + h->n_seqs + 1;
 	S.extra_flag = in->extra_flag;
+	return BWAGPU_OK;
+}
+
+// The two passes of the formatter on n > 0 reads whose lists are d_cnt / d_off and whose records S names, and the final copies; d_sampe: the pair records of
+// a paired-end call (the kernels of dev_samtext_pe.h), or null.  e: the four events the passes run between (kernel_ms[1], [2]).  Host waits: one for the
+// total size, one for the final copies.
+static int sam_passes(bwagpu_t *h, const bwagpu_opt_t *opt, int n, const i32 *d_cnt, const i64 *d_off, const SamIn &S, const bwagpu_sampe_t *d_sampe, const int e[4], bwagpu_sam_out_t *out)
+{
+	DevBuf *B = h->d_st;
+	ResultBlock<i64> off = result_block<i64>((size_t)n + 1);
+	ResultBlock<i32> flags = result_block<i32>((size_t)n), lines = result_block<i32>((size_t)n);
+	if (!off || !flags || !lines) return BWAGPU_ENOMEM;
 	i32 *d_size = B[bwagpu_s::ST_SIZE].as<i32>(), *d_flags = B[bwagpu_s::ST_FLAGS].as<i32>(), *d_lines = B[bwagpu_s::ST_LINES].as<i32>();
 	i64 *d_toff = B[bwagpu_s::ST_TOFF].as<i64>();
 	const int nb = n < 256 * 16 ? n : 256 * 16;
-	(void)hipEventRecord(h->ev[2], h->stream);
-	hipLaunchKernelGGL(k_sam_size, dim3(nb), dim3(64), 0, h->stream, *opt, n, L.d_cnt, L.d_off, S, d_size, d_flags, d_lines);
+	(void)hipEventRecord(h->ev[e[0]], h->stream);
+	if (d_sampe) hipLaunchKernelGGL(k_sam_pe_size, dim3(nb), dim3(64), 0, h->stream, *opt, n, d_cnt, d_off, S, d_sampe, d_size, d_flags, d_lines);
+	else hipLaunchKernelGGL(k_sam_size, dim3(nb), dim3(64), 0, h->stream, *opt, n, d_cnt, d_off, S, d_size, d_flags, d_lines);
 	HIPCHK(h, hipGetLastError());
 	hipLaunchKernelGGL(k_rescue_scan, dim3(1), dim3(256), 0, h->stream, d_size, n, d_toff);
 	HIPCHK(h, hipGetLastError());
-	(void)hipEventRecord(h->ev[3], h->stream);
+	(void)hipEventRecord(h->ev[e[1]], h->stream);
 	i64 total = 0;
 	HIPCHK(h, hipMemcpyAsync(&total, d_toff + n, 8, hipMemcpyDeviceToHost, h->stream));
 	HIPCHK(h, wait_stream(h));
@@ -2664,23 +2672,41 @@ static int sam_run(bwagpu_t *h, const bwagpu_opt_t *opt, const RegLists &L, i64 
 	ResultBlock<char> text = result_block<char>((size_t)total);
 	if (!text) return BWAGPU_ENOMEM;
 	if (B[bwagpu_s::ST_TEXT].ensure((size_t)total + 1)) { h->err = "hipMalloc failed (sam)"; return BWAGPU_ENOMEM; }
-	(void)hipEventRecord(h->ev[4], h->stream);
-	hipLaunchKernelGGL(k_sam_write, dim3(nb), dim3(64), 0, h->stream, *opt, n, L.d_cnt, L.d_off, S, d_toff, d_flags, B[bwagpu_s::ST_TEXT].as<char>());
+	(void)hipEventRecord(h->ev[e[2]], h->stream);
+	if (d_sampe) hipLaunchKernelGGL(k_sam_pe_write, dim3(nb), dim3(64), 0, h->stream, *opt, n, d_cnt, d_off, S, d_sampe, d_toff, d_flags, B[bwagpu_s::ST_TEXT].as<char>());
+	else hipLaunchKernelGGL(k_sam_write, dim3(nb), dim3(64), 0, h->stream, *opt, n, d_cnt, d_off, S, d_toff, d_flags, B[bwagpu_s::ST_TEXT].as<char>());
 	HIPCHK(h, hipGetLastError());
-	(void)hipEventRecord(h->ev[5], h->stream);
+	(void)hipEventRecord(h->ev[e[3]], h->stream);
 	if (total) HIPCHK(h, hipMemcpyAsync(text.get(), B[bwagpu_s::ST_TEXT].p, (size_t)total, hipMemcpyDeviceToHost, h->stream));
 	HIPCHK(h, hipMemcpyAsync(off.get(), d_toff, ((size_t)n + 1) * 8, hipMemcpyDeviceToHost, h->stream));
 	HIPCHK(h, hipMemcpyAsync(flags.get(), d_flags, (size_t)n * 4, hipMemcpyDeviceToHost, h->stream));
 	HIPCHK(h, hipMemcpyAsync(lines.get(), d_lines, (size_t)n * 4, hipMemcpyDeviceToHost, h->stream));
 	HIPCHK(h, wait_stream(h));
-	float ms = 0.f;
-	if (L.tot > 0) (void)hipEventElapsedTime(&ms, h->ev[0], h->ev[1]);
-	out->kernel_ms[0] = ms_pri + ms;
-	(void)hipEventElapsedTime(&out->kernel_ms[1], h->ev[2], h->ev[3]);
-	(void)hipEventElapsedTime(&out->kernel_ms[2], h->ev[4], h->ev[5]);
+	(void)hipEventElapsedTime(&out->kernel_ms[1], h->ev[e[0]], h->ev[e[1]]);
+	(void)hipEventElapsedTime(&out->kernel_ms[2], h->ev[e[2]], h->ev[e[3]]);
 	for (int i = 0; i < n; ++i) out->n_declined += flags[i] & 1;
 	out->n_text = total;
 	out->text = text.release(); out->off = off.release(); out->flags = flags.release(); out->n_lines = lines.release();
+	return BWAGPU_OK;
+}
+
+// The kernels of both entry points on the lists L of reads d_seq / d_seqoff (n_bases in all): alns_run with its records left on the device, then the two
+// passes of the formatter.  Host waits: the marking's, one for the total size, one for the final copies.
+static int sam_run(bwagpu_t *h, const bwagpu_opt_t *opt, const RegLists &L, i64 log_need, AlnIn I, const u8 *d_seq, const i64 *d_seqoff, i64 n_bases, const bwagpu_sam_in_t *in, bwagpu_sam_out_t *out)
+{
+	if (L.n == 0) return sam_none(out);
+	SamIn S = {};
+	if (int rc = sam_upload(h, L.n, n_bases, in, S)) return rc;
+	float ms_pri = 0.f, ms = 0.f;
+	const int rc = alns_run(h, opt, L, log_need, I, nullptr, nullptr, nullptr, nullptr, &ms_pri, true);
+	if (rc != BWAGPU_OK) return rc;
+	S.alns = h->d_aln_out.as<bwagpu_aln_t>(); S.pri = h->d_pri_out.as<bwagpu_primary_t>(); S.cigs = I.cigs; S.ops = I.ops;
+	S.seq = d_seq; S.seq_off = d_seqoff;
+	const int e[4] = { 2, 3, 4, 5 };
+	const int rcp = sam_passes(h, opt, L.n, L.d_cnt, L.d_off, S, nullptr, e, out);
+	if (rcp != BWAGPU_OK) return rcp;
+	if (L.tot > 0) (void)hipEventElapsedTime(&ms, h->ev[0], h->ev[1]);
+	out->kernel_ms[0] = ms_pri + ms;
 	return BWAGPU_OK;
 }
 
@@ -2748,9 +2774,11 @@ extern "C" int bwagpu_sampe_size(void) { return (int)sizeof(bwagpu_sampe_t); }
 
 // The kernels of both entry points on the L.n = 2 n_pairs reads of the lists L (sequences d_seq / d_seqoff, the longest of max_len bases, n_bases in all):
 // rescue_run with marking and pairing; the decision kernels on its resident records; the CIGAR kernels on the merged lists; the alignment lists from the patched
-// marking records.  Host waits: rescue_run's, cigars_run's, one for the final copies.
+// marking records.  Host waits: rescue_run's, cigars_run's, one for the final copies.  resident (a caller that wants text and no records, sam_pe_run): alignment
+// records, patched marking records and operation array stay in d_aln_out / d_pri_out / d_sp and do not come to the host -- out->alns, out->ops are empty, out->pri is
+// rescue_run's, n_aln and the path-1 n_aa are not filled, there is no final wait and kernel_ms[5] is the caller's to read from ev[5], ev[6] behind a wait of its own.
 static int sampe_run(bwagpu_t *h, const bwagpu_opt_t *opt, const bwagpu_pestat_t pes[4], const RegLists &L, const u8 *d_seq, const i64 *d_seqoff, int max_len, i64 n_bases, int32_t *counts,
-					 bwagpu_pe_out_t *out)
+					 bwagpu_pe_out_t *out, bool resident = false)
 {
 	const int n_reads = L.n, np = n_reads / 2;
 	// MEM_F_NO_RESCUE is 0x20 (bwamem.h:44); k_rescue_count reads bit 0x8 for it, so this call hands it the bit where the reference would look
@@ -2765,7 +2793,7 @@ static int sampe_run(bwagpu_t *h, const bwagpu_opt_t *opt, const bwagpu_pestat_t
 	ResultBlock<bwagpu_alnreg_t> res_regs(regs_); ResultBlock<int32_t> res_src(src_); ResultBlock<bwagpu_rescue_t> res_resc(resc_); ResultBlock<bwagpu_primary_t> res_pri(pri_);
 	ResultBlock<bwagpu_pair_t> res_pairs(pairs_);
 	ResultBlock<bwagpu_cigar_t> res_cigs = result_block<bwagpu_cigar_t>((size_t)mtot);
-	ResultBlock<bwagpu_aln_t> res_alns = result_block<bwagpu_aln_t>((size_t)mtot);
+	ResultBlock<bwagpu_aln_t> res_alns = result_block<bwagpu_aln_t>(resident ? 0 : (size_t)mtot);
 	ResultBlock<uint32_t> res_ops;
 	if (!res_cigs || !res_alns) return BWAGPU_ENOMEM;
 	i64 ext_n = 0;
@@ -2822,7 +2850,7 @@ static int sampe_run(bwagpu_t *h, const bwagpu_opt_t *opt, const bwagpu_pestat_t
 		if (rcc != BWAGPU_OK) return rcc;
 		ms[4] = msc[0];
 		(void)hipEventElapsedTime(&ms[3], h->ev[3], h->ev[4]);
-		res_ops = result_block<uint32_t>((size_t)ext_n);
+		res_ops = result_block<uint32_t>(resident ? 0 : (size_t)ext_n);
 		if (!res_ops) return BWAGPU_ENOMEM;
 		// pairs that met a logarithm outside the table: the same statements with the host's log(), on the call's own copies; their records go back to the device
 		std::vector<i64> hoff;
@@ -2854,13 +2882,15 @@ static int sampe_run(bwagpu_t *h, const bwagpu_opt_t *opt, const bwagpu_pestat_t
 			HIPCHK(h, hipGetLastError());
 		}
 		(void)hipEventRecord(h->ev[6], h->stream);
-		HIPCHK(h, hipMemcpyAsync(res_alns.get(), d_out, (size_t)mtot * sizeof(bwagpu_aln_t), hipMemcpyDeviceToHost, h->stream));
-		HIPCHK(h, hipMemcpyAsync(res_naln.get(), d_n, (size_t)n_reads * 4, hipMemcpyDeviceToHost, h->stream));
-		HIPCHK(h, hipMemcpyAsync(res_pri.get(), I.pri, (size_t)mtot * sizeof(bwagpu_primary_t), hipMemcpyDeviceToHost, h->stream));      // (as the decision kernels left them)
-		if (ext_n) HIPCHK(h, hipMemcpyAsync(res_ops.get(), S[bwagpu_s::SP_EXT].p, (size_t)ext_n * 4, hipMemcpyDeviceToHost, h->stream));
-		HIPCHK(h, wait_stream(h));
-		(void)hipEventElapsedTime(&ms[5], h->ev[5], h->ev[6]);
-		for (int p = 0; p < np; ++p) if (res_s[p].path == 1) { res_s[p].n_aa[0] = res_naln[2 * (size_t)p]; res_s[p].n_aa[1] = res_naln[2 * (size_t)p + 1]; }
+		if (!resident) {
+			HIPCHK(h, hipMemcpyAsync(res_alns.get(), d_out, (size_t)mtot * sizeof(bwagpu_aln_t), hipMemcpyDeviceToHost, h->stream));
+			HIPCHK(h, hipMemcpyAsync(res_naln.get(), d_n, (size_t)n_reads * 4, hipMemcpyDeviceToHost, h->stream));
+			HIPCHK(h, hipMemcpyAsync(res_pri.get(), I.pri, (size_t)mtot * sizeof(bwagpu_primary_t), hipMemcpyDeviceToHost, h->stream));      // (as the decision kernels left them)
+			if (ext_n) HIPCHK(h, hipMemcpyAsync(res_ops.get(), S[bwagpu_s::SP_EXT].p, (size_t)ext_n * 4, hipMemcpyDeviceToHost, h->stream));
+			HIPCHK(h, wait_stream(h));
+			(void)hipEventElapsedTime(&ms[5], h->ev[5], h->ev[6]);
+			for (int p = 0; p < np; ++p) if (res_s[p].path == 1) { res_s[p].n_aa[0] = res_naln[2 * (size_t)p]; res_s[p].n_aa[1] = res_naln[2 * (size_t)p + 1]; }
+		}
 	}
 	out->regs = res_regs.release(); out->src = res_src.release(); out->n_regs = mtot; out->rescue = res_resc.release(); out->pri = res_pri.release(); out->n_pri = res_npri.release();
 	out->pairs = res_pairs.release(); out->sampe = res_s.release(); out->cigs = res_cigs.release(); out->ops = res_ops.release(); out->n_ops = ext_n; out->alns = res_alns.release();
@@ -2894,6 +2924,102 @@ extern "C" int bwagpu_sampe_flat(bwagpu_t *h, const bwagpu_opt_t *opt, const bwa
 	HIPCHK(h, hipSetDevice(h->device));
 	const int rc = flat_pairs_upload(h, "sampe", n_pairs, seqs, off, counts_in, regs_in, ids, F, L);
 	return rc != BWAGPU_OK ? rc : sampe_run(h, opt, pes, L, h->d_rs[bwagpu_s::RS_SEQ].as<u8>(), h->d_rs[bwagpu_s::RS_SEQOFF].as<i64>(), max_len, n_pairs ? off[2 * n_pairs] - off[0] : 0, counts, out);
+}
+
+// ---- paired-end SAM text on the device (dev_samtext_pe.h) ---------------------------------------------------------------------------------------------
+extern "C" void bwagpu_sam_pe_limits(int32_t out[2]) { out[0] = SAM_STAGE; out[1] = SAM_STEP; }
+
+// mates carry one name (the reference dies on a pair that does not, bwamem_pair.c:386, :416)
+static int sam_pe_names_check(bwagpu_t *h, int n_pairs, const bwagpu_sam_in_t *in, const char *what)
+{
+	for (int p = 0; p < n_pairs; ++p) {
+		const i64 a = in->name_off[2 * (size_t)p], b = in->name_off[2 * (size_t)p + 1], c = in->name_off[2 * (size_t)p + 2];
+		if (b - a != c - b || memcmp(in->names + a, in->names + b, (size_t)(b - a)) != 0) {
+			h->err = std::string(what) + ": paired reads have different names (pair " + std::to_string(p) + ")"; return BWAGPU_EINVAL;
+		}
+	}
+	return BWAGPU_OK;
+}
+
+static void pe_out_free(bwagpu_pe_out_t *o)
+{
+	bwagpu_free(o->regs); bwagpu_free(o->src); bwagpu_free(o->rescue); bwagpu_free(o->pri); bwagpu_free(o->n_pri); bwagpu_free(o->pairs); bwagpu_free(o->sampe); bwagpu_free(o->cigs);
+	bwagpu_free(o->ops); bwagpu_free(o->alns); bwagpu_free(o->n_aln);
+	memset(o, 0, sizeof *o);
+}
+
+// Both entry points: sampe_run (its arguments), then the two passes of the formatter on the records it left on the device.  q_bases: bytes of in->quals.
+// Without pe, sampe_run leaves alignment records, patched marking records and the operation array where they are.
+static int sam_pe_run(bwagpu_t *h, const bwagpu_opt_t *opt, const bwagpu_pestat_t pes[4], const RegLists &L, const u8 *d_seq, const i64 *d_seqoff, int max_len, i64 n_bases, i64 q_bases,
+					  const bwagpu_sam_in_t *in, int32_t *counts, bwagpu_pe_out_t *pe, bwagpu_sam_out_t *out)
+{
+	const int n = L.n;
+	bwagpu_pe_out_t own; memset(&own, 0, sizeof own);
+	bwagpu_pe_out_t *P = pe ? pe : &own;
+	int rc = sampe_run(h, opt, pes, L, d_seq, d_seqoff, max_len, n_bases, counts, P, pe == nullptr);
+	if (rc != BWAGPU_OK) return rc;
+	if (n == 0) rc = sam_none(out);
+	else {
+		SamIn S = {};
+		rc = sam_upload(h, n, q_bases, in, S);
+		DevBuf *D = h->d_rs, *Sp = h->d_sp;
+		if (rc == BWAGPU_OK && P->n_regs == 0) {      // no region in the whole batch: the lists and pair records are the host's only
+			if (D[bwagpu_s::RS_ACNT].ensure((size_t)n * 4) || D[bwagpu_s::RS_POFF].ensure(((size_t)n + 1) * 8) || Sp[bwagpu_s::SP_OUT].ensure((size_t)(n / 2) * sizeof(bwagpu_sampe_t))) {
+				h->err = "hipMalloc failed (sam_pe)"; rc = BWAGPU_ENOMEM;
+			} else if (hipMemsetAsync(D[bwagpu_s::RS_ACNT].p, 0, (size_t)n * 4, h->stream) != hipSuccess || hipMemsetAsync(D[bwagpu_s::RS_POFF].p, 0, ((size_t)n + 1) * 8, h->stream) != hipSuccess ||
+					   hipMemcpyAsync(Sp[bwagpu_s::SP_OUT].p, P->sampe, (size_t)(n / 2) * sizeof(bwagpu_sampe_t), hipMemcpyHostToDevice, h->stream) != hipSuccess) {
+				h->err = "hipMemcpy failed (sam_pe)"; rc = BWAGPU_EHIP;
+			}
+		}
+		if (rc == BWAGPU_OK) {
+			S.alns = h->d_aln_out.as<bwagpu_aln_t>(); S.pri = h->d_pri_out.as<bwagpu_primary_t>(); S.cigs = Sp[bwagpu_s::SP_CIGS].as<bwagpu_cigar_t>(); S.ops = Sp[bwagpu_s::SP_EXT].as<u32>();
+			S.seq = d_seq; S.seq_off = d_seqoff;
+			const int e[4] = { 0, 1, 2, 3 };      // (ev[5], ev[6] hold sampe_run's last segment)
+			rc = sam_passes(h, opt, n, D[bwagpu_s::RS_ACNT].as<i32>(), D[bwagpu_s::RS_POFF].as<i64>(), S, Sp[bwagpu_s::SP_OUT].as<bwagpu_sampe_t>(), e, out);
+		}
+		if (rc == BWAGPU_OK) {
+			if (!pe && P->n_regs > 0) (void)hipEventElapsedTime(&P->kernel_ms[5], h->ev[5], h->ev[6]);
+			for (int k = 0; k < 6; ++k) out->kernel_ms[0] += P->kernel_ms[k];
+		}
+	}
+	if (!pe || rc != BWAGPU_OK) pe_out_free(P);
+	return rc;
+}
+
+extern "C" int bwagpu_batch_sam_pe(bwagpu_t *h, const bwagpu_opt_t *opt, const bwagpu_pestat_t pes[4], int64_t id0, const bwagpu_sam_in_t *in, int32_t *counts, bwagpu_pe_out_t *pe,
+								   bwagpu_sam_out_t *out)
+{
+	if (pe) memset(pe, 0, sizeof *pe);
+	if (out) memset(out, 0, sizeof *out);
+	if (!h || !opt || !pes || !h->ran || !h->downloaded || !in || !out || (h->n_reads > 0 && !counts)) return BWAGPU_EINVAL;
+	if ((h->n_reads & 1) || (id0 & 1) || opt->e_del <= 0 || opt->e_ins <= 0 || (opt->flag & 0x800 /* MEM_F_PRIMARY5 */)) return BWAGPU_EINVAL;
+	if (int rc = sam_in_check(h, h->n_reads, in, "bwagpu_batch_sam_pe")) return rc;
+	if (int rc = sam_pe_names_check(h, h->n_reads / 2, in, "bwagpu_batch_sam_pe")) return rc;
+	const BusyGuard busy(h->ibuf->busy);
+	HIPCHK(h, hipSetDevice(h->device));
+	return sam_pe_run(h, opt, pes, lists_of_batch(h, id0), h->d_seq.as<u8>(), h->d_off.as<i64>(), h->max_len, h->n_bases, h->n_bases, in, counts, pe, out);
+}
+
+extern "C" int bwagpu_sam_pe_flat(bwagpu_t *h, const bwagpu_opt_t *opt, const bwagpu_pestat_t pes[4], int n_pairs, const uint8_t *seqs, const int64_t *off, const int32_t *counts_in,
+								  const bwagpu_alnreg_t *regs_in, const int64_t *ids, const bwagpu_sam_in_t *in, int32_t *counts, bwagpu_pe_out_t *pe, bwagpu_sam_out_t *out)
+{
+	if (pe) memset(pe, 0, sizeof *pe);
+	if (out) memset(out, 0, sizeof *out);
+	if (!h || !opt || !pes || n_pairs < 0 || n_pairs > 0x1fffffff || !in || !out) return BWAGPU_EINVAL;
+	if (n_pairs > 0 && (!seqs || !off || !counts_in || !counts || !ids)) return BWAGPU_EINVAL;
+	if (opt->e_del <= 0 || opt->e_ins <= 0 || (opt->flag & 0x800 /* MEM_F_PRIMARY5 */)) return BWAGPU_EINVAL;
+	if (int rc = sam_in_check(h, 2 * n_pairs, in, "bwagpu_sam_pe_flat")) return rc;
+	if (int rc = sam_pe_names_check(h, n_pairs, in, "bwagpu_sam_pe_flat")) return rc;
+	FlatLists F; RegLists L;
+	if (!flat_pairs_ok(h, n_pairs, seqs, off, counts_in, regs_in, F)) return BWAGPU_EINVAL;
+	int max_len = 0;
+	for (int i = 0; i < 2 * n_pairs; ++i) max_len = std::max(max_len, (int)(off[i + 1] - off[i]));
+	const BusyGuard busy(h->ibuf->busy);
+	HIPCHK(h, hipSetDevice(h->device));
+	const int rc = flat_pairs_upload(h, "sam_pe", n_pairs, seqs, off, counts_in, regs_in, ids, F, L);
+	if (rc != BWAGPU_OK) return rc;
+	return sam_pe_run(h, opt, pes, L, h->d_rs[bwagpu_s::RS_SEQ].as<u8>(), h->d_rs[bwagpu_s::RS_SEQOFF].as<i64>(), max_len, n_pairs ? off[2 * n_pairs] - off[0] : 0, n_pairs ? off[2 * n_pairs] : 0,
+					  in, counts, pe, out);
 }
 
 extern "C" int bwagpu_align_flat(bwagpu_t *h, const bwagpu_opt_t *opt, int n, const uint8_t *seqs, const int64_t *off,

@@ -1,11 +1,12 @@
-// dev_samtext.h -- the SAM text of single-end reads on the device: mem_aln2sam (bwamem.c:851-976, add_cigar :838-849) for m == NULL, what mem_reg2sam
-// (bwamem.c:1033-1079) wraps around it, and the XA strings of mem_gen_alt (bwamem_extra.c:118-172).  bwagpu_batch_sam / bwagpu_sam_flat (bwagpu.hip).
+// dev_samtext.h -- the SAM text of reads on the device: mem_aln2sam (bwamem.c:851-976, add_cigar :838-849), what mem_reg2sam (bwamem.c:1033-1079) wraps
+// around it, and the XA strings of mem_gen_alt (bwamem_extra.c:118-172).  The kernels here are the single-end ones (m == NULL), bwagpu_batch_sam /
+// bwagpu_sam_flat (bwagpu.hip); the mate enters sam_line as a type (SamNoMate / SamMate), and the paired-end kernels are in dev_samtext_pe.h.
 //
 // Everything is read from what the earlier stages left in HBM: the alignment records (dev_alns.h), the marking records (dev_primary.h), the CIGAR records
 // with their operation array and packed MD strings (dev_cigar.h), the reads in nt4; besides them the names, qualities and comments of the reads and the
 // names and annotations of the contigs.
 //
-// One routine, sam_read<S>, writes all lines of a read into a sink S.  k_sam_size runs it on SamCount, which only counts; a prefix sum of the counts gives
+// One routine, sam_read<S, M>, writes all lines of a read into a sink S.  k_sam_size runs it on SamCount, which only counts; a prefix sum of the counts gives
 // every read its place in the batch's text; k_sam_write runs the same routine on SamWrite.  The two passes cannot disagree: there is one formatter.
 //
 // Mapping: one wavefront per read in both passes, and the formatter's control flow is wave-uniform -- every lane runs every statement with the same values.
@@ -210,17 +211,50 @@ DEVFN bool sam_declined(const bwagpu_opt_t &opt, const SamRead &Q, int lane)
 	return bad;
 }
 
-// One line: place k of the marked list as line `which` of the read, or (k < 0) the unmapped record of mem_reg2aln(.., NULL)
-template <class S> DEVFN void sam_line(S &s, const bwagpu_opt_t &opt, const SamIn &I, const SamRead &Q, int k, int which, int lane)
+// The mate as mem_aln2sam's last argument: SamNoMate is m == NULL -- a type, so that the single-end kernels carry nothing of what a mate adds
+struct SamNoMate { static constexpr bool present = false; };
+struct SamMate {
+	static constexpr bool present = true;
+	const bwagpu_aln_t *a;        // the mate's record, or (null) mem_reg2aln(.., NULL): no coordinate
+	const bwagpu_cigar_t *c;      // its region's CIGAR record
+	int mapq;                     // what MQ prints
+	int rlen;                     // get_rlen of the mate's final CIGAR
+	int flag;                     // 0x40 << end | the pair's extra_flag
+};
+
+// get_rlen (bwamem.c:827-836) of record R's final CIGAR: the M and D operations without a dropped deletion (the clips count nothing)
+DEVFN int sam_rlen(const SamIn &I, const bwagpu_aln_t &R, const bwagpu_cigar_t *c)
+{
+	const int nc = c->n_cigar;
+	const u32 *o = nc <= 6 ? c->cigar : I.ops + ((u64)c->cigar[1] << 32 | c->cigar[0]);
+	const int lo = (R.flags & BWAGPU_ALN_DEL5) ? 1 : 0, hi = nc - ((R.flags & BWAGPU_ALN_DEL3) ? 1 : 0);
+	int l = 0;
+	for (int j = lo; j < hi; ++j) { const u32 x = o[j]; if ((x & 0xf) == 0 || (x & 0xf) == 2) l += (int)(x >> 4); }
+	return l;
+}
+
+// One line: place k of the marked list as line `which` of the read, or (k < 0) the unmapped record of mem_reg2aln(.., NULL); mate: mem_aln2sam's m
+template <class S, class M> DEVFN void sam_line(S &s, const bwagpu_opt_t &opt, const SamIn &I, const SamRead &Q, int k, int which, int lane, const M &mate)
 {
 	bwagpu_aln_t R;
 	R.pos = -1; R.rid = -1; R.flag = 0x4; R.mapq = 0; R.mapq_out = 0; R.nm = 0; R.n_cigar = 0; R.score = 0; R.sub = 0; R.alt_sc = 0; R.sel = 0; R.clip5 = 0; R.clip3 = 0; R.flags = 0; R.pad_ = 0;
 	const bwagpu_cigar_t *c = nullptr;
 	if (k >= 0) { R = Q.alns[k]; c = Q.cigs + Q.pri[k].src; }
-	const bool rev = (R.flags & BWAGPU_ALN_REV) != 0, alt = (R.flags & BWAGPU_ALN_ALT) != 0;
+	bool rev = (R.flags & BWAGPU_ALN_REV) != 0;
+	const bool alt = (R.flags & BWAGPU_ALN_ALT) != 0;
 	const bool has_cigar = R.rid >= 0 && R.n_cigar > 0;
 	const bool hard = which && !(opt.flag & 0x200 /* MEM_F_SOFTCLIP */) && !alt;
-	const int flag = R.flag | I.extra_flag | (R.rid < 0 ? 0x4 : 0) | (rev ? 0x10 : 0);
+	int flag = R.flag | I.extra_flag | (R.rid < 0 ? 0x4 : 0);
+	i64 mpos = -1; int mrid = -1; bool mrev = false, mcig = false;      // the mate's columns (:858-866)
+	if constexpr (M::present) {
+		flag |= 0x1 | mate.flag;
+		if (mate.a && mate.a->rid >= 0) { mrid = mate.a->rid; mpos = mate.a->pos; mrev = (mate.a->flags & BWAGPU_ALN_REV) != 0; mcig = mate.a->n_cigar > 0; }
+		if (mrid < 0) flag |= 0x8;
+		if (R.rid < 0 && mrid >= 0) { R.rid = mrid; R.pos = mpos; rev = mrev; }      // copy mate to alignment: n_cigar = 0, which has_cigar says already
+		else if (mrid < 0 && R.rid >= 0) { mrid = R.rid; mpos = R.pos; mrev = rev; }      // copy alignment to mate: n_cigar = 0, as mcig says already
+		if (mrev) flag |= 0x20;
+	}
+	if (rev) flag |= 0x10;
 	sam_bytes(s, Q.name, Q.l_name); sam_ch(s, '\t');
 	sam_int(s, (flag & 0xffff) | (flag & 0x10000 ? 0x100 : 0)); sam_ch(s, '\t');
 	if (R.rid >= 0) {
@@ -229,7 +263,18 @@ template <class S> DEVFN void sam_line(S &s, const bwagpu_opt_t &opt, const SamI
 		sam_int(s, R.mapq_out); sam_ch(s, '\t');
 		if (has_cigar) sam_cigar(s, I, R, c, hard ? 'H' : 'S'); else sam_ch(s, '*');
 	} else sam_lit(s, "*\t0\t0\t*");
-	sam_lit(s, "\t*\t0\t0\t");
+	if constexpr (M::present) {
+		sam_ch(s, '\t');
+		if (mrid >= 0) {      // :882-893
+			if (R.rid == mrid) sam_ch(s, '='); else sam_ctg_name(s, I, mrid);
+			sam_ch(s, '\t'); sam_int(s, mpos + 1); sam_ch(s, '\t');
+			if (R.rid == mrid && has_cigar && mcig) {
+				const i64 p0 = R.pos + (rev ? sam_rlen(I, R, c) - 1 : 0), p1 = mpos + (mrev ? mate.rlen - 1 : 0);
+				sam_int(s, -(p0 - p1 + (p0 > p1 ? 1 : p0 < p1 ? -1 : 0)));
+			} else sam_ch(s, '0');
+		} else sam_lit(s, "*\t0\t0");
+		sam_ch(s, '\t');
+	} else sam_lit(s, "\t*\t0\t0\t");
 	if (flag & 0x100) sam_lit(s, "*\t*");
 	else {
 		int qb = 0, qe = Q.l_seq;
@@ -243,6 +288,13 @@ template <class S> DEVFN void sam_line(S &s, const bwagpu_opt_t &opt, const SamI
 		else sam_bytes(s, Q.qual + qb, len);
 	}
 	if (has_cigar) { sam_lit(s, "\tNM:i:"); sam_int(s, R.nm); sam_lit(s, "\tMD:Z:"); sam_md(s, I, c); }
+	if constexpr (M::present) {
+		if (mcig) {      // add_cigar(opt, m, str, which): this line's `which`, the mate's ALT bit
+			sam_lit(s, "\tMC:Z:");
+			sam_cigar(s, I, *mate.a, mate.c, which && !(opt.flag & 0x200 /* MEM_F_SOFTCLIP */) && !(mate.a->flags & BWAGPU_ALN_ALT) ? 'H' : 'S');
+		}
+		sam_lit(s, "\tMQ:i:"); sam_int(s, mate.mapq);
+	}
 	if (R.score >= 0) { sam_lit(s, "\tAS:i:"); sam_int(s, R.score); }
 	if (R.sub >= 0) { sam_lit(s, "\tXS:i:"); sam_int(s, R.sub); }
 	if (I.rg_len) { sam_lit(s, "\tRG:Z:"); sam_bytes(s, I.rg, I.rg_len); }
@@ -291,7 +343,7 @@ template <class S> DEVFN void sam_line(S &s, const bwagpu_opt_t &opt, const SamI
 }
 
 // all lines of a read (mem_reg2sam's second loop); returns their number
-template <class S> DEVFN int sam_read(S &s, const bwagpu_opt_t &opt, const SamIn &I, const SamRead &Q, int lane)
+template <class S, class M> DEVFN int sam_read(S &s, const bwagpu_opt_t &opt, const SamIn &I, const SamRead &Q, int lane, const M &mate)
 {
 	int which = 0;
 	for (int base = 0; base < Q.n || which == 0; base += SAM_STEP) {
@@ -299,7 +351,7 @@ template <class S> DEVFN int sam_read(S &s, const bwagpu_opt_t &opt, const SamIn
 		unsigned long long m = __ballot(i < Q.n && Q.alns[i].sel >= 0);
 		const bool none = base + SAM_STEP >= Q.n && which == 0 && m == 0;      // the list is through and nothing was printed: the unmapped record (one call site for both)
 		if (none) m = 1;
-		for (; m; m &= m - 1) sam_line(s, opt, I, Q, none ? -1 : base + __ffsll(m) - 1, which++, lane);
+		for (; m; m &= m - 1) sam_line(s, opt, I, Q, none ? -1 : base + __ffsll(m) - 1, which++, lane, mate);
 	}
 	return which;
 }
@@ -327,7 +379,7 @@ __global__ void __launch_bounds__(64) k_sam_size(bwagpu_opt_t opt, int n_reads, 
 		SamCount s; s.n = 0;
 		int lines = 0;
 		const bool declined = sam_declined(opt, Q, lane);
-		if (!declined) lines = sam_read(s, opt, I, Q, lane);
+		if (!declined) lines = sam_read(s, opt, I, Q, lane, SamNoMate());
 		if (lane == 0) { size[r] = (i32)s.n; flags[r] = declined ? 1 : 0; n_lines[r] = lines; }
 	}
 }
@@ -341,7 +393,7 @@ __global__ void __launch_bounds__(64) k_sam_write(bwagpu_opt_t opt, int n_reads,
 		if (flags[r] & 1) continue;
 		const SamRead Q = sam_view(I, cnt, off, r);
 		SamWrite s; s.out = text + toff[r]; s.stage = stage; s.fill = 0; s.lane = lane;
-		sam_read(s, opt, I, Q, lane);
+		sam_read(s, opt, I, Q, lane, SamNoMate());
 		s.flush();
 	}
 }

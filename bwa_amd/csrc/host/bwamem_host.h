@@ -82,10 +82,11 @@ struct Read {   // == bseq1_t as the finalize code needs it
 	const bwagpu_pair_t *pair = nullptr;                   // first read of a pair: the device's mem_pair record of the pair as downloaded (bwagpu_batch_pair); both reads then have `pri`
 	const bwagpu_alnreg_t *merged = nullptr; int n_merged = 0;   // this read's list after the device's merge of mate-rescue hits (bwagpu_batch_rescue); `pri` then describes this list
 	const bwagpu_sampe_t *sampe = nullptr;                 // first read of a pair: the device's decision of the pair (bwagpu_batch_sampe); both reads then have `merged`, `pri` (as mem_sam_pe leaves the lists), `alns` and `hints` of the merged lists
-	const char *dev_text = nullptr; int64_t n_dev_text = 0;   // single-end: the read's lines as the device wrote them (bwagpu_batch_sam); null: the read is formatted here
+	const char *dev_text = nullptr; int64_t n_dev_text = 0;   // the read's lines as the device wrote them (bwagpu_batch_sam; paired-end, bwagpu_batch_sam_pe: both reads of a pair or neither); null: the read is formatted here
 	const bwagpu_rescue_t *rescue = nullptr;               // first read of a pair: what that merge did with the pair; `pair` is then the record of the merged lists
 };
 extern std::atomic<long> g_pairs_merged_on_device, g_pairs_merged_aligned;   // pairs whose merged lists sam_pe took from the device; those of them with rescue alignments
+extern std::atomic<long> g_pairs_from_samtext;            // pairs whose text sam_pe took from the device (bwagpu_batch_sam_pe)
 extern std::atomic<long> g_pairs_from_sampe;              // pairs sam_pe finished from the device's pair records (bwagpu_batch_sampe)
 extern std::atomic<long> g_pairs_from_device;             // pairs whose marking and mem_pair result sam_pe took from the device's records
 

@@ -283,7 +283,7 @@ int64_t host_matesw_records(const bwagpu_opt_t &opt, const RefSeqs &ref, int n, 
 	return nout;
 }
 
-std::atomic<long> g_pairs_from_device(0), g_pairs_merged_on_device(0), g_pairs_merged_aligned(0), g_pairs_from_sampe(0);
+std::atomic<long> g_pairs_from_device(0), g_pairs_merged_on_device(0), g_pairs_merged_aligned(0), g_pairs_from_sampe(0), g_pairs_from_samtext(0);
 
 // ---- pairing (mem_pair, bwamem_pair.c:208-274) --------------------------------------------------------------------------------
 static int pair_ends(const bwagpu_opt_t &opt, const RefSeqs &ref, const Pestat pes[4], const Regs a[2], int id, int *sub, int *n_sub, int z[2], const int n_pri[2])
@@ -355,6 +355,11 @@ int sam_pe(const bwagpu_opt_t &opt, const RefSeqs &ref, const Pestat pes[4], uin
 	int n = 0, z[2] = {0, 0}, o = 0, subo = 0, n_sub = 0, extra_flag = 1, n_pri[2];
 	Aln h[2];
 	SamText &out0 = *outp[0], &out1 = *outp[1];
+	if (s[0].dev_text && s[1].dev_text) {      // the pair's text as the device wrote it (bwagpu_batch_sam_pe)
+		out0.append(s[0].dev_text, (size_t)s[0].n_dev_text); out1.append(s[1].dev_text, (size_t)s[1].n_dev_text);
+		++g_pairs_from_samtext;
+		return 0;
+	}
 	out0.reserve(out0.size() + 2 * (size_t)s[0].l_seq + 320); out1.reserve(out1.size() + 2 * (size_t)s[1].l_seq + 320);      // one allocation instead of the five a growing string makes
 	// The device's merge (bwagpu_batch_rescue): the lists as the loop below would leave them, with the marking records and the pair record of those lists.  A pair
 	// the device flagged, or whose pair record is flagged, runs the host code unchanged.

@@ -46,7 +46,8 @@ static int g_device_primary = 0;  // BWAGPU_CLI_PRIMARY=1: single-end batches ta
 static int g_device_sampe = 0;    // BWAGPU_CLI_SAMPE=1: paired-end batches without -5 take the whole of mem_sam_pe up to the text from the device (bwagpu_batch_sampe, in place of bwagpu_batch_cigars and bwagpu_batch_rescue; conditions: BWAGPU_CLI_RESCUE's, device CIGARs on; same output)
 static int g_device_alns = 0;     // BWAGPU_CLI_ALNS=1: single-end batches without -5 also take every region's alignment record and the read's list from the device (bwagpu_batch_alns, after the CIGAR call; same output)
 static std::atomic<long> g_n_alns_reads(0);      // ... reads finalized from such records
-static int g_device_samtext = 0;  // BWAGPU_CLI_SAMTEXT=1: single-end batches without -5 take their SAM text from the device (bwagpu_batch_sam, after the CIGAR call, in place of bwagpu_batch_alns / bwagpu_batch_primary; device CIGARs on; same output); a read the device declines goes through the host formatter
+static int g_device_samtext = 0;  // BWAGPU_CLI_SAMTEXT=1: single-end batches without -5 take their SAM text from the device (bwagpu_batch_sam, after the CIGAR call, in place of bwagpu_batch_alns / bwagpu_batch_primary; device CIGARs on; same output); a read the device declines goes through the host formatter.
+                                  // Paired-end batches, under BWAGPU_CLI_SAMPE's conditions (whether or not that switch is set): bwagpu_batch_sam_pe in place of every device call behind the download; a pair the device declines runs the host's mem_sam_pe on the download's lists
 static std::atomic<long> g_n_samtext_reads(0);   // ... reads written from such text
 static std::string g_dev_rg_id; static bool g_dev_copy_comment = false;      // -R's id and -C for that call (set before the stages start)
 static std::atomic<long> g_n_primary_reads(0);   // ... reads finalized from such records (the BWAGPU_CLI_TRACE line at the end of the run)
@@ -505,8 +506,9 @@ static void device_sub(const std::vector<bwagpu_t*> &gpus, Sub &u, const RefSeqs
 	}
 	// BWAGPU_CLI_SAMPE: the whole of mem_sam_pe up to the text in one call per shard further down, CIGAR records of the merged lists included -- it stands for the CIGAR
 	// call on the download's lists too (a pair the device declines has the download's lists as its merged lists, so its records are there as well)
-	const bool dev_sampe = g_device_sampe && g_device_cigars && pe && u.have_pes && !(u.opt.flag & (F_PRIMARY5 | F_NOPAIRING)) && !(u.n_processed & 1) && u.tot > 0;
-	const bool have_cigs = g_device_cigars && u.tot > 0 && !dev_sampe;
+	const bool dev_sam_pe = g_device_samtext && g_device_cigars && pe && in && u.have_pes && !(u.opt.flag & (F_PRIMARY5 | F_NOPAIRING)) && !(u.n_processed & 1) && u.tot > 0;
+	const bool dev_sampe = !dev_sam_pe && g_device_sampe && g_device_cigars && pe && u.have_pes && !(u.opt.flag & (F_PRIMARY5 | F_NOPAIRING)) && !(u.n_processed & 1) && u.tot > 0;
+	const bool have_cigs = g_device_cigars && u.tot > 0 && !dev_sampe && !dev_sam_pe;
 	if (have_cigs) on_devices([&](int d) {       // the DP of mem_reg2aln, NM and MD on the device as well; the host keeps the text
 		Shard &s = sh[d];
 		if (s.tot == 0) return;
@@ -611,10 +613,45 @@ static void device_sub(const std::vector<bwagpu_t*> &gpus, Sub &u, const RefSeqs
 	}
 	t4 = now_s();
 	if (pes_thread.joinable()) pes_thread.join();
+	// The text of paired-end batches: one call per shard runs bwagpu_batch_sampe's kernels and formats every pair from their resident records -- no record comes to
+	// the host, and the calls below (rescue, pairing, mate-rescue alignments) are not made.  A pair the device declines, and every pair of a shard that is not
+	// formatted, runs the host's mem_sam_pe on the download's lists.
+	if (dev_sam_pe) {
+		bwagpu_pestat_t dp[4];
+		for (int d = 0; d < 4; ++d) { memset(&dp[d], 0, sizeof dp[d]); dp[d].low = u.pes[d].low; dp[d].high = u.pes[d].high; dp[d].failed = u.pes[d].failed; dp[d].avg = u.pes[d].avg; dp[d].std = u.pes[d].std; }
+		u.sam.assign((size_t)D, bwagpu_sam_out_t()); u.sam_lo.assign((size_t)D, 0);
+		on_devices([&](int d) {
+			Shard &s = sh[d];
+			u.sam_lo[(size_t)d] = s.lo;
+			memset(&u.sam[(size_t)d], 0, sizeof(bwagpu_sam_out_t));
+			if (s.tot == 0) return;      // (no region: the host prints the shard's unmapped records)
+			const int m = s.hi - s.lo;
+			int n_qual = 0;
+			for (int i = s.lo; i < s.hi; ++i) n_qual += in->seqs[u.idx[i]].has_qual;
+			if (n_qual != 0 && n_qual != m) return;      // (qualities for some reads only: the host formatter)
+			std::string names, quals, comments; std::vector<int64_t> name_off(1, 0), comment_off(1, 0);
+			for (int i = s.lo; i < s.hi; ++i) {
+				const Seq &q = in->seqs[u.idx[i]];
+				const char *T = in->T(q);
+				if ((i & 1) && strcmp(T + q.name, in->T(in->seqs[u.idx[i - 1]]) + in->seqs[u.idx[i - 1]].name) != 0) return;      // (mates of different names: the finalize stage reports them as the reference does)
+				names += T + q.name; name_off.push_back((int64_t)names.size());
+				if (n_qual) quals.append(T + q.qual, (size_t)q.l_seq);
+				if (g_dev_copy_comment && q.has_comment) comments += T + q.comment;
+				comment_off.push_back((int64_t)comments.size());
+			}
+			bwagpu_sam_in_t si; memset(&si, 0, sizeof si);
+			si.names = names.data(); si.name_off = name_off.data(); si.quals = n_qual ? quals.data() : nullptr;
+			if (g_dev_copy_comment) { si.comments = comments.data(); si.comment_off = comment_off.data(); }
+			si.rg_id = g_dev_rg_id.c_str();
+			std::vector<int32_t> m_counts((size_t)m);
+			const int rc = bwagpu_batch_sam_pe(gpus[d], &u.opt, dp, u.n_processed + s.lo, &si, m_counts.data(), nullptr, &u.sam[(size_t)d]);
+			if (rc != BWAGPU_OK) device_fail(gpus[d], rc);
+		});
+	}
 	// mem_pair of the pairs as downloaded, and the marking of their ends, on the device too: the windows are known here.  Read i of the batch has id
 	// n_processed + i (mem_sam_pe: id << 1 | r with id = (n_processed + i) >> 1); a shard starts at an even read.
 	// The merge of mate-rescue hits, the marking of the merged lists and mem_pair on those records in one call, under the same conditions: it stands for both blocks below.
-	const bool dev_rescue = (g_device_rescue || dev_sampe) && pe && u.have_pes && !(u.opt.flag & (F_PRIMARY5 | F_NOPAIRING)) && !(u.n_processed & 1) && u.tot > 0;
+	const bool dev_rescue = !dev_sam_pe && (g_device_rescue || dev_sampe) && pe && u.have_pes && !(u.opt.flag & (F_PRIMARY5 | F_NOPAIRING)) && !(u.n_processed & 1) && u.tot > 0;
 	if (dev_rescue) {
 		bwagpu_pestat_t dp[4];
 		for (int d = 0; d < 4; ++d) { memset(&dp[d], 0, sizeof dp[d]); dp[d].low = u.pes[d].low; dp[d].high = u.pes[d].high; dp[d].failed = u.pes[d].failed; dp[d].avg = u.pes[d].avg; dp[d].std = u.pes[d].std; }
@@ -669,7 +706,7 @@ static void device_sub(const std::vector<bwagpu_t*> &gpus, Sub &u, const RefSeqs
 			bwagpu_free(s.m_all); s.m_all = nullptr; bwagpu_free(s.m_src); s.m_src = nullptr; bwagpu_free(s.rescue); s.rescue = nullptr; bwagpu_free(s.pri); s.pri = nullptr; bwagpu_free(s.pairs); s.pairs = nullptr;
 		}
 	}
-	if (!dev_rescue && g_device_pair && pe && u.have_pes && !(u.opt.flag & (F_PRIMARY5 | F_NOPAIRING)) && !(u.n_processed & 1) && u.tot > 0) {
+	if (!dev_rescue && !dev_sam_pe && g_device_pair && pe && u.have_pes && !(u.opt.flag & (F_PRIMARY5 | F_NOPAIRING)) && !(u.n_processed & 1) && u.tot > 0) {
 		bwagpu_pestat_t dp[4];
 		for (int d = 0; d < 4; ++d) { memset(&dp[d], 0, sizeof dp[d]); dp[d].low = u.pes[d].low; dp[d].high = u.pes[d].high; dp[d].failed = u.pes[d].failed; dp[d].avg = u.pes[d].avg; dp[d].std = u.pes[d].std; }
 		on_devices([&](int d) {
@@ -689,7 +726,7 @@ static void device_sub(const std::vector<bwagpu_t*> &gpus, Sub &u, const RefSeqs
 			k += s.tot; bwagpu_free(s.pri); s.pri = nullptr; bwagpu_free(s.pairs); s.pairs = nullptr;
 		}
 	}
-	if (want_matesw && !dev_rescue) {
+	if (want_matesw && !dev_rescue && !dev_sam_pe) {
 		bwagpu_pes_t dp[4];
 		for (int d = 0; d < 4; ++d) { dp[d].low = u.pes[d].low; dp[d].high = u.pes[d].high; dp[d].failed = u.pes[d].failed; dp[d].pad_ = 0; }
 		on_devices([&](int d) {
@@ -778,7 +815,7 @@ static void finalize_sub(const RefSeqs &ref, Work &w, Sub &u, const Pestat *pes0
 	if (u.pairs) { free(u.pairs); u.pairs = nullptr; free(u.pri); u.pri = nullptr; }
 	if (!u.sam.empty()) {
 		long k = 0;
-		for (int i = 0; i < n; ++i) k += reads[i].dev_text != nullptr;
+		if (!(u.opt.flag & F_PE)) for (int i = 0; i < n; ++i) k += reads[i].dev_text != nullptr;      // (pairs are counted where they are appended: g_pairs_from_samtext)
 		g_n_samtext_reads += k;
 		for (bwagpu_sam_out_t &o : u.sam) { bwagpu_free(o.text); bwagpu_free(o.off); bwagpu_free(o.flags); bwagpu_free(o.n_lines); }
 		u.sam.clear(); u.sam_lo.clear();
@@ -1265,6 +1302,7 @@ int main(int argc, char *argv[])
 	if (g_device_pair && tl_trace) fprintf(stderr, "[D::main_mem] %ld pairs paired from device records (BWAGPU_CLI_PAIR)\n", hostmem::g_pairs_from_device.load());
 	if (g_device_sampe && tl_trace) fprintf(stderr, "[D::main_mem] %ld pairs finished from the device's pair records (BWAGPU_CLI_SAMPE)\n", hostmem::g_pairs_from_sampe.load());
 	if (g_device_samtext && tl_trace) fprintf(stderr, "[D::main_mem] %ld reads written from device SAM text (BWAGPU_CLI_SAMTEXT)\n", g_n_samtext_reads.load());
+	if (g_device_samtext && (tl_trace || g_verbose >= 4)) fprintf(stderr, "[D::main_mem] %ld pairs written from device SAM text (BWAGPU_CLI_SAMTEXT)\n", hostmem::g_pairs_from_samtext.load());
 	if (g_device_alns && tl_trace) fprintf(stderr, "[D::main_mem] %ld reads finalized from device alignment records (BWAGPU_CLI_ALNS)\n", g_n_alns_reads.load());
 	if (g_device_primary && tl_trace) fprintf(stderr, "[D::main_mem] %ld reads finalized from device primary/mapQ records (BWAGPU_CLI_PRIMARY)\n", g_n_primary_reads.load());
 	if (g_verbose >= 3) { const double dt = now_s() - t_start; fprintf(stderr, "[M::%s] %ld reads in %.3f sec after the index was loaded: %.0f reads/s\n", "main_mem", n_reads_total.load(), dt, dt > 0 ? n_reads_total.load() / dt : 0.);

@@ -512,6 +512,24 @@ int  bwagpu_sampe_flat(bwagpu_t *h, const bwagpu_opt_t *opt, const bwagpu_pestat
 void bwagpu_sampe_limits(int32_t out[2]);
 int  bwagpu_sampe_size(void);   /* sizeof(bwagpu_sampe_t) as compiled */
 
+/* The SAM text of read pairs on the device: what mem_sam_pe prints (bwamem_pair.c:360-385, :397-415) -- mem_aln2sam with a mate: flag bits 0x1 / 0x8 / 0x20 /
+ * 0x40 / 0x80 and the pair's extra_flag, the two copy rules for an unmapped end, RNEXT / PNEXT / TLEN, MC:Z: and MQ:i:.  The kernels of bwagpu_batch_sampe run
+ * first; the formatter of bwagpu_batch_sam then reads their resident records (alignment, patched marking and CIGAR records, the pair records), one wavefront per
+ * read.  `in` describes all 2 * n_pairs reads; in->extra_flag is ORed into every line.  With pe == NULL the alignment records, the marking records and the
+ * operation array do not come to the host; with pe the pair output is exactly bwagpu_batch_sampe's.  A pair is declined as a whole (no bytes, bit 0 of both reads'
+ * flag words; the caller runs mem_sam_pe's text for it): its bwagpu_sampe_t has flags & 1 or path < 0, or an end is declined by bwagpu_batch_sam's rule, or
+ * an end's mate place (z[1 - i]) has BWAGPU_ALN_NOCIGAR; nothing else is.  out->kernel_ms[0] is the sum of bwagpu_batch_sampe's six segments.
+ * BWAGPU_EINVAL: bwagpu_batch_sampe's cases, bwagpu_batch_sam's (contig names, offsets), and mates whose names differ (bwagpu_last_error names the pair; the
+ * reference dies on them) -- all checked before anything is launched. */
+int  bwagpu_batch_sam_pe(bwagpu_t *h, const bwagpu_opt_t *opt, const bwagpu_pestat_t pes[4], int64_t id0, const bwagpu_sam_in_t *in, int32_t *counts,
+		bwagpu_pe_out_t *pe /* may be NULL */, bwagpu_sam_out_t *out);
+/* The same on reads and lists of the caller: bwagpu_sampe_flat's inputs; in->quals follows `off`. */
+int  bwagpu_sam_pe_flat(bwagpu_t *h, const bwagpu_opt_t *opt, const bwagpu_pestat_t pes[4], int n_pairs, const uint8_t *seqs, const int64_t *off,
+		const int32_t *counts_in, const bwagpu_alnreg_t *regs_in, const int64_t *ids, const bwagpu_sam_in_t *in, int32_t *counts,
+		bwagpu_pe_out_t *pe /* may be NULL */, bwagpu_sam_out_t *out);
+/* as bwagpu_sam_limits */
+void bwagpu_sam_pe_limits(int32_t out[2]);
+
 /* ---- index construction on the device -------------------------------------------------------- */
 /* The arrays `bwa index` leaves in bwt_t after bwt_bwtgen2/bwt_pac2bwt + bwt_bwtupdate_core + bwt_cal_sa
  * (bwtindex.c:64-120, 150-172; bwt.c:62-84), built from the 2-bit packed forward strand by a suffix sort in HBM
