@@ -645,3 +645,96 @@ class BwaGpu:
         p, n = C.c_void_p(), C.c_int64()
         self._chk(self.L.bwagpu_tap_regs_raw(self.h, counts.ctypes.data, C.byref(p), C.byref(n)))
         return counts, self._take(p, n.value, ALNREG_DTYPE)
+
+
+FASTQ_REC_DTYPE = np.dtype([("file", "<i4"), ("has_comment", "<i4"), ("name", "<i4"), ("l_name", "<i4"), ("comment", "<i4"), ("l_comment", "<i4"),
+                            ("seq", "<i4"), ("l_seq", "<i4"), ("qual", "<i4"), ("l_qual", "<i4")])   # bwagpu_fastq_rec_t
+assert FASTQ_REC_DTYPE.itemsize == 40
+FQ_CUT, FQ_END, FQ_MORE, FQ_DECLINED = 0, 1, 2, 3
+
+
+class FastqOut(C.Structure):
+    """bwagpu_fastq_out_t"""
+    _fields_ = [("status", C.c_int32), ("n_reads", C.c_int32), ("consumed", C.c_int64 * 2), ("declined_file", C.c_int32), ("declined_at", C.c_int64),
+                ("seqs", C.c_void_p), ("off", C.c_void_p), ("names", C.c_void_p), ("name_off", C.c_void_p), ("quals", C.c_void_p),
+                ("comments", C.c_void_p), ("comment_off", C.c_void_p), ("has_comment", C.c_void_p), ("recs", C.c_void_p), ("kernel_ms", C.c_float * 3)]
+
+
+class FastqParser:
+    """The device FASTQ reader (bwagpu_fastq_*): windows of FASTQ text in, the batch bseq_read would cut from them out.  It needs no index.
+    lib_path selects another build of the library (the CPU tests pass the mock-runtime one); there is no CPU implementation."""
+
+    def __init__(self, device: int = 0, lib_path: str | None = None):
+        self.L = L = load_library(lib_path)
+        P = C.c_void_p
+        L.bwagpu_fastq_begin.argtypes = [C.POINTER(P), C.c_int, C.c_char_p, C.c_size_t]
+        L.bwagpu_fastq_reserve.argtypes = [P, C.c_int64]
+        L.bwagpu_fastq_batch.argtypes = [P, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p]
+        L.bwagpu_fastq_out_free.argtypes = [C.c_void_p]
+        L.bwagpu_fastq_out_free.restype = None
+        L.bwagpu_fastq_end.argtypes = [P]
+        L.bwagpu_fastq_end.restype = None
+        L.bwagpu_fastq_last_error.argtypes = [P]
+        L.bwagpu_fastq_last_error.restype = C.c_char_p
+        assert L.bwagpu_fastq_rec_size() == FASTQ_REC_DTYPE.itemsize
+        self.h = P()
+        err = C.create_string_buffer(512)
+        rc = L.bwagpu_fastq_begin(C.byref(self.h), device, err, 512)
+        if rc != 0:
+            self.h = P()
+            raise BwaGpuError(f"bwagpu_fastq_begin failed: {L.bwagpu_strerror(rc).decode()} {err.value.decode()}")
+
+    def _chk(self, rc, what):
+        if rc != 0:
+            raise BwaGpuError(f"{what} failed ({rc}): {self.L.bwagpu_strerror(rc).decode()} {self.L.bwagpu_fastq_last_error(self.h).decode()}")
+
+    def reserve(self, window_bytes: int):
+        self._chk(self.L.bwagpu_fastq_reserve(self.h, int(window_bytes)), "bwagpu_fastq_reserve")
+
+    def batch_rc(self, raw1, len1, eof1, raw2, len2, eof2, chunk_size, out):
+        """the bare call (tests of the error paths): returns the library's code"""
+        return self.L.bwagpu_fastq_batch(self.h, raw1, len1, eof1, raw2, len2, eof2, chunk_size, out)
+
+    def batch(self, raw1, raw2=None, chunk_size: int = 10_000_000, eof=(True, True)) -> dict:
+        """raw1 / raw2: bytes-like windows, each starting at a record start (raw2 None: one file).  Returns a dict with status (FQ_*),
+        n_reads, consumed, declined_file, declined_at, kernel_ms and -- for FQ_CUT / FQ_END -- copies of the arrays: seqs (nt4), off,
+        names, name_off, quals, comments, comment_off, has_comment, recs."""
+        b1 = np.frombuffer(raw1, dtype=np.uint8) if len(raw1) else np.zeros(1, dtype=np.uint8)
+        b2 = None if raw2 is None else (np.frombuffer(raw2, dtype=np.uint8) if len(raw2) else np.zeros(1, dtype=np.uint8))
+        o = FastqOut()
+        rc = self.L.bwagpu_fastq_batch(self.h, b1.ctypes.data, len(raw1), int(bool(eof[0])), None if b2 is None else b2.ctypes.data,
+                                       0 if raw2 is None else len(raw2), int(bool(eof[1])), int(chunk_size), C.byref(o))
+        self._chk(rc, "bwagpu_fastq_batch")
+        r = {"status": int(o.status), "n_reads": int(o.n_reads), "consumed": (int(o.consumed[0]), int(o.consumed[1])),
+             "declined_file": int(o.declined_file), "declined_at": int(o.declined_at), "kernel_ms": tuple(float(x) for x in o.kernel_ms)}
+        try:
+            if o.status in (FQ_CUT, FQ_END):
+                n = int(o.n_reads)
+
+                def take(ptr, count, dtype):
+                    if count == 0:
+                        return np.zeros(0, dtype=dtype)
+                    return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_uint8)), shape=(count * np.dtype(dtype).itemsize,)).view(dtype).copy()
+
+                for k in ("off", "name_off", "comment_off"):
+                    r[k] = take(getattr(o, k), n + 1, np.int64)
+                r["seqs"] = take(o.seqs, int(r["off"][n]), np.uint8)
+                r["quals"] = take(o.quals, int(r["off"][n]), np.uint8).tobytes()
+                r["names"] = take(o.names, int(r["name_off"][n]), np.uint8).tobytes()
+                r["comments"] = take(o.comments, int(r["comment_off"][n]), np.uint8).tobytes()
+                r["has_comment"] = take(o.has_comment, n, np.uint8)
+                r["recs"] = take(o.recs, n, FASTQ_REC_DTYPE)
+        finally:
+            self.L.bwagpu_fastq_out_free(C.byref(o))
+        return r
+
+    def close(self):
+        if self.h:
+            self.L.bwagpu_fastq_end(self.h)
+            self.h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()

@@ -40,6 +40,7 @@ typedef unsigned char u8;
 #define IDX_RANK_BITS 34          // rows < 2^34: l_pac up to 8.5 Gbp
 
 #include "dev_fasta.h"            // FASTA -> .pac / holes (bwagpu_fasta_*)
+#include "dev_fastq.h"            // FASTQ windows -> batches (bwagpu_fastq_*)
 
 namespace {
 
@@ -838,5 +839,185 @@ done:
 	const int rc = p->rc;
 	if (rc) fa_err(p, errbuf, errlen);
 	delete p;
+	return rc;
+}
+
+// ---- FASTQ windows -> batches (bseq_read, bwa.c:79-112) -------------------------------------------------------------------------
+// The device does everything per byte and per record (dev_fastq.h); the host copies the windows up, waits once for the status, the
+// batch size and the total sizes (FqInfo), sizes the result arrays, launches the emit pass and waits once for the copies.
+struct bwagpu_fastq_parser_s {
+	int device = 0;
+	hipStream_t st = nullptr;
+	hipEvent_t ev[4] = { nullptr, nullptr, nullptr, nullptr };
+	Buf d_buf[2], d_nl[2], d_recs[2], d_tcount, d_tbase, d_units, d_uscan, d_words, d_tmp;
+	Buf o_seqs, o_off, o_names, o_name_off, o_quals, o_com, o_com_off, o_has, o_recs;
+	std::string err;
+
+	~bwagpu_fastq_parser_s()
+	{
+		for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+		if (st) (void)hipStreamDestroy(st);
+	}
+	int fail(int code, const std::string &msg) { err = msg; return code; }
+	int hip(const char *what, hipError_t e) { return e == hipSuccess ? 0 : fail(BWAGPU_EHIP, std::string(what) + ": " + hipGetErrorString(e)); }
+	// buffers only grow (Buf::ensure keeps a buffer that is large enough)
+	static u32 nl_cap_for(u64 n) { return (u32)(((n >> 1) + 8 + 3) & ~3ull); }
+	int ensure_window(int k, u64 n)
+	{
+		const u64 cap = nl_cap_for(n);
+		if (d_buf[k].ensure(n + 16) || d_nl[k].ensure(cap * 4) || d_recs[k].ensure((cap >> 2) * sizeof(bwagpu_fastq_rec_t)))
+			return fail(BWAGPU_ENOMEM, "hipMalloc failed (FASTQ window)");
+		return 0;
+	}
+	int ensure_shared(u64 tiles, u64 cap_units)
+	{
+		if (d_tcount.ensure(tiles * 8 + 8) || d_tbase.ensure(tiles * 8 + 8) || d_units.ensure(cap_units * sizeof(FqSum)) || d_uscan.ensure(cap_units * sizeof(FqSum)) ||
+			d_words.ensure(FQ_N_WORDS * 8 + sizeof(FqInfo))) return fail(BWAGPU_ENOMEM, "hipMalloc failed (FASTQ scans)");
+		return 0;
+	}
+	template <class T, class Op> int scan_incl(T *in, T *out, u64 m, Op op)
+	{
+		size_t bytes = 0;
+		hipError_t e = rocprim::inclusive_scan(nullptr, bytes, in, out, (size_t)m, op, st);
+		if (e != hipSuccess) return hip("inclusive_scan(size)", e);
+		if (d_tmp.ensure(bytes)) return fail(BWAGPU_ENOMEM, "hipMalloc failed (scan scratch)");
+		return hip("inclusive_scan", rocprim::inclusive_scan(d_tmp.p, bytes, in, out, (size_t)m, op, st));
+	}
+	int scan_excl(u64 *in, u64 *out, u64 m)
+	{
+		size_t bytes = 0;
+		hipError_t e = rocprim::exclusive_scan(nullptr, bytes, in, out, (u64)0, (size_t)m, rocprim::plus<u64>(), st);
+		if (e != hipSuccess) return hip("exclusive_scan(size)", e);
+		if (d_tmp.ensure(bytes)) return fail(BWAGPU_ENOMEM, "hipMalloc failed (scan scratch)");
+		return hip("exclusive_scan", rocprim::exclusive_scan(d_tmp.p, bytes, in, out, (u64)0, (size_t)m, rocprim::plus<u64>(), st));
+	}
+};
+
+extern "C" const char *bwagpu_fastq_last_error(const bwagpu_fastq_parser_t *p) { return p ? p->err.c_str() : ""; }
+extern "C" int bwagpu_fastq_rec_size(void) { return (int)sizeof(bwagpu_fastq_rec_t); }
+
+extern "C" int bwagpu_fastq_begin(bwagpu_fastq_parser_t **out, int device, char *errbuf, size_t errlen)
+{
+	if (errbuf && errlen) errbuf[0] = 0;
+	if (!out) return BWAGPU_EINVAL;
+	*out = nullptr;
+	int ndev = 0;
+	if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev || hipSetDevice(device) != hipSuccess) return BWAGPU_ENODEV;
+	bwagpu_fastq_parser_t *p = new bwagpu_fastq_parser_t();
+	p->device = device;
+	bool ok = hipStreamCreate(&p->st) == hipSuccess;
+	for (hipEvent_t &e : p->ev) ok = ok && hipEventCreate(&e) == hipSuccess;
+	if (!ok) { delete p; if (errbuf && errlen) snprintf(errbuf, errlen, "could not create the FASTQ parser's stream and events"); return BWAGPU_ENODEV; }
+	*out = p;
+	return 0;
+}
+
+extern "C" void bwagpu_fastq_end(bwagpu_fastq_parser_t *p) { delete p; }
+
+extern "C" int bwagpu_fastq_reserve(bwagpu_fastq_parser_t *p, int64_t window_bytes)
+{
+	if (!p || window_bytes < 0 || window_bytes >= ((int64_t)1 << 31)) return BWAGPU_EINVAL;
+	if (hipSetDevice(p->device) != hipSuccess) return p->fail(BWAGPU_ENODEV, "hipSetDevice failed");
+	const u64 n = (u64)window_bytes, tiles = 2 * ((n + FQ_TILE - 1) / FQ_TILE);
+	int rc = p->ensure_window(0, n);
+	if (!rc) rc = p->ensure_window(1, n);
+	if (!rc) rc = p->ensure_shared(tiles, bwagpu_fastq_parser_s::nl_cap_for(n) >> 2);
+	// the outputs of a window's worth of records: the text itself bounds every blob
+	if (!rc && (p->o_seqs.ensure(2 * n) || p->o_quals.ensure(2 * n) || p->o_names.ensure(2 * n) || p->o_com.ensure(2 * n))) rc = p->fail(BWAGPU_ENOMEM, "hipMalloc failed (FASTQ outputs)");
+	return rc;
+}
+
+extern "C" void bwagpu_fastq_out_free(bwagpu_fastq_out_t *o)
+{
+	if (!o) return;
+	bwagpu_free(o->seqs); bwagpu_free(o->off); bwagpu_free(o->names); bwagpu_free(o->name_off); bwagpu_free(o->quals);
+	bwagpu_free(o->comments); bwagpu_free(o->comment_off); bwagpu_free(o->has_comment); bwagpu_free(o->recs);
+	o->seqs = nullptr; o->off = nullptr; o->names = nullptr; o->name_off = nullptr; o->quals = nullptr;
+	o->comments = nullptr; o->comment_off = nullptr; o->has_comment = nullptr; o->recs = nullptr;
+}
+
+extern "C" int bwagpu_fastq_batch(bwagpu_fastq_parser_t *p, const void *raw1, int64_t len1, int eof1, const void *raw2, int64_t len2, int eof2,
+								  int chunk_size, bwagpu_fastq_out_t *out)
+{
+	const int64_t lim = (int64_t)1 << 31;
+	if (!p) return BWAGPU_EINVAL;
+	if (!out || !raw1 || len1 < 0 || len2 < 0 || len1 >= lim || len2 >= lim || chunk_size <= 0 || (!raw2 && len2 != 0))
+		return p->fail(BWAGPU_EINVAL, "bwagpu_fastq_batch: NULL argument, negative length, window of 2^31 bytes or more, chunk_size <= 0, or a length without a second window");
+	memset(out, 0, sizeof *out);
+	out->declined_file = -1; out->declined_at = -1;
+	p->err.clear();
+	if (hipSetDevice(p->device) != hipSuccess) return p->fail(BWAGPU_ENODEV, "hipSetDevice failed");      // (the caller's thread may be another one than bwagpu_fastq_begin's)
+	FqArgs A; memset(&A, 0, sizeof A);
+	A.nw = raw2 ? 2 : 1;
+	const void *raw[2] = { raw1, raw2 }; const u64 len[2] = { (u64)len1, (u64)len2 }; const int eof[2] = { eof1, eof2 };
+	u32 tiles = 0; u64 cap_units = ~0ull;
+	for (int k = 0; k < A.nw; ++k) {
+		if (int rc = p->ensure_window(k, len[k])) return rc;
+		FqWin &W = A.w[k];
+		W.buf = p->d_buf[k].as<u8>(); W.n = (u32)len[k]; W.tile0 = tiles; W.n_tiles = (u32)((len[k] + FQ_TILE - 1) / FQ_TILE); tiles += W.n_tiles;
+		W.nl = p->d_nl[k].as<u32>(); W.nl_cap = bwagpu_fastq_parser_s::nl_cap_for(len[k]); W.recs = p->d_recs[k].as<bwagpu_fastq_rec_t>(); W.rec_cap = W.nl_cap >> 2; W.eof = eof[k];
+		if (W.rec_cap < cap_units) cap_units = W.rec_cap;
+	}
+	A.cap_units = (u32)cap_units;
+	if (int rc = p->ensure_shared(tiles, cap_units)) return rc;
+	u64 *words = p->d_words.as<u64>();
+	FqInfo *d_info = (FqInfo*)(words + FQ_N_WORDS);
+	FqSum *units = p->d_units.as<FqSum>(), *uscan = p->d_uscan.as<FqSum>();
+	for (int k = 0; k < A.nw; ++k)
+		if (len[k] && p->hip("copy window", hipMemcpyAsync(p->d_buf[k].p, raw[k], (size_t)len[k], hipMemcpyHostToDevice, p->st))) return BWAGPU_EHIP;
+	if (p->hip("memset", hipMemsetAsync(words, 0, FQ_N_WORDS * 8, p->st))) return BWAGPU_EHIP;
+	(void)hipEventRecord(p->ev[0], p->st);
+	if (tiles) {
+		hipLaunchKernelGGL(k_fq_count, dim3(tiles), dim3(FQ_BLOCK), 0, p->st, A, p->d_tcount.as<u64>());
+		if (int rc = p->scan_excl(p->d_tcount.as<u64>(), p->d_tbase.as<u64>(), tiles)) return rc;
+		hipLaunchKernelGGL(k_fq_index, dim3(tiles), dim3(FQ_BLOCK), 0, p->st, A, p->d_tbase.as<u64>(), words);
+	}
+	const unsigned ugrid = grid_for(cap_units) < 1024 ? grid_for(cap_units) : 1024;
+	hipLaunchKernelGGL(k_fq_records, dim3(ugrid), dim3(FQ_BLOCK), 0, p->st, A, words, units);
+	(void)hipEventRecord(p->ev[1], p->st);
+	if (int rc = p->scan_incl(units, uscan, cap_units, FqPlus())) return rc;
+	hipLaunchKernelGGL(k_fq_cut, dim3(ugrid), dim3(FQ_BLOCK), 0, p->st, A, words, uscan, (u64)chunk_size);
+	hipLaunchKernelGGL(k_fq_decide, dim3(1), dim3(FQ_WAVE), 0, p->st, A, words, uscan, d_info);
+	(void)hipEventRecord(p->ev[2], p->st);
+	FqInfo info;
+	// wait 1: status, batch size, total sizes
+	if (p->hip("read back the batch's sizes", hipMemcpyAsync(&info, d_info, sizeof info, hipMemcpyDeviceToHost, p->st)) || p->hip("sync", hipStreamSynchronize(p->st))) return BWAGPU_EHIP;
+	if (p->hip("FASTQ kernels", hipGetLastError())) return BWAGPU_EHIP;
+	{ float ms = 0; if (hipEventElapsedTime(&ms, p->ev[0], p->ev[1]) == hipSuccess) out->kernel_ms[0] = ms; if (hipEventElapsedTime(&ms, p->ev[1], p->ev[2]) == hipSuccess) out->kernel_ms[1] = ms; }
+	out->status = (int32_t)info.status;
+	if (info.status == BWAGPU_FQ_DECLINED) { out->declined_file = (int32_t)info.declined_file; out->declined_at = info.declined_at; return 0; }
+	if (info.status == BWAGPU_FQ_MORE) return 0;
+	const u64 n_reads = (u64)info.n_units * (u64)A.nw;
+	if (n_reads >= (1ull << 31)) return p->fail(BWAGPU_EUNSUP, "a batch of 2^31 reads or more");
+	out->n_reads = (int32_t)n_reads; out->consumed[0] = info.consumed[0]; out->consumed[1] = info.consumed[1];
+	const u64 ts = info.total.seq, tn = info.total.name, tc = info.total.com;
+	out->seqs = (uint8_t*)bwagpu_alloc_host(ts + 1); out->off = (int64_t*)bwagpu_alloc_host((n_reads + 1) * 8);
+	out->names = (char*)bwagpu_alloc_host(tn + 1); out->name_off = (int64_t*)bwagpu_alloc_host((n_reads + 1) * 8);
+	out->quals = (char*)bwagpu_alloc_host(ts + 1);
+	out->comments = (char*)bwagpu_alloc_host(tc + 1); out->comment_off = (int64_t*)bwagpu_alloc_host((n_reads + 1) * 8);
+	out->has_comment = (uint8_t*)bwagpu_alloc_host(n_reads + 1); out->recs = (bwagpu_fastq_rec_t*)bwagpu_alloc_host((n_reads + 1) * sizeof(bwagpu_fastq_rec_t));
+	int rc = 0;
+	if (!out->seqs || !out->off || !out->names || !out->name_off || !out->quals || !out->comments || !out->comment_off || !out->has_comment || !out->recs)
+		rc = p->fail(BWAGPU_ENOMEM, "out of host memory (FASTQ batch)");
+	if (!rc && n_reads == 0) { out->off[0] = out->name_off[0] = out->comment_off[0] = 0; return 0; }
+	if (!rc && (p->o_seqs.ensure(ts + 1) || p->o_quals.ensure(ts + 1) || p->o_names.ensure(tn + 1) || p->o_com.ensure(tc + 1) || p->o_off.ensure((n_reads + 1) * 8) ||
+				p->o_name_off.ensure((n_reads + 1) * 8) || p->o_com_off.ensure((n_reads + 1) * 8) || p->o_has.ensure(n_reads) || p->o_recs.ensure(n_reads * sizeof(bwagpu_fastq_rec_t))))
+		rc = p->fail(BWAGPU_ENOMEM, "hipMalloc failed (FASTQ outputs)");
+	if (!rc) {
+		FqOut o;
+		o.seqs = p->o_seqs.as<u8>(); o.off = p->o_off.as<i64>(); o.names = p->o_names.as<char>(); o.name_off = p->o_name_off.as<i64>(); o.quals = p->o_quals.as<char>();
+		o.comments = p->o_com.as<char>(); o.comment_off = p->o_com_off.as<i64>(); o.has_comment = p->o_has.as<u8>(); o.recs = p->o_recs.as<bwagpu_fastq_rec_t>();
+		const u64 eblocks = (n_reads + FQ_BLOCK / FQ_WAVE - 1) / (FQ_BLOCK / FQ_WAVE);
+		hipLaunchKernelGGL(k_fq_emit, dim3((unsigned)(eblocks < 65536 ? eblocks : 65536)), dim3(FQ_BLOCK), 0, p->st, A, uscan, n_reads, info.total, o);
+		(void)hipEventRecord(p->ev[3], p->st);
+		auto down = [&](void *dst, const Buf &src, u64 bytes) { return bytes ? p->hip("download", hipMemcpyAsync(dst, src.p, (size_t)bytes, hipMemcpyDeviceToHost, p->st)) : 0; };
+		// wait 2: the copies
+		if (down(out->seqs, p->o_seqs, ts) || down(out->quals, p->o_quals, ts) || down(out->names, p->o_names, tn) || down(out->comments, p->o_com, tc) ||
+			down(out->off, p->o_off, (n_reads + 1) * 8) || down(out->name_off, p->o_name_off, (n_reads + 1) * 8) || down(out->comment_off, p->o_com_off, (n_reads + 1) * 8) ||
+			down(out->has_comment, p->o_has, n_reads) || down(out->recs, p->o_recs, n_reads * sizeof(bwagpu_fastq_rec_t)) || p->hip("sync", hipStreamSynchronize(p->st)) ||
+			p->hip("FASTQ emit kernel", hipGetLastError())) rc = BWAGPU_EHIP;
+		else { float ms = 0; if (hipEventElapsedTime(&ms, p->ev[2], p->ev[3]) == hipSuccess) out->kernel_ms[2] = ms; }
+	}
+	if (rc) { bwagpu_fastq_out_free(out); out->status = 0; out->n_reads = 0; }
 	return rc;
 }

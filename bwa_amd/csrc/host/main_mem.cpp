@@ -49,6 +49,8 @@ static std::atomic<long> g_n_alns_reads(0);      // ... reads finalized from suc
 static int g_device_samtext = 0;  // BWAGPU_CLI_SAMTEXT=1: single-end batches without -5 take their SAM text from the device (bwagpu_batch_sam, after the CIGAR call, in place of bwagpu_batch_alns / bwagpu_batch_primary; device CIGARs on; same output); a read the device declines goes through the host formatter.
                                   // Paired-end batches, under BWAGPU_CLI_SAMPE's conditions (whether or not that switch is set): bwagpu_batch_sam_pe in place of every device call behind the download; a pair the device declines runs the host's mem_sam_pe on the download's lists
 static std::atomic<long> g_n_samtext_reads(0);   // ... reads written from such text
+static int g_device_fastq = 0;    // BWAGPU_CLI_FASTQ=1: plain FASTQ files (one or two, no -p) are parsed on the device (bwagpu_fastq_batch): records, bseq_read's cut, base codes and the name / quality / comment
+                                  // blobs of BWAGPU_CLI_SAMTEXT come from there; a batch the device declines, and the input behind it, goes through the reader below (same output)
 static std::string g_dev_rg_id; static bool g_dev_copy_comment = false;      // -R's id and -C for that call (set before the stages start)
 static std::atomic<long> g_n_primary_reads(0);   // ... reads finalized from such records (the BWAGPU_CLI_TRACE line at the end of the run)
 
@@ -259,13 +261,14 @@ struct Source {
 static void trim_readno(Seq &s, Arena &A) { char *T = s.base ? s.base : A.data(); if (s.l_name > 2 && T[s.name + s.l_name - 2] == '/' && isdigit((unsigned char)T[s.name + s.l_name - 1])) { s.l_name -= 2; T[s.name + s.l_name] = 0; } }
 
 struct Batch { Arena text; std::vector<Seq> seqs; std::vector<std::shared_ptr<ParBlock>> blocks;   /* parsed blocks the records with a base of their own lie in */
+	std::shared_ptr<bwagpu_fastq_out_t> fq;   /* a batch parsed on the device (BWAGPU_CLI_FASTQ): its arrays -- read i of the batch is read i there; seqs has gone to the Sub's flat */
 	const char *T(const Seq &q) const { return q.base ? q.base : text.data(); } };
 
 static bool read_batch(Source &r1, Source *r2, int chunk, Batch &out)
 {
 	static long batch_no = 0;
 	const long id = batch_no++;
-	out.seqs.clear(); out.text.clear(); out.blocks.clear();
+	out.seqs.clear(); out.text.clear(); out.blocks.clear(); out.fq.reset();
 	if (out.text.capacity() == 0) { out.text.reserve((size_t)chunk * 5 / 2 + (1 << 20)); out.seqs.reserve((size_t)chunk / 64 + 1024); }   // ~2.3 text bytes per base
 	long size = 0; Seq s, s2;
 	while (r1.read(s, out.text, out.blocks, id)) {
@@ -347,7 +350,7 @@ struct HostBuf {
 };
 struct Sub {      // one mem_process_seqs call (bwamem.c:1235-1264) on the reads `idx` of its batch
 	std::vector<int> idx; bwagpu_opt_t opt; int64_t n_processed = 0;
-	HostBuf flat; std::vector<int64_t> off; std::vector<int32_t> counts;
+	HostBuf flat; std::vector<int64_t> off; std::vector<int32_t> counts; bool encoded = false;   /* flat / off came with the batch (BWAGPU_CLI_FASTQ) */
 	bwagpu_alnreg_t *all = nullptr; int64_t tot = 0;
 	bwagpu_cigar_t *cigs = nullptr;           // device-side global alignments of the regions (bwagpu_batch_cigars)
 	uint32_t *cig_ops = nullptr;              // ... and the operation array its records with more than 6 operations point into
@@ -395,6 +398,88 @@ static void encode_sub(const Batch &in, Sub &u)
 // stage 2: the kt_for(worker1) of mem_process_seqs (bwamem.c:1252) on the device
 static std::mutex g_dev_mutex;
 static bool g_dev_serialize = false;   // BWAGPU_CLI_SERIALIZE=1: one device call at a time (the mock HIP runtime of the CPU tests is not thread-safe)
+
+// ---- BWAGPU_CLI_FASTQ: the input stage on the device ------------------------------------------------------------------------------
+// The plain input files are mapped; per batch a window of each goes to bwagpu_fastq_batch from the current offsets (about three bytes per base of the chunk plus slack,
+// doubled when the device answers MORE), and the offsets advance by what the batch consumed.  The batch's records come out of the record table: every field is copied
+// by its recorded offset and length into the batch's arena (the host formatter wants terminated strings), nothing is searched for.  The base codes are the device's.
+// When the device declines a batch -- a record that is not of the plain kind, a file that ends early -- that batch and the rest of the input go through the streaming
+// reader from the batch's start offsets, whose general path has the reference's kseq semantics: the output is the same either way.
+struct DevInput {
+	bwagpu_fastq_parser_t *p = nullptr;
+	int nf = 0; std::string path[2]; int fd[2] = { -1, -1 }; const char *map[2] = { nullptr, nullptr }; size_t size[2] = { 0, 0 }, pos[2] = { 0, 0 };
+	bool fallback = false;
+	long n_dev_batches = 0, n_dev_reads = 0, n_host_batches = 0;
+	~DevInput() { for (int k = 0; k < 2; ++k) { if (map[k]) munmap((void*)map[k], size[k]); if (fd[k] >= 0) ::close(fd[k]); } if (p) bwagpu_fastq_end(p); }
+	// ParFile::open's test: a regular file that does not start with the gzip magic
+	bool open_file(int k, const char *fn) {
+		if (!strcmp(fn, "-")) return false;
+		const int f = ::open(fn, O_RDONLY);
+		if (f < 0) return false;
+		unsigned char magic[2] = { 0, 0 }; struct stat st;
+		if (!(fstat(f, &st) == 0 && S_ISREG(st.st_mode) && pread(f, magic, 2, 0) >= 0 && !(magic[0] == 0x1f && magic[1] == 0x8b))) { ::close(f); return false; }
+		size[k] = (size_t)st.st_size;
+		if (size[k] > 0) {
+			void *mp = mmap(nullptr, size[k], PROT_READ, MAP_PRIVATE, f, 0);
+			if (mp == MAP_FAILED) { ::close(f); return false; }
+			madvise(mp, size[k], MADV_SEQUENTIAL);
+			map[k] = (const char*)mp;
+			ParFile::guard_mapped_input(map[k], size[k]);
+		}
+		fd[k] = f; path[k] = fn;
+		return true;
+	}
+	static size_t window_for(int chunk) { const size_t w = (size_t)chunk * 3 + ((size_t)1 << 20); return w < ((size_t)1 << 31) - 1 ? w : ((size_t)1 << 31) - 1; }
+	// 1: a batch in out (flat / off: the codes); 0: the input has ended; -1: declined -- the caller's reader takes over at pos[]
+	int next(int chunk, Batch &out, HostBuf &flat, std::vector<int64_t> &off, int n_threads) {
+		size_t win = window_for(chunk);
+		std::shared_ptr<bwagpu_fastq_out_t> o(new bwagpu_fastq_out_t(), [](bwagpu_fastq_out_t *x) { bwagpu_fastq_out_free(x); delete x; });
+		memset(o.get(), 0, sizeof(bwagpu_fastq_out_t));
+		for (;;) {
+			size_t len[2] = { 0, 0 }; int eof[2] = { 1, 1 };
+			for (int k = 0; k < nf; ++k) { const size_t left = size[k] - pos[k]; len[k] = left < win ? left : win; eof[k] = len[k] == left; }
+			int rc;
+			{
+				std::unique_lock<std::mutex> serial(g_dev_mutex, std::defer_lock);
+				if (g_dev_serialize) serial.lock();
+				rc = bwagpu_fastq_batch(p, map[0] ? map[0] + pos[0] : "", (int64_t)len[0], eof[0], nf > 1 ? (map[1] ? map[1] + pos[1] : "") : nullptr, (int64_t)len[1], eof[1], chunk, o.get());
+			}
+			if (rc != BWAGPU_OK) { fprintf(stderr, "[E::%s] bwagpu_fastq_batch: %s: %s\n", "main_mem", bwagpu_strerror(rc), bwagpu_fastq_last_error(p)); fflush(stderr); fflush(stdout); _exit(EXIT_FAILURE); }
+			if (o->status == BWAGPU_FQ_MORE) {
+				if (win >= ((size_t)1 << 31) - 1) return -1;      // (a batch that does not fit the largest window: the streaming reader)
+				win = win * 2 < ((size_t)1 << 31) - 1 ? win * 2 : ((size_t)1 << 31) - 1;
+				continue;
+			}
+			break;
+		}
+		if (o->status == BWAGPU_FQ_DECLINED) return -1;
+		const int n = o->n_reads;
+		if (n == 0) return 0;
+		out.seqs.clear(); out.text.clear(); out.blocks.clear();
+		out.seqs.resize((size_t)n);
+		out.text.resize((size_t)(o->name_off[n] + o->comment_off[n] + o->off[n]) + 3 * (size_t)n);
+		char *A = out.text.data();
+		const bwagpu_fastq_out_t *r = o.get();
+		const char *m0 = map[0] + pos[0], *m1 = nf > 1 ? map[1] + pos[1] : nullptr;
+		parallel_for(n_threads < 4 ? n_threads : 4, n, [&](long i) {
+			const bwagpu_fastq_rec_t &e = r->recs[i];
+			const char *src = e.file ? m1 : m0;
+			Seq &s = out.seqs[(size_t)i];
+			s = Seq();
+			size_t a = (size_t)(r->name_off[i] + r->comment_off[i] + r->off[i]) + 3 * (size_t)i;
+			s.name = a; s.l_name = e.l_name; memcpy(A + a, src + e.name, (size_t)e.l_name); a += (size_t)e.l_name; A[a++] = 0;
+			s.comment = a; s.has_comment = e.has_comment != 0; memcpy(A + a, src + e.comment, (size_t)e.l_comment); a += (size_t)e.l_comment; A[a] = 0;
+			s.seq = a++;                                         // (the bases exist as codes only: an empty string here)
+			s.qual = a; s.l_seq = e.l_seq; s.l_qual = e.l_qual; s.has_qual = true; memcpy(A + a, src + e.qual, (size_t)e.l_qual); A[a + (size_t)e.l_qual] = 0;
+		});
+		off.assign(o->off, o->off + n + 1);
+		{ HostBuf b; b.p = o->seqs; b.cap = (size_t)o->off[n] + 1; o->seqs = nullptr; flat = std::move(b); }      // (the codes' block goes where encode_sub's would: bwagpu_alloc_host's pool either way)
+		for (int k = 0; k < nf; ++k) pos[k] += (size_t)o->consumed[k];
+		out.fq = o;
+		++n_dev_batches; n_dev_reads += n;
+		return 1;
+	}
+};
 
 // (_exit: this runs on a device thread while sibling threads may be inside HIP calls -- no atexit handlers / static destructors under them)
 static void device_fail(bwagpu_t *gpu, int rc, const char *what = nullptr)
@@ -555,6 +640,16 @@ static void device_sub(const std::vector<bwagpu_t*> &gpus, Sub &u, const RefSeqs
 			memset(&u.sam[(size_t)d], 0, sizeof(bwagpu_sam_out_t));
 			if (s.tot == 0) return;      // (no CIGAR call for this shard: its reads print the unmapped record on the host)
 			const int m = s.hi - s.lo;
+			bwagpu_sam_in_t si; memset(&si, 0, sizeof si);
+			if (in->fq && u.encoded) {      // parsed on the device: the shard is a slice of the parse's blobs (offsets need not start at 0)
+				const bwagpu_fastq_out_t &f = *in->fq;
+				si.names = f.names; si.name_off = f.name_off + s.lo; si.quals = f.quals + u.off[s.lo];
+				if (g_dev_copy_comment) { si.comments = f.comments; si.comment_off = f.comment_off + s.lo; }
+				si.rg_id = g_dev_rg_id.c_str();
+				const int rc = bwagpu_batch_sam(gpus[d], &u.opt, u.n_processed + s.lo, &si, &u.sam[(size_t)d]);
+				if (rc != BWAGPU_OK) device_fail(gpus[d], rc);
+				return;
+			}
 			int n_qual = 0;
 			for (int i = s.lo; i < s.hi; ++i) n_qual += in->seqs[u.idx[i]].has_qual;
 			if (n_qual != 0 && n_qual != m) return;      // (qualities for some reads only: the host formatter)
@@ -567,7 +662,6 @@ static void device_sub(const std::vector<bwagpu_t*> &gpus, Sub &u, const RefSeqs
 				if (g_dev_copy_comment && q.has_comment) comments += T + q.comment;
 				comment_off.push_back((int64_t)comments.size());
 			}
-			bwagpu_sam_in_t si; memset(&si, 0, sizeof si);
 			si.names = names.data(); si.name_off = name_off.data(); si.quals = n_qual ? quals.data() : nullptr;
 			if (g_dev_copy_comment) { si.comments = comments.data(); si.comment_off = comment_off.data(); }
 			si.rg_id = g_dev_rg_id.c_str();
@@ -626,6 +720,21 @@ static void device_sub(const std::vector<bwagpu_t*> &gpus, Sub &u, const RefSeqs
 			memset(&u.sam[(size_t)d], 0, sizeof(bwagpu_sam_out_t));
 			if (s.tot == 0) return;      // (no region: the host prints the shard's unmapped records)
 			const int m = s.hi - s.lo;
+			bwagpu_sam_in_t si; memset(&si, 0, sizeof si);
+			std::vector<int32_t> m_counts((size_t)m);
+			if (in->fq && u.encoded) {      // parsed on the device: slices of the parse's blobs
+				const bwagpu_fastq_out_t &f = *in->fq;
+				for (int i = s.lo + 1; i < s.hi; i += 2) {      // (mates of different names: the finalize stage reports them as the reference does)
+					const int64_t a = f.name_off[i - 1], b = f.name_off[i], c = f.name_off[i + 1];
+					if (b - a != c - b || memcmp(f.names + a, f.names + b, (size_t)(b - a)) != 0) return;
+				}
+				si.names = f.names; si.name_off = f.name_off + s.lo; si.quals = f.quals + u.off[s.lo];
+				if (g_dev_copy_comment) { si.comments = f.comments; si.comment_off = f.comment_off + s.lo; }
+				si.rg_id = g_dev_rg_id.c_str();
+				const int rc = bwagpu_batch_sam_pe(gpus[d], &u.opt, dp, u.n_processed + s.lo, &si, m_counts.data(), nullptr, &u.sam[(size_t)d]);
+				if (rc != BWAGPU_OK) device_fail(gpus[d], rc);
+				return;
+			}
 			int n_qual = 0;
 			for (int i = s.lo; i < s.hi; ++i) n_qual += in->seqs[u.idx[i]].has_qual;
 			if (n_qual != 0 && n_qual != m) return;      // (qualities for some reads only: the host formatter)
@@ -639,11 +748,9 @@ static void device_sub(const std::vector<bwagpu_t*> &gpus, Sub &u, const RefSeqs
 				if (g_dev_copy_comment && q.has_comment) comments += T + q.comment;
 				comment_off.push_back((int64_t)comments.size());
 			}
-			bwagpu_sam_in_t si; memset(&si, 0, sizeof si);
 			si.names = names.data(); si.name_off = name_off.data(); si.quals = n_qual ? quals.data() : nullptr;
 			if (g_dev_copy_comment) { si.comments = comments.data(); si.comment_off = comment_off.data(); }
 			si.rg_id = g_dev_rg_id.c_str();
-			std::vector<int32_t> m_counts((size_t)m);
 			const int rc = bwagpu_batch_sam_pe(gpus[d], &u.opt, dp, u.n_processed + s.lo, &si, m_counts.data(), nullptr, &u.sam[(size_t)d]);
 			if (rc != BWAGPU_OK) device_fail(gpus[d], rc);
 		});
@@ -999,6 +1106,24 @@ int main(int argc, char *argv[])
 		rc = bwagpu_set_contig_names(gpu, names.data(), name_off.data(), annos.data(), anno_off.data());
 		if (rc != BWAGPU_OK) { fprintf(stderr, "[E::%s] %s\n", "main_mem", bwagpu_strerror(rc)); return 1; }
 	}
+	// BWAGPU_CLI_FASTQ: the device parser and its window buffers, before the suffix array below is sized against the free memory
+	if (getenv("BWAGPU_CLI_FASTQ")) g_device_fastq = atoi(getenv("BWAGPU_CLI_FASTQ"));
+	std::unique_ptr<DevInput> dev_in;
+	if (g_device_fastq && !(opt.flag & F_SMARTPE) && !getenv("BWAGPU_CLI_PARSE_ONLY")) {
+		dev_in.reset(new DevInput());
+		dev_in->nf = optind + 2 < argc ? 2 : 1;
+		bool ok = dev_in->open_file(0, argv[optind + 1]) && (dev_in->nf < 2 || dev_in->open_file(1, argv[optind + 2]));      // (anything but plain regular files: the switch does not apply)
+		if (ok) {
+			char eb[256];
+			const int rc = bwagpu_fastq_begin(&dev_in->p, device, eb, sizeof eb);
+			if (rc != BWAGPU_OK) { fprintf(stderr, "[E::%s] bwagpu_fastq_begin: %s %s\n", "main_mem", bwagpu_strerror(rc), eb); return 1; }
+			const int64_t chunk0 = fixed_chunk > 0 ? fixed_chunk : (int64_t)opt.chunk_size * opt.n_threads;
+			size_t w = DevInput::window_for((int)(chunk0 < (1 << 30) ? chunk0 : (1 << 30))), longest = dev_in->size[0] > dev_in->size[1] ? dev_in->size[0] : dev_in->size[1];
+			if (w > longest) w = longest;
+			const int rr = bwagpu_fastq_reserve(dev_in->p, (int64_t)w);
+			if (rr != BWAGPU_OK && g_verbose >= 2) fprintf(stderr, "[W::%s] could not reserve the FASTQ parser's buffers (%s); they grow with the first batch instead\n", "main_mem", bwagpu_strerror(rr));
+		} else dev_in.reset();
+	}
 	bwagpu_set_taps(gpu, 0);
 	bwagpu_set_cigar_filter(gpu, getenv("BWAGPU_CLI_CIGAR_FILTER") ? atoi(getenv("BWAGPU_CLI_CIGAR_FILTER")) : 1);   // (clones inherit it)
 	{	// SA look-ups walk ~31 LF steps with the reference's interval of 32; HBM has room for the full array (same values): 8 bytes per text position, 50 GB for a
@@ -1046,8 +1171,9 @@ int main(int argc, char *argv[])
 	const int n_parse = getenv("BWAGPU_CLI_PARSE_THREADS") ? atoi(getenv("BWAGPU_CLI_PARSE_THREADS")) : (any_bgzf ? (opt.n_threads / 2 > 8 ? 8 : (opt.n_threads / 2 < 4 ? 4 : opt.n_threads / 2)) : 4);
 	std::unique_ptr<ParPool> parse_pool(n_parse > 0 ? new ParPool(n_parse) : nullptr);
 	Source r1, r2; Source *pr2 = nullptr;
-	if (!r1.open(argv[optind + 1], parse_pool.get())) { fprintf(stderr, "[E::%s] fail to open file `%s'.\n", "main_mem", argv[optind + 1]); return 1; }
-	if (optind + 2 < argc) {
+	if (dev_in) { if (dev_in->nf > 1) { pr2 = &r2; opt.flag |= F_PE; } }      // (the readers are opened where the device hands over, at its offsets)
+	else if (!r1.open(argv[optind + 1], parse_pool.get())) { fprintf(stderr, "[E::%s] fail to open file `%s'.\n", "main_mem", argv[optind + 1]); return 1; }
+	if (!dev_in && optind + 2 < argc) {
 		if (opt.flag & F_PE) { if (g_verbose >= 2) fprintf(stderr, "[W::%s] when '-p' is in use, the second query file is ignored.\n", "main_mem"); }
 		else { if (!r2.open(argv[optind + 2], parse_pool.get())) { fprintf(stderr, "[E::%s] fail to open file `%s'.\n", "main_mem", argv[optind + 2]); return 1; } pr2 = &r2; opt.flag |= F_PE; }
 	}
@@ -1168,7 +1294,20 @@ int main(int argc, char *argv[])
 			WorkP w(new Work()); w->no = no;
 			{ std::lock_guard<std::mutex> l(pool_m); if (!batch_pool.empty()) { w->in = std::move(batch_pool.back()); batch_pool.pop_back(); } }
 			const double tr = now_s();
-			if (!read_batch(r1, pr2, chunk, w->in)) break;
+			HostBuf dev_flat; std::vector<int64_t> dev_off; bool from_dev = false;
+			if (dev_in && !dev_in->fallback) {
+				const int got = dev_in->next(chunk, w->in, dev_flat, dev_off, opt.n_threads);
+				if (got == 0) break;
+				if (got > 0) from_dev = true;
+				else {      // declined: this batch and everything behind it through the streaming reader, from the batch's start
+					dev_in->fallback = true;
+					Source *rs[2] = { &r1, &r2 };
+					for (int k = 0; k < dev_in->nf; ++k)
+						if (!rs[k]->open(dev_in->path[k].c_str(), nullptr) || rs[k]->ser.raw_fd < 0 || lseek(rs[k]->ser.raw_fd, (off_t)dev_in->pos[k], SEEK_SET) < 0) { fprintf(stderr, "[E::%s] fail to re-open file `%s'.\n", "main_mem", dev_in->path[k].c_str()); exit(EXIT_FAILURE); }
+					if (tl_trace) fprintf(stderr, "[D::input] the device declined batch %ld: the streaming reader takes over at bytes %zu / %zu\n", no, dev_in->pos[0], dev_in->pos[1]);
+				}
+			}
+			if (!from_dev) { if (!read_batch(r1, pr2, chunk, w->in)) break; if (dev_in) ++dev_in->n_host_batches; }
 			const int n = (int)w->in.seqs.size();
 			long bp = 0; for (auto &q : w->in.seqs) bp += (long)q.l_seq;
 			if (g_verbose >= 3) fprintf(stderr, "[M::%s] read %d sequences (%ld bp)...\n", "process", n, bp);
@@ -1189,6 +1328,7 @@ int main(int argc, char *argv[])
 			} else {
 				Sub u; u.idx.resize((size_t)n); for (int i = 0; i < n; ++i) u.idx[i] = i;
 				u.opt = opt; u.n_processed = n_processed;
+				if (from_dev) { u.flat = std::move(dev_flat); u.off = std::move(dev_off); u.counts.assign((size_t)n, 0); u.encoded = true; }      // (the device's codes: nothing left for the encoder)
 				w->subs.push_back(std::move(u));
 			}
 			n_processed += n; ++no; ++progress;
@@ -1209,6 +1349,7 @@ int main(int argc, char *argv[])
 		while (to_enc.pop(w)) {
 			const double te = now_s();
 			for (Sub &u : w->subs) {
+				if (u.encoded) continue;
 				{ std::lock_guard<std::mutex> l(pool_m); if (!flat_pool.empty()) { u.flat = std::move(flat_pool.back()); flat_pool.pop_back(); } }
 				encode_sub(w->in, u);
 			}
@@ -1283,9 +1424,9 @@ int main(int argc, char *argv[])
 		if (tl_trace) fprintf(stderr, "[D::timeline] batch %ld finalize %.3f .. %.3f\n", w->no, tf - t_start, now_s() - t_start);
 		{
 			std::lock_guard<std::mutex> l(pool_m);
-			w->in.blocks.clear();                 // (the parsed blocks go back to their pool now, not when the batch is next used)
+			w->in.blocks.clear(); w->in.fq.reset(); // (the parsed blocks go back to their pool now, not when the batch is next used)
 			if (batch_pool.size() < 4) batch_pool.push_back(std::move(w->in));
-			for (Sub &u : w->subs) if (flat_pool.size() < 6) flat_pool.push_back(std::move(u.flat));
+			for (Sub &u : w->subs) if (!u.encoded && flat_pool.size() < 6) flat_pool.push_back(std::move(u.flat));      // (a device-parsed batch's codes go back to the result pool its next batch draws from)
 		}
 		w->in = Batch(); w->subs.clear();
 		to_out.push(std::move(w));
@@ -1297,6 +1438,7 @@ int main(int argc, char *argv[])
 	to_out.close();
 	writer.join();
 	all_done = true; watchdog.join();
+	if (dev_in && tl_trace) fprintf(stderr, "[D::input] %ld batches (%ld reads) parsed on the device, %ld by the host reader\n", dev_in->n_dev_batches, dev_in->n_dev_reads, dev_in->n_host_batches);
 	if (g_device_rescue && tl_trace && hostmem::g_pairs_merged_on_device.load() > 0)
 		fprintf(stderr, "[D::main_mem] %ld pairs merged on the device (BWAGPU_CLI_RESCUE), %ld of them with rescue alignments\n", hostmem::g_pairs_merged_on_device.load(), hostmem::g_pairs_merged_aligned.load());
 	if (g_device_pair && tl_trace) fprintf(stderr, "[D::main_mem] %ld pairs paired from device records (BWAGPU_CLI_PAIR)\n", hostmem::g_pairs_from_device.load());

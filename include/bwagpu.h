@@ -579,6 +579,59 @@ int bwagpu_fasta_feed(bwagpu_fasta_parser_t *p, const void *data, int64_t len, c
 int bwagpu_fasta_end(bwagpu_fasta_parser_t *p, bwagpu_fasta_t *out, char *errbuf, size_t errlen);
 void bwagpu_fasta_free(bwagpu_fasta_t *r);
 
+/* ---- FASTQ batches on the device (what bseq_read delivers, bwa.c:79-112 over kseq.h:175-215) --------------------------------- */
+/* A parser of its own (no index, no bwagpu_t).  A call takes a window of the uncompressed FASTQ text of one file, or of two files
+ * of mates, each starting at a record start, and returns the batch bseq_read(chunk_size) would cut from there: records parsed as
+ * kseq_read parses them, trim_readno applied, bases recoded by nst_nt4_table, two files interleaved as reads 2i, 2i + 1 -- in the
+ * layouts bwagpu_batch_upload (seqs, off) and bwagpu_sam_in_t (names, name_off, quals, comments, comment_off) take.
+ * The device reads PLAIN records only: four lines with all four newlines, '@' first, the third line starting with '+', sequence and
+ * quality of the same non-zero length, no '\r' before the first, second or fourth newline, a sequence line that does not start with
+ * '>', '+' or '@' and holds no byte <= ' ' and none >= 0x80.  Every record before the first one that is not plain is read exactly
+ * as the reference reads it (dev_fastq.h has the argument); at that record the device stops and says where.
+ *   BWAGPU_FQ_CUT       the cut was reached: the batch is complete.  A non-plain record behind the cut does not matter.
+ *   BWAGPU_FQ_END       every eof flag is set, every byte of every window became a record and (two windows) both hold the same number
+ *                       of records: the batch is the rest of the input (n_reads == 0 for empty windows; arrays are still delivered).
+ *   BWAGPU_FQ_MORE      a window without eof ran out before the cut and held no non-plain record: nothing is delivered, the caller
+ *                       repeats the call from the same start with a longer window.
+ *   BWAGPU_FQ_DECLINED  before the cut there is a non-plain record, an incomplete last record at eof (a missing final newline included),
+ *                       or one window ends at eof while the other has records left (the reference's "fewer sequences" cases): n_reads == 0,
+ *                       no arrays; declined_file / declined_at: the window and the byte offset in it of the first record not taken.  The
+ *                       caller reads this batch with a reader of its own.
+ * consumed[k]: bytes of window k that became the batch's records (CUT, END); the next call's window starts there.
+ * Host waits: one for the counts and total sizes, one for the final copies.  Device buffers only grow.  The arrays come from the
+ * result pool: release them with bwagpu_fastq_out_free (or bwagpu_free, each).
+ * BWAGPU_EINVAL: NULL p / raw1 / out, a negative length, a window of 2^31 bytes or more, chunk_size <= 0, raw2 == NULL with len2 != 0. */
+typedef struct bwagpu_fastq_parser_s bwagpu_fastq_parser_t;
+enum { BWAGPU_FQ_CUT = 0, BWAGPU_FQ_END = 1, BWAGPU_FQ_MORE = 2, BWAGPU_FQ_DECLINED = 3 };
+typedef struct {
+	int32_t file, has_comment;      /* window index (0 / 1); the header had a delimiter behind the name */
+	int32_t name, l_name;           /* window offsets and lengths: the name (trim_readno applied), */
+	int32_t comment, l_comment;     /* the comment (l_comment may be 0 with has_comment set), */
+	int32_t seq, l_seq;             /* the bases, */
+	int32_t qual, l_qual;           /* the qualities (l_qual == l_seq) */
+} bwagpu_fastq_rec_t;              /* 40 bytes */
+typedef struct {
+	int32_t status, n_reads;
+	int64_t consumed[2];            /* bytes of window k that became this batch's records */
+	int32_t declined_file; int64_t declined_at;   /* DECLINED: which window, byte offset of the first record not taken */
+	uint8_t *seqs;  int64_t *off;                  /* nt4, n_reads + 1: what bwagpu_batch_upload reads; seqs from bwagpu_alloc_host's pool */
+	char *names;    int64_t *name_off;             /* bwagpu_sam_in_t's layouts, trim_readno applied */
+	char *quals;                                   /* at the reads' own offsets */
+	char *comments; int64_t *comment_off; uint8_t *has_comment;   /* has_comment[i]: the header had a delimiter (the comment may be empty) */
+	bwagpu_fastq_rec_t *recs;                      /* per read: window index, offsets and lengths of its four fields in the window */
+	float kernel_ms[3];                            /* newline + check passes, cut, emit */
+} bwagpu_fastq_out_t;
+int  bwagpu_fastq_begin(bwagpu_fastq_parser_t **p, int device, char *errbuf, size_t errlen);
+/* device buffers for two windows of window_bytes each, ahead of the first call (BWAGPU_ENOMEM leaves the parser usable) */
+int  bwagpu_fastq_reserve(bwagpu_fastq_parser_t *p, int64_t window_bytes);
+int  bwagpu_fastq_batch(bwagpu_fastq_parser_t *p, const void *raw1, int64_t len1, int eof1,
+                        const void *raw2 /* NULL: one file */, int64_t len2, int eof2,
+                        int chunk_size, bwagpu_fastq_out_t *out);
+const char *bwagpu_fastq_last_error(const bwagpu_fastq_parser_t *p);
+void bwagpu_fastq_out_free(bwagpu_fastq_out_t *out);
+void bwagpu_fastq_end(bwagpu_fastq_parser_t *p);
+int  bwagpu_fastq_rec_size(void);   /* sizeof(bwagpu_fastq_rec_t) as compiled */
+
 /* ---- lifetime ------------------------------------------------------------------------------------------ */
 
 /* Create a handle on HIP device `device` and upload the index once (replaces nothing in the reference; it is
