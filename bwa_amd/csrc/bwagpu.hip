@@ -117,6 +117,8 @@ struct bwagpu_s {
 	DevBuf d_rs[RS_N];      // bwagpu_batch_rescue / bwagpu_rescue_flat (dev_rescue.h): anchors x 4 per read and their prefix sums, the task table, the arena of working lists (regions, src, lengths), the packed merged lists (offsets, regions, src), records, the wavefront forms' pair lists and their lengths, HBM sort keys; bwagpu_rescue_flat's sequences, the pairs' ids
 	enum { SP_OUT, SP_LIST, SP_CTR, SP_READ, SP_CIGS, SP_EXT, SP_N };
 	DevBuf d_sp[SP_N];      // bwagpu_batch_sampe / bwagpu_sampe_flat (dev_sampe.h): the pair records, the wavefront form's pair list and its length, the merged lists' region-to-read map, their CIGAR records and operation array
+	enum { CF_SEQ, CF_SEQOFF, CF_READ, CF_CIGS, CF_EXT, CF_N };
+	DevBuf d_cf[CF_N];      // bwagpu_cigars_flat: the caller's reads and their offsets, the region-to-read map, the CIGAR records and the operation array (none of them a batch's)
 	i64 cigl_z_cap = 0;                          // bytes per direction matrix of the long CIGAR tier's scratch (grows with the batches)
 	DevBuf d_cigl_z, d_cigl_ops, d_cigl_md, d_cigl_list;      // scratch of the long-segment CIGAR tier (k_cigar_long): direction matrices, operations, MD strings per workgroup
 	DevBuf d_cig_ext; i64 cig_ext_n = -1;   // operation array of the last bwagpu_batch_cigars (records with 7..64 operations point into it)
@@ -526,6 +528,7 @@ extern "C" void bwagpu_destroy(bwagpu_t *h)
 	for (DevBuf *b : all) b->release();
 	for (DevBuf &b : h->d_rs) b.release();
 	for (DevBuf &b : h->d_sp) b.release();
+	for (DevBuf &b : h->d_cf) b.release();
 	for (DevBuf &b : h->d_st) b.release();
 	for (int i = 0; i < 8; ++i) if (h->ev[i]) (void)hipEventDestroy(h->ev[i]);
 	if (h->ev_wait) (void)hipEventDestroy(h->ev_wait);
@@ -1715,6 +1718,75 @@ struct FlatLists {
 		return BWAGPU_OK;
 	}
 };
+// ---- the CIGAR kernels on lists of the caller (test hook) ------------------------------------------------------------------------------------------------
+extern "C" void bwagpu_cigar_limits(int32_t out[10])
+{
+	const int32_t v[10] = { CIG_MAX_LEN, CIG_Z_SMALL, CIG_Z_BIG, CIG_MAX_COLS, CIG_MAX_OPS, CIG_TMP_OPS, CIG_MD_CAP, CIGL_MAX_COLS, CIGL_MAX_OPS, CIGL_QCAP };
+	memcpy(out, v, sizeof v);
+}
+
+extern "C" int bwagpu_cigars_flat(bwagpu_t *h, const bwagpu_opt_t *opt, int n_reads, const uint8_t *seqs, const int64_t *seq_off, const int32_t *counts, const bwagpu_alnreg_t *regs,
+								  bwagpu_cigar_t **cigs, int64_t *n_cigs, uint32_t **ops, int64_t *n_ops)
+{
+	if (!h || !opt || n_reads < 0 || !cigs || !n_cigs || !ops || !n_ops || (n_reads > 0 && (!counts || !seq_off))) return BWAGPU_EINVAL;
+	if (opt->e_del <= 0 || opt->e_ins <= 0) { h->err = "bwagpu_cigars_flat: e_del and e_ins must be positive"; return BWAGPU_EINVAL; }
+	for (int i = 0; i < n_reads; ++i) if (counts[i] < 0) { h->err = "bwagpu_cigars_flat: a negative count"; return BWAGPU_EINVAL; }
+	FlatLists F; RegLists L;
+	if (!F.scan(h, (size_t)n_reads, counts, regs, nullptr)) { h->err = "bwagpu_cigars_flat: a count outside [0, 2^30), or counts without regions"; return BWAGPU_EINVAL; }
+	if (F.tot > 0x7fffffff) { h->err = "bwagpu_cigars_flat: more than 2^31 - 1 regions"; return BWAGPU_EINVAL; }
+	int max_len = 0;
+	for (int i = 0; i < n_reads; ++i) {
+		if (seq_off[0] != 0 || seq_off[i + 1] < seq_off[i] || seq_off[i + 1] - seq_off[i] > 0x3fffffff) { h->err = "bwagpu_cigars_flat: offsets that do not ascend"; return BWAGPU_EINVAL; }
+		max_len = std::max(max_len, (int)(seq_off[i + 1] - seq_off[i]));
+	}
+	const i64 n_bases = n_reads ? seq_off[n_reads] : 0;
+	if (n_bases > 0 && !seqs) return BWAGPU_EINVAL;
+	for (i64 k = 0; k < n_bases; ++k) if (seqs[k] > 4) { h->err = "bwagpu_cigars_flat: a base code above 4"; return BWAGPU_EINVAL; }
+	for (int i = 0; i < n_reads; ++i) {
+		const i64 len = seq_off[i + 1] - seq_off[i];
+		for (i64 k = F.off[(size_t)i]; k < F.off[(size_t)i + 1]; ++k) {
+			const bwagpu_alnreg_t &a = regs[k];
+			if (a.qb < 0 || a.qe > len) { h->err = "bwagpu_cigars_flat: region " + std::to_string(k) + ": qb < 0 or qe beyond the read"; return BWAGPU_EINVAL; }
+			if (a.rb < 0 || a.re > 2 * h->l_pac) { h->err = "bwagpu_cigars_flat: region " + std::to_string(k) + ": rb < 0 or re beyond 2 l_pac"; return BWAGPU_EINVAL; }
+		}
+	}
+	const BusyGuard busy(h->ibuf->busy);
+	HIPCHK(h, hipSetDevice(h->device));
+	*cigs = nullptr; *ops = nullptr; *n_cigs = 0; *n_ops = 0;
+	ResultBlock<bwagpu_cigar_t> res = result_block<bwagpu_cigar_t>((size_t)F.tot);
+	if (!res) return BWAGPU_ENOMEM;
+	i64 ext_n = 0;
+	DevBuf *D = h->d_cf;
+	if (F.tot > 0) {
+		const int rc = F.upload(h, "cigars_flat", counts, regs, nullptr, 0, L);
+		if (rc != BWAGPU_OK) return rc;
+		if (D[bwagpu_s::CF_SEQ].ensure((size_t)n_bases + 1) || D[bwagpu_s::CF_SEQOFF].ensure(((size_t)n_reads + 1) * 8) || D[bwagpu_s::CF_READ].ensure((size_t)F.tot * 4)) {
+			h->err = "hipMalloc failed (cigars_flat)"; return BWAGPU_ENOMEM;
+		}
+		if (n_bases) HIPCHK(h, hipMemcpyAsync(D[bwagpu_s::CF_SEQ].p, seqs, (size_t)n_bases, hipMemcpyHostToDevice, h->stream));
+		HIPCHK(h, hipMemcpyAsync(D[bwagpu_s::CF_SEQOFF].p, seq_off, ((size_t)n_reads + 1) * 8, hipMemcpyHostToDevice, h->stream));
+		HIPCHK(h, wait_stream(h));      // (the caller's arrays are pageable, as in bwagpu_alns_flat)
+		int nb = (n_reads + 3) / 4; if (nb > 8192) nb = 8192;
+		hipLaunchKernelGGL(k_sampe_reg_read, dim3(nb), dim3(BLOCK), 0, h->stream, n_reads, L.d_cnt, L.d_off, D[bwagpu_s::CF_READ].as<i32>());
+		HIPCHK(h, hipGetLastError());
+		// (the filter's table is the lists' offsets: a read's first region is its best)
+		const CigLists C = { F.tot, L.d_regs, D[bwagpu_s::CF_READ].as<i32>(), L.d_off, D[bwagpu_s::CF_SEQ].as<u8>(), D[bwagpu_s::CF_SEQOFF].as<i64>(), n_reads, max_len, n_bases,
+							 &D[bwagpu_s::CF_CIGS], &D[bwagpu_s::CF_EXT] };
+		float ms[2] = { 0.f, 0.f };
+		const int rcc = cigars_run(h, opt, C, res.get(), &ext_n, ms);
+		if (rcc != BWAGPU_OK) return rcc;
+	}
+	ResultBlock<uint32_t> res_ops = result_block<uint32_t>((size_t)ext_n);
+	if (!res_ops) return BWAGPU_ENOMEM;
+	if (ext_n) {
+		HIPCHK(h, hipMemcpyAsync(res_ops.get(), D[bwagpu_s::CF_EXT].p, (size_t)ext_n * 4, hipMemcpyDeviceToHost, h->stream));
+		HIPCHK(h, wait_stream(h));
+	}
+	*n_cigs = F.tot; *n_ops = ext_n;
+	*cigs = res.release(); *ops = res_ops.release();
+	return BWAGPU_OK;
+}
+
 // the largest argument a logarithm of the marking can get: a region's longer side, its seed coverage, its incoming sub_n plus the increments of both rounds plus one
 static i64 pri_log_need(const i32 *counts, const bwagpu_alnreg_t *regs, int n)
 {

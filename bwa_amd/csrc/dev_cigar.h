@@ -215,7 +215,9 @@ __device__ int wave_global2_fill_lds(const DevIndex &ix, const bwagpu_opt_t &opt
 		wave_sync();
 	}
 	cells += cells32;
-	return hd[qlen];
+	const int score = hd[qlen];
+	wave_sync();                                      // (every lane has its copy before the fill of the next band-doubling attempt rewrites the column)
+	return score;
 }
 
 // ... and its traceback (ksw.c:624-639), lane 0; the other lanes wait at the barrier below

@@ -272,6 +272,18 @@ int bwagpu_batch_cigars(bwagpu_t *h, const bwagpu_opt_t *opt, bwagpu_cigar_t **o
 int bwagpu_set_cigar_filter(bwagpu_t *h, int enable);
 /* The operation array of the last bwagpu_batch_cigars call (records with more than 6 operations point into it).  Free with bwagpu_free. */
 int bwagpu_batch_cigar_ops(bwagpu_t *h, uint32_t **ops, int64_t *n_ops);
+/* Test hook: the kernels of bwagpu_batch_cigars on reads (nt4 codes 0..4, n_reads + 1 offsets starting at 0) and region lists of the caller (read i: counts[i]
+ * records of regs; with the filter of bwagpu_set_cigar_filter on, the first of them is the read's best region).  *cigs: one record per region, in the regions'
+ * order; *ops: the operation array they point into, *n_ops entries.  Free both with bwagpu_free.  Needs no batch and leaves the records and operation array of
+ * bwagpu_batch_cigars / bwagpu_batch_cigar_ops on the same handle alone.  BWAGPU_EINVAL (with bwagpu_last_error text): negative counts, offsets that do not
+ * ascend, base codes above 4, qb < 0 or qe > the read's length, rb < 0 or re > 2 l_pac, e_del <= 0 or e_ins <= 0.  Shapes the kernels classify themselves come
+ * back as records that were not computed: qe <= qb, rb >= re, rb < l_pac < re (reason 2), score below opt->T (reason 1). */
+int bwagpu_cigars_flat(bwagpu_t *h, const bwagpu_opt_t *opt, int n_reads, const uint8_t *seqs, const int64_t *seq_off, const int32_t *counts, const bwagpu_alnreg_t *regs,
+					   bwagpu_cigar_t **cigs, int64_t *n_cigs, uint32_t **ops, int64_t *n_ops);
+/* The constants of the CIGAR kernels, as compiled: CIG_MAX_LEN, CIG_Z_SMALL, CIG_Z_BIG, CIG_MAX_COLS, CIG_MAX_OPS, CIG_TMP_OPS, CIG_MD_CAP (the LDS tiers: longest
+ * segment, direction nibbles of the first and second tier, widest band, operations kept in a record, operations and MD characters a wavefront stages);
+ * CIGL_MAX_COLS, CIGL_MAX_OPS, CIGL_QCAP (the long tier: widest band, most operations, query bases staged in LDS). */
+void bwagpu_cigar_limits(int32_t out[10]);
 
 /* After bwagpu_batch_download of a paired batch (mates interleaved 2i, 2i+1): the local alignments mem_matesw
  * (bwamem_pair.c:137-206) would run for every (anchor region, orientation) that the downloaded region lists do not already
