@@ -672,7 +672,7 @@ class BwaGpu:
 FASTQ_REC_DTYPE = np.dtype([("file", "<i4"), ("has_comment", "<i4"), ("name", "<i4"), ("l_name", "<i4"), ("comment", "<i4"), ("l_comment", "<i4"),
                             ("seq", "<i4"), ("l_seq", "<i4"), ("qual", "<i4"), ("l_qual", "<i4")])   # bwagpu_fastq_rec_t
 assert FASTQ_REC_DTYPE.itemsize == 40
-FQ_CUT, FQ_END, FQ_MORE, FQ_DECLINED = 0, 1, 2, 3
+FQ_CUT, FQ_END, FQ_MORE, FQ_DECLINED, FQ_DAMAGED = 0, 1, 2, 3, 4
 
 
 class FastqOut(C.Structure):
@@ -680,6 +680,20 @@ class FastqOut(C.Structure):
     _fields_ = [("status", C.c_int32), ("n_reads", C.c_int32), ("consumed", C.c_int64 * 2), ("declined_file", C.c_int32), ("declined_at", C.c_int64),
                 ("seqs", C.c_void_p), ("off", C.c_void_p), ("names", C.c_void_p), ("name_off", C.c_void_p), ("quals", C.c_void_p),
                 ("comments", C.c_void_p), ("comment_off", C.c_void_p), ("has_comment", C.c_void_p), ("recs", C.c_void_p), ("kernel_ms", C.c_float * 3)]
+
+
+class BgzfWin(C.Structure):
+    """bwagpu_bgzf_win_t"""
+    _fields_ = [("comp", C.c_void_p), ("comp_len", C.c_int64), ("skip", C.c_int32), ("eof", C.c_int32)]
+
+
+class BgzfInfo(C.Structure):
+    """bwagpu_bgzf_info_t"""
+    _fields_ = [("used_comp", C.c_int64), ("inflated", C.c_int64), ("n_blocks", C.c_int32), ("next_coff", C.c_int64), ("next_uoff", C.c_int32),
+                ("damaged_at", C.c_int64), ("inflate_ms", C.c_float)]
+
+    def as_dict(self) -> dict:
+        return {k: (float(getattr(self, k)) if k == "inflate_ms" else int(getattr(self, k))) for k, _ in self._fields_}
 
 
 class FastqParser:
@@ -692,6 +706,8 @@ class FastqParser:
         L.bwagpu_fastq_begin.argtypes = [C.POINTER(P), C.c_int, C.c_char_p, C.c_size_t]
         L.bwagpu_fastq_reserve.argtypes = [P, C.c_int64]
         L.bwagpu_fastq_batch.argtypes = [P, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p]
+        L.bwagpu_bgzf_inflate.argtypes = [P, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]
+        L.bwagpu_fastq_batch_bgzf.argtypes = [P, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         L.bwagpu_fastq_out_free.argtypes = [C.c_void_p]
         L.bwagpu_fastq_out_free.restype = None
         L.bwagpu_fastq_end.argtypes = [P]
@@ -727,6 +743,10 @@ class FastqParser:
         rc = self.L.bwagpu_fastq_batch(self.h, b1.ctypes.data, len(raw1), int(bool(eof[0])), None if b2 is None else b2.ctypes.data,
                                        0 if raw2 is None else len(raw2), int(bool(eof[1])), int(chunk_size), C.byref(o))
         self._chk(rc, "bwagpu_fastq_batch")
+        return self._result(o)
+
+    def _result(self, o) -> dict:
+        """a filled FastqOut as a dict of copies; the library's arrays are released"""
         r = {"status": int(o.status), "n_reads": int(o.n_reads), "consumed": (int(o.consumed[0]), int(o.consumed[1])),
              "declined_file": int(o.declined_file), "declined_at": int(o.declined_at), "kernel_ms": tuple(float(x) for x in o.kernel_ms)}
         try:
@@ -748,6 +768,48 @@ class FastqParser:
                 r["recs"] = take(o.recs, n, FASTQ_REC_DTYPE)
         finally:
             self.L.bwagpu_fastq_out_free(C.byref(o))
+        return r
+
+    def inflate_bgzf(self, data, eof: bool = True):
+        """data: BGZF bytes that start at a block start.  Returns (text of the whole blocks taken, info dict); the text is None when a block
+        is damaged (info["damaged_at"] >= 0).  info has bwagpu_bgzf_info_t's fields."""
+        b = np.frombuffer(data, dtype=np.uint8) if len(data) else np.zeros(1, dtype=np.uint8)
+        total = 0
+        info = BgzfInfo()
+        dst = np.zeros(1, dtype=np.uint8)
+        for _ in range(2):      # (the first call may only say how much text there is: BWAGPU_EINVAL, inflated set)
+            rc = self.L.bwagpu_bgzf_inflate(self.h, b.ctypes.data, len(data), int(bool(eof)), dst.ctypes.data, total, C.byref(info))
+            if rc == -2 and info.inflated > total:
+                total = int(info.inflated)
+                dst = np.zeros(total, dtype=np.uint8)
+                continue
+            break
+        self._chk(rc, "bwagpu_bgzf_inflate")
+        d = info.as_dict()
+        return (None if d["damaged_at"] >= 0 else dst[:d["inflated"]].tobytes()), d
+
+    def batch_bgzf_rc(self, w1, w2, chunk_size, out, info):
+        """the bare call (tests of the error paths): returns the library's code"""
+        return self.L.bwagpu_fastq_batch_bgzf(self.h, w1, w2, chunk_size, out, info)
+
+    def batch_bgzf(self, c1, c2=None, skip=(0, 0), chunk_size: int = 10_000_000, eof=(True, True)) -> dict:
+        """c1 / c2: bytes-like windows of BGZF data, each starting at a block start (c2 None: one file); skip[k]: bytes of window k's first
+        block's text that earlier batches consumed.  Returns batch()'s dict plus "bgzf": one info dict per window (bwagpu_bgzf_info_t's
+        fields).  consumed, declined_at and recs refer to the text window, which exists on the device only."""
+        keep, wins = [], []
+        for k, c in enumerate((c1, c2)):
+            if c is None:
+                wins.append(None)
+                continue
+            b = np.frombuffer(c, dtype=np.uint8) if len(c) else np.zeros(1, dtype=np.uint8)
+            keep.append(b)
+            wins.append(BgzfWin(b.ctypes.data, len(c), int(skip[k]), int(bool(eof[k]))))
+        o = FastqOut()
+        info = (BgzfInfo * 2)()
+        rc = self.L.bwagpu_fastq_batch_bgzf(self.h, C.byref(wins[0]), None if wins[1] is None else C.byref(wins[1]), int(chunk_size), C.byref(o), info)
+        self._chk(rc, "bwagpu_fastq_batch_bgzf")
+        r = self._result(o)
+        r["bgzf"] = [info[k].as_dict() for k in range(1 if c2 is None else 2)]
         return r
 
     def close(self):

@@ -41,6 +41,7 @@ typedef unsigned char u8;
 
 #include "dev_fasta.h"            // FASTA -> .pac / holes (bwagpu_fasta_*)
 #include "dev_fastq.h"            // FASTQ windows -> batches (bwagpu_fastq_*)
+#include "dev_bgzf.h"             // BGZF blocks -> text (bwagpu_bgzf_inflate, bwagpu_fastq_batch_bgzf)
 
 namespace {
 
@@ -848,7 +849,8 @@ done:
 struct bwagpu_fastq_parser_s {
 	int device = 0;
 	hipStream_t st = nullptr;
-	hipEvent_t ev[4] = { nullptr, nullptr, nullptr, nullptr };
+	hipEvent_t ev[6] = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };      // (4, 5: around the BGZF inflate)
+	Buf d_comp[2], d_blk[2], d_bzstat;      // BGZF: compressed windows, block tables, status words + the bad words of both windows
 	Buf d_buf[2], d_nl[2], d_recs[2], d_tcount, d_tbase, d_units, d_uscan, d_words, d_tmp;
 	Buf o_seqs, o_off, o_names, o_name_off, o_quals, o_com, o_com_off, o_has, o_recs;
 	std::string err;
@@ -936,20 +938,11 @@ extern "C" void bwagpu_fastq_out_free(bwagpu_fastq_out_t *o)
 	o->comments = nullptr; o->comment_off = nullptr; o->has_comment = nullptr; o->recs = nullptr;
 }
 
-extern "C" int bwagpu_fastq_batch(bwagpu_fastq_parser_t *p, const void *raw1, int64_t len1, int eof1, const void *raw2, int64_t len2, int eof2,
-								  int chunk_size, bwagpu_fastq_out_t *out)
+// the windows of a call: buffers sized, A filled (W.buf: the window buffer's start)
+static int fq_setup(bwagpu_fastq_parser_t *p, FqArgs &A, int nw, const u64 len[2], const int eof[2], u32 *n_tiles, u64 *n_units)
 {
-	const int64_t lim = (int64_t)1 << 31;
-	if (!p) return BWAGPU_EINVAL;
-	if (!out || !raw1 || len1 < 0 || len2 < 0 || len1 >= lim || len2 >= lim || chunk_size <= 0 || (!raw2 && len2 != 0))
-		return p->fail(BWAGPU_EINVAL, "bwagpu_fastq_batch: NULL argument, negative length, window of 2^31 bytes or more, chunk_size <= 0, or a length without a second window");
-	memset(out, 0, sizeof *out);
-	out->declined_file = -1; out->declined_at = -1;
-	p->err.clear();
-	if (hipSetDevice(p->device) != hipSuccess) return p->fail(BWAGPU_ENODEV, "hipSetDevice failed");      // (the caller's thread may be another one than bwagpu_fastq_begin's)
-	FqArgs A; memset(&A, 0, sizeof A);
-	A.nw = raw2 ? 2 : 1;
-	const void *raw[2] = { raw1, raw2 }; const u64 len[2] = { (u64)len1, (u64)len2 }; const int eof[2] = { eof1, eof2 };
+	memset(&A, 0, sizeof A);
+	A.nw = nw;
 	u32 tiles = 0; u64 cap_units = ~0ull;
 	for (int k = 0; k < A.nw; ++k) {
 		if (int rc = p->ensure_window(k, len[k])) return rc;
@@ -959,12 +952,16 @@ extern "C" int bwagpu_fastq_batch(bwagpu_fastq_parser_t *p, const void *raw1, in
 		if (W.rec_cap < cap_units) cap_units = W.rec_cap;
 	}
 	A.cap_units = (u32)cap_units;
-	if (int rc = p->ensure_shared(tiles, cap_units)) return rc;
+	*n_tiles = tiles; *n_units = cap_units;
+	return p->ensure_shared(tiles, cap_units);
+}
+
+// everything behind the copy-up: the text windows are in place on the device (in stream order)
+static int fq_run(bwagpu_fastq_parser_t *p, const FqArgs &A, u32 tiles, u64 cap_units, int chunk_size, bwagpu_fastq_out_t *out)
+{
 	u64 *words = p->d_words.as<u64>();
 	FqInfo *d_info = (FqInfo*)(words + FQ_N_WORDS);
 	FqSum *units = p->d_units.as<FqSum>(), *uscan = p->d_uscan.as<FqSum>();
-	for (int k = 0; k < A.nw; ++k)
-		if (len[k] && p->hip("copy window", hipMemcpyAsync(p->d_buf[k].p, raw[k], (size_t)len[k], hipMemcpyHostToDevice, p->st))) return BWAGPU_EHIP;
 	if (p->hip("memset", hipMemsetAsync(words, 0, FQ_N_WORDS * 8, p->st))) return BWAGPU_EHIP;
 	(void)hipEventRecord(p->ev[0], p->st);
 	if (tiles) {
@@ -1020,4 +1017,200 @@ extern "C" int bwagpu_fastq_batch(bwagpu_fastq_parser_t *p, const void *raw1, in
 	}
 	if (rc) { bwagpu_fastq_out_free(out); out->status = 0; out->n_reads = 0; }
 	return rc;
+}
+
+extern "C" int bwagpu_fastq_batch(bwagpu_fastq_parser_t *p, const void *raw1, int64_t len1, int eof1, const void *raw2, int64_t len2, int eof2,
+								  int chunk_size, bwagpu_fastq_out_t *out)
+{
+	const int64_t lim = (int64_t)1 << 31;
+	if (!p) return BWAGPU_EINVAL;
+	if (!out || !raw1 || len1 < 0 || len2 < 0 || len1 >= lim || len2 >= lim || chunk_size <= 0 || (!raw2 && len2 != 0))
+		return p->fail(BWAGPU_EINVAL, "bwagpu_fastq_batch: NULL argument, negative length, window of 2^31 bytes or more, chunk_size <= 0, or a length without a second window");
+	memset(out, 0, sizeof *out);
+	out->declined_file = -1; out->declined_at = -1;
+	p->err.clear();
+	if (hipSetDevice(p->device) != hipSuccess) return p->fail(BWAGPU_ENODEV, "hipSetDevice failed");      // (the caller's thread may be another one than bwagpu_fastq_begin's)
+	FqArgs A;
+	const void *raw[2] = { raw1, raw2 }; const u64 len[2] = { (u64)len1, (u64)len2 }; const int eof[2] = { eof1, eof2 };
+	u32 tiles = 0; u64 cap_units = 0;
+	if (int rc = fq_setup(p, A, raw2 ? 2 : 1, len, eof, &tiles, &cap_units)) return rc;
+	for (int k = 0; k < A.nw; ++k)
+		if (len[k] && p->hip("copy window", hipMemcpyAsync(p->d_buf[k].p, raw[k], (size_t)len[k], hipMemcpyHostToDevice, p->st))) return BWAGPU_EHIP;
+	return fq_run(p, A, tiles, cap_units, chunk_size, out);
+}
+
+// ---- BGZF windows -> text (dev_bgzf.h) ---------------------------------------------------------------------------------------------
+// The host walks the block headers (BgzfPipe::block_len's test, host/host_input.h) and reads the trailers; the device inflates and tests.
+namespace {
+
+// total length of the BGZF block at p (header .. trailer), or 0 if p does not start one that lies within the n bytes in view
+size_t bz_block_len(const u8 *p, size_t n)
+{
+	if (n < 18 || p[0] != 0x1f || p[1] != 0x8b || p[2] != 8 || !(p[3] & 4)) return 0;
+	const size_t xlen = p[10] | (size_t)p[11] << 8;
+	if (12 + xlen > n) return 0;
+	for (size_t o = 12; o + 4 <= 12 + xlen;) {
+		const size_t sl = p[o + 2] | (size_t)p[o + 3] << 8;
+		if (p[o] == 'B' && p[o + 1] == 'C' && sl == 2 && o + 6 <= 12 + xlen) { const size_t bs = (p[o + 4] | (size_t)p[o + 5] << 8) + 1; return bs >= 12 + xlen + 8 && bs <= n ? bs : 0; }
+		o += 4 + sl;
+	}
+	return 0;
+}
+u32 bz_le32(const u8 *p) { return p[0] | (u32)p[1] << 8 | (u32)p[2] << 16 | (u32)p[3] << 24; }
+
+// the blocks a call takes from a window
+struct BzPlan {
+	std::vector<BzBlock> blk, table; std::vector<i64> coff;      // (blk[j].out: offset of the block's text among the taken blocks' text; table: as uploaded)
+	i64 used = 0, inflated = 0, host_bad = -1; bool cut_short = false;
+};
+void bz_walk(const u8 *comp, i64 comp_len, int eof, BzPlan &P)
+{
+	i64 o = 0;
+	while (o < comp_len) {
+		const size_t bl = bz_block_len(comp + o, (size_t)(comp_len - o));
+		if (!bl) break;
+		const size_t xlen = comp[o + 10] | (size_t)comp[o + 11] << 8;
+		const u32 isize = bz_le32(comp + o + bl - 4);
+		if (isize > BZ_MAX_OUT) { P.host_bad = o; break; }                       // (never size anything from an unbounded ISIZE)
+		if (P.inflated + (i64)isize >= ((i64)1 << 31)) { P.cut_short = true; break; }
+		BzBlock B; B.pay = (u64)o + 12 + xlen; B.pay_len = (u32)(bl - 12 - xlen - 8); B.isize = isize; B.crc = bz_le32(comp + o + bl - 8); B.pad = 0; B.out = (u64)P.inflated;
+		P.blk.push_back(B); P.coff.push_back(o);
+		P.inflated += isize; o += (i64)bl;
+	}
+	P.used = o;
+	if (P.host_bad < 0 && !P.cut_short && o < comp_len && eof) P.host_bad = o;   // a partial block, or bytes that are no block, where the input ends
+}
+
+// upload window k's taken blocks and their table: a block's text goes to blk.out + shift of the text buffer
+int bz_upload(bwagpu_fastq_parser_t *p, int k, const u8 *comp, BzPlan &P, u64 shift)
+{
+	const size_t nb = P.blk.size();
+	if (!nb) return 0;
+	if (p->d_comp[k].ensure((size_t)P.used + 32) || p->d_blk[k].ensure(nb * sizeof(BzBlock))) return p->fail(BWAGPU_ENOMEM, "hipMalloc failed (BGZF window)");
+	P.table = P.blk;                            // (lives until the caller has waited for the stream)
+	for (BzBlock &B : P.table) B.out += shift;
+	if (p->hip("copy blocks", hipMemcpyAsync(p->d_comp[k].p, comp, (size_t)P.used, hipMemcpyHostToDevice, p->st)) ||
+		p->hip("copy block table", hipMemcpyAsync(p->d_blk[k].p, P.table.data(), nb * sizeof(BzBlock), hipMemcpyHostToDevice, p->st))) return BWAGPU_EHIP;
+	return 0;
+}
+// one wavefront per block of window k
+void bz_launch(bwagpu_fastq_parser_t *p, int k, const BzPlan &P, u8 *dst)
+{
+	const size_t nb = P.blk.size();
+	if (!nb) return;
+	BzArgs A; A.comp = p->d_comp[k].as<u8>(); A.blk = p->d_blk[k].as<BzBlock>(); A.n_blocks = (u32)nb; A.out = dst; A.bad = p->d_bzstat.as<u64>() + k;
+	hipLaunchKernelGGL(k_bz_inflate, dim3((unsigned)nb), dim3(BZ_WAVE), 0, p->st, A);
+}
+
+void bz_info(const BzPlan &P, bwagpu_bgzf_info_t *I)
+{
+	memset(I, 0, sizeof *I);
+	I->used_comp = P.used; I->inflated = P.inflated; I->n_blocks = (int32_t)P.blk.size(); I->damaged_at = -1;
+}
+// the verdict of window k: the first damaged block's offset (device word `bad`), or what the walk found behind the blocks
+i64 bz_damage(bwagpu_fastq_parser_t *p, const BzPlan &P, u64 bad)
+{
+	if (bad) {
+		const u64 j = BZ_BIG - (bad >> 8);
+		const i64 at = j < P.coff.size() ? P.coff[j] : P.used;
+		p->err = "BGZF block at offset " + std::to_string(at) + " of its window is damaged (dev_bgzf.h BZ_E_* " + std::to_string((int)(bad & 255)) + ")";
+		return at;
+	}
+	if (P.host_bad >= 0) p->err = "no whole BGZF block with an ISIZE of at most 65536 at offset " + std::to_string(P.host_bad) + " of its window";
+	return P.host_bad;
+}
+
+}
+
+extern "C" int bwagpu_bgzf_inflate(bwagpu_fastq_parser_t *p, const void *comp, int64_t comp_len, int eof, void *dst, int64_t dst_cap, bwagpu_bgzf_info_t *info)
+{
+	if (!p) return BWAGPU_EINVAL;
+	if (!comp || comp_len < 0 || !dst || dst_cap < 0 || !info) return p->fail(BWAGPU_EINVAL, "bwagpu_bgzf_inflate: NULL argument or negative length");
+	p->err.clear();
+	BzPlan P;
+	bz_walk((const u8*)comp, comp_len, eof, P);
+	bz_info(P, info);
+	if (dst_cap < P.inflated) return p->fail(BWAGPU_EINVAL, "bwagpu_bgzf_inflate: dst_cap is smaller than the blocks' summed ISIZE");
+	if (hipSetDevice(p->device) != hipSuccess) return p->fail(BWAGPU_ENODEV, "hipSetDevice failed");
+	u64 bad[2] = { 0, 0 };
+	if (!P.blk.empty()) {
+		if (p->d_buf[0].ensure((size_t)P.inflated + 16) || p->d_bzstat.ensure(16)) return p->fail(BWAGPU_ENOMEM, "hipMalloc failed (BGZF text)");
+		if (p->hip("memset", hipMemsetAsync(p->d_bzstat.p, 0, 16, p->st))) return BWAGPU_EHIP;
+		if (int rc = bz_upload(p, 0, (const u8*)comp, P, 0)) return rc;
+		(void)hipEventRecord(p->ev[4], p->st);
+		bz_launch(p, 0, P, p->d_buf[0].as<u8>());
+		(void)hipEventRecord(p->ev[5], p->st);
+		if (p->hip("read back the verdict", hipMemcpyAsync(bad, p->d_bzstat.p, 16, hipMemcpyDeviceToHost, p->st)) || p->hip("sync", hipStreamSynchronize(p->st)) ||
+			p->hip("BGZF kernel", hipGetLastError())) return BWAGPU_EHIP;
+		float ms = 0; if (hipEventElapsedTime(&ms, p->ev[4], p->ev[5]) == hipSuccess) info->inflate_ms = ms;
+	}
+	info->damaged_at = bz_damage(p, P, bad[0]);
+	info->next_coff = P.used; info->next_uoff = 0;
+	if (info->damaged_at >= 0 || !P.inflated) return 0;
+	if (p->hip("download", hipMemcpyAsync(dst, p->d_buf[0].p, (size_t)P.inflated, hipMemcpyDeviceToHost, p->st)) || p->hip("sync", hipStreamSynchronize(p->st))) return BWAGPU_EHIP;
+	return 0;
+}
+
+extern "C" int bwagpu_fastq_batch_bgzf(bwagpu_fastq_parser_t *p, const bwagpu_bgzf_win_t *w1, const bwagpu_bgzf_win_t *w2, int chunk_size,
+									   bwagpu_fastq_out_t *out, bwagpu_bgzf_info_t info[2])
+{
+	if (!p) return BWAGPU_EINVAL;
+	const bwagpu_bgzf_win_t *w[2] = { w1, w2 };
+	const int nw = w2 ? 2 : 1;
+	bool ok = w1 && out && info && chunk_size > 0;
+	for (int k = 0; ok && k < nw; ++k) ok = w[k]->comp && w[k]->comp_len >= 0 && w[k]->skip >= 0;
+	if (!ok) return p->fail(BWAGPU_EINVAL, "bwagpu_fastq_batch_bgzf: NULL argument, negative length or skip, or chunk_size <= 0");
+	memset(out, 0, sizeof *out);
+	out->declined_file = -1; out->declined_at = -1;
+	p->err.clear();
+	BzPlan P[2];
+	memset(info, 0, 2 * sizeof info[0]);
+	info[1].damaged_at = -1;
+	for (int k = 0; k < nw; ++k) {
+		bz_walk((const u8*)w[k]->comp, w[k]->comp_len, w[k]->eof, P[k]);
+		bz_info(P[k], &info[k]);
+	}
+	for (int k = 0; k < nw; ++k) {
+		if (P[k].blk.empty() && w[k]->skip > 0 && !w[k]->eof && P[k].host_bad < 0) { out->status = BWAGPU_FQ_MORE; return 0; }      // (the first block is not in view yet)
+		if ((u32)w[k]->skip > (P[k].blk.empty() ? 0u : P[k].blk[0].isize)) return p->fail(BWAGPU_EINVAL, "bwagpu_fastq_batch_bgzf: skip is larger than the first block's ISIZE");
+	}
+	if (hipSetDevice(p->device) != hipSuccess) return p->fail(BWAGPU_ENODEV, "hipSetDevice failed");
+	// the text windows: buffers first (they may move), then the inflate into them.  Block text starts `pad` bytes into the buffer so that the
+	// text window -- skip bytes further on -- starts at a 16-byte boundary, as an uploaded window does
+	u64 len[2] = { 0, 0 }, pad[2] = { 0, 0 }; int eof[2] = { 1, 1 };
+	for (int k = 0; k < nw; ++k) {
+		len[k] = (u64)P[k].inflated - (u64)w[k]->skip; pad[k] = (16 - ((u64)w[k]->skip & 15)) & 15; eof[k] = w[k]->eof && !P[k].cut_short;
+		if (p->d_buf[k].ensure((size_t)(pad[k] + (u64)P[k].inflated + 16))) return p->fail(BWAGPU_ENOMEM, "hipMalloc failed (BGZF text)");
+	}
+	FqArgs A;
+	u32 tiles = 0; u64 cap_units = 0;
+	if (int rc = fq_setup(p, A, nw, len, eof, &tiles, &cap_units)) return rc;
+	if (p->d_bzstat.ensure(16)) return p->fail(BWAGPU_ENOMEM, "hipMalloc failed (BGZF status)");
+	if (p->hip("memset", hipMemsetAsync(p->d_bzstat.p, 0, 16, p->st))) return BWAGPU_EHIP;
+	for (int k = 0; k < nw; ++k) if (int rc = bz_upload(p, k, (const u8*)w[k]->comp, P[k], pad[k])) return rc;
+	(void)hipEventRecord(p->ev[4], p->st);
+	for (int k = 0; k < nw; ++k) {
+		bz_launch(p, k, P[k], p->d_buf[k].as<u8>());
+		A.w[k].buf = p->d_buf[k].as<u8>() + pad[k] + (u64)w[k]->skip;
+	}
+	(void)hipEventRecord(p->ev[5], p->st);
+	u64 bad[2] = { 0, 0 };
+	// the wait for the inflate's verdict
+	if (p->hip("read back the verdict", hipMemcpyAsync(bad, p->d_bzstat.p, 16, hipMemcpyDeviceToHost, p->st)) || p->hip("sync", hipStreamSynchronize(p->st)) ||
+		p->hip("BGZF kernel", hipGetLastError())) return BWAGPU_EHIP;
+	{ float ms = 0; if (hipEventElapsedTime(&ms, p->ev[4], p->ev[5]) == hipSuccess) info[0].inflate_ms = info[1].inflate_ms = ms; }
+	bool damaged = false;
+	for (int k = 0; k < nw; ++k) { info[k].damaged_at = bz_damage(p, P[k], bad[k]); damaged = damaged || info[k].damaged_at >= 0; info[k].next_coff = 0; info[k].next_uoff = w[k]->skip; }
+	if (damaged) { out->status = BWAGPU_FQ_DAMAGED; return 0; }
+	if (int rc = fq_run(p, A, tiles, cap_units, chunk_size, out)) return rc;
+	if (out->status == BWAGPU_FQ_CUT || out->status == BWAGPU_FQ_END)
+		for (int k = 0; k < nw; ++k) {
+			const u64 t = (u64)w[k]->skip + (u64)out->consumed[k];
+			info[k].next_coff = P[k].used; info[k].next_uoff = 0;
+			// the first block whose text reaches beyond t (empty blocks at t are stepped over)
+			size_t lo = 0, hi = P[k].blk.size();
+			while (lo < hi) { const size_t m = (lo + hi) >> 1; if (P[k].blk[m].out + P[k].blk[m].isize > t) hi = m; else lo = m + 1; }
+			if (lo < P[k].blk.size()) { info[k].next_coff = P[k].coff[lo]; info[k].next_uoff = (int32_t)(t - P[k].blk[lo].out); }
+		}
+	return 0;
 }

@@ -100,6 +100,7 @@ struct BgzfPipe {
 	std::mutex m; std::condition_variable cv;
 	std::deque<std::shared_ptr<BgzfGroup>> inflight; bool io_done = false, stop = false, bad = false; int pending = 0;
 	std::thread io; std::shared_ptr<BgzfGroup> cur; size_t cpos = 0;
+	size_t start_off = 0, drop = 0;      // where the stream starts: the offset of a block in the file, and the leading bytes of the text from there that are not delivered (0, 0: the whole file)
 	// total length of the BGZF block at p (header .. trailer), or 0 if p does not start one
 	static size_t block_len(const unsigned char *p, size_t n) {
 		if (n < 18 || p[0] != 0x1f || p[1] != 0x8b || p[2] != 8 || !(p[3] & 4)) return 0;
@@ -131,10 +132,12 @@ struct BgzfPipe {
 		if (map) munmap((void*)map, size);
 		if (fd >= 0) ::close(fd);
 	}
-	bool open(const char *fn, ParPool *pl) {
+	bool open(const char *fn, ParPool *pl, size_t block_off = 0, size_t drop_bytes = 0) {
 		fd = ::open(fn, O_RDONLY); if (fd < 0) return false;
 		struct stat st; if (fstat(fd, &st) != 0 || st.st_size <= 0) return false;
 		size = (size_t)st.st_size;
+		if (block_off > size) return false;
+		start_off = block_off; drop = drop_bytes;
 		void *mp = mmap(nullptr, size, PROT_READ, MAP_PRIVATE, fd, 0);
 		if (mp == MAP_FAILED) return false;
 		madvise(mp, size, MADV_SEQUENTIAL);
@@ -166,7 +169,7 @@ struct BgzfPipe {
 		G.out_len = w;
 	}
 	void scan() {
-		size_t off = 0;
+		size_t off = start_off;
 		const size_t group_bytes = getenv("BWAGPU_CLI_BGZF_GROUP") ? (size_t)atoll(getenv("BWAGPU_CLI_BGZF_GROUP")) : (size_t)512 << 10;   // (tests: a block per group)
 		while (off < size) {
 			{ std::unique_lock<std::mutex> l(m); cv.wait(l, [&] { return stop || inflight.size() < 16; }); if (stop) break; }
@@ -187,6 +190,7 @@ struct BgzfPipe {
 	// the next bytes of the inflated stream (blocking; in file order): > 0 bytes, 0 at the end, -1 for a damaged file
 	int read(char *dst, size_t cap) {
 		for (;;) {
+			if (cur && drop) { const size_t d = drop < cur->out_len - cpos ? drop : cur->out_len - cpos; cpos += d; drop -= d; }
 			if (cur && cpos < cur->out_len) { const size_t n = cur->out_len - cpos < cap ? cur->out_len - cpos : cap; memcpy(dst, cur->out.data() + cpos, n); cpos += n; return (int)n; }
 			cur.reset();
 			std::unique_lock<std::mutex> l(m);
@@ -234,6 +238,16 @@ struct Reader {
 		} else fp = gzdopen(fileno(stdin), "r");
 		if (fp) gzbuffer(fp, 1 << 20);
 		return fp != nullptr;
+	}
+	// a BGZF file from a virtual offset on: the block at block_off, without the first drop_bytes of the text from there (pool may be null: the blocks are inflated by the pipe's own thread)
+	bool open_bgzf_at(const char *fn, ParPool *pool, size_t block_off, size_t drop_bytes) {
+		size_t cap = 1 << 20;
+		if (getenv("BWAGPU_CLI_BUF")) { cap = (size_t)atoll(getenv("BWAGPU_CLI_BUF")); if (cap < 8) cap = 8; }
+		buf.resize(cap); nbuf.resize(cap);
+		bg.reset(new BgzfPipe());
+		if (bg->open(fn, pool, block_off, drop_bytes)) return true;
+		bg.reset();
+		return false;
 	}
 	int read_some(char *dst, size_t cap) {
 		int n;

@@ -49,6 +49,7 @@ static std::atomic<long> g_n_alns_reads(0);      // ... reads finalized from suc
 static int g_device_samtext = 0;  // BWAGPU_CLI_SAMTEXT=1: single-end batches without -5 take their SAM text from the device (bwagpu_batch_sam, after the CIGAR call, in place of bwagpu_batch_alns / bwagpu_batch_primary; device CIGARs on; same output); a read the device declines goes through the host formatter.
                                   // Paired-end batches, under BWAGPU_CLI_SAMPE's conditions (whether or not that switch is set): bwagpu_batch_sam_pe in place of every device call behind the download; a pair the device declines runs the host's mem_sam_pe on the download's lists
 static std::atomic<long> g_n_samtext_reads(0);   // ... reads written from such text
+static int g_device_bgzf = 0;     // BWAGPU_CLI_BGZF_DEV=1 (with BWAGPU_CLI_FASTQ=1): BGZF files (all of them, no -p) go to the device compressed and are inflated there (bwagpu_fastq_batch_bgzf)
 static int g_device_fastq = 0;    // BWAGPU_CLI_FASTQ=1: plain FASTQ files (one or two, no -p) are parsed on the device (bwagpu_fastq_batch): records, bseq_read's cut, base codes and the name / quality / comment
                                   // blobs of BWAGPU_CLI_SAMTEXT come from there; a batch the device declines, and the input behind it, goes through the reader below (same output)
 static std::string g_dev_rg_id; static bool g_dev_copy_comment = false;      // -R's id and -C for that call (set before the stages start)
@@ -409,6 +410,9 @@ struct DevInput {
 	bwagpu_fastq_parser_t *p = nullptr;
 	int nf = 0; std::string path[2]; int fd[2] = { -1, -1 }; const char *map[2] = { nullptr, nullptr }; size_t size[2] = { 0, 0 }, pos[2] = { 0, 0 };
 	bool fallback = false;
+	// BWAGPU_CLI_BGZF_DEV: the files are BGZF.  The position of a file is a BGZF virtual offset -- pos[k]: a block's offset in the file, uoff[k]: the byte in that block's text --, a
+	// window is compressed bytes from pos[k]: the chunk's three text bytes per base divided by the compression ratio (the first batch), then what the last batch took and a quarter, plus slack for the blocks at both ends, doubled on MORE
+	bool bgzf = false; size_t uoff[2] = { 0, 0 }, last_comp = 0; double ratio = 3.0; long n_bgzf_blocks = 0;
 	long n_dev_batches = 0, n_dev_reads = 0, n_host_batches = 0;
 	~DevInput() { for (int k = 0; k < 2; ++k) { if (map[k]) munmap((void*)map[k], size[k]); if (fd[k] >= 0) ::close(fd[k]); } if (p) bwagpu_fastq_end(p); }
 	// ParFile::open's test: a regular file that does not start with the gzip magic
@@ -417,7 +421,11 @@ struct DevInput {
 		const int f = ::open(fn, O_RDONLY);
 		if (f < 0) return false;
 		unsigned char magic[2] = { 0, 0 }; struct stat st;
-		if (!(fstat(f, &st) == 0 && S_ISREG(st.st_mode) && pread(f, magic, 2, 0) >= 0 && !(magic[0] == 0x1f && magic[1] == 0x8b))) { ::close(f); return false; }
+		if (!(fstat(f, &st) == 0 && S_ISREG(st.st_mode) && pread(f, magic, 2, 0) >= 0)) { ::close(f); return false; }
+		// plain files, or -- with BWAGPU_CLI_BGZF_DEV -- BGZF files, all of one kind; other gzip input stays with the host reader
+		const bool z = magic[0] == 0x1f && magic[1] == 0x8b;
+		if (z ? !(g_device_bgzf && BgzfPipe::is_bgzf(fn) && (k == 0 || bgzf)) : (k > 0 && bgzf)) { ::close(f); return false; }
+		if (z) bgzf = true;
 		size[k] = (size_t)st.st_size;
 		if (size[k] > 0) {
 			void *mp = mmap(nullptr, size[k], PROT_READ, MAP_PRIVATE, f, 0);
@@ -429,9 +437,73 @@ struct DevInput {
 		fd[k] = f; path[k] = fn;
 		return true;
 	}
+	// a batch from BGZF windows: next()'s contract
+	int next_bgzf(int chunk, Batch &out, HostBuf &flat, std::vector<int64_t> &off, int n_threads) {
+		// (blocks behind the cut are inflated for nothing: the window follows what the last batch took, a quarter more, rather than the plain path's generous bound)
+		size_t win = last_comp ? last_comp + last_comp / 4 + ((size_t)192 << 10) : (size_t)((double)window_for(chunk) / nf / (ratio > 1.0 ? ratio : 1.0)) + ((size_t)256 << 10);
+		std::shared_ptr<bwagpu_fastq_out_t> o(new bwagpu_fastq_out_t(), [](bwagpu_fastq_out_t *x) { bwagpu_fastq_out_free(x); delete x; });
+		memset(o.get(), 0, sizeof(bwagpu_fastq_out_t));
+		bwagpu_bgzf_info_t info[2];
+		for (;;) {
+			bwagpu_bgzf_win_t w[2]; bool all = true;
+			for (int k = 0; k < nf; ++k) {
+				const size_t left = size[k] - pos[k], len = left < win ? left : win;
+				w[k].comp = map[k] ? map[k] + pos[k] : ""; w[k].comp_len = (int64_t)len; w[k].skip = (int32_t)uoff[k]; w[k].eof = len == left;
+				all = all && len == left;
+			}
+			int rc;
+			{
+				std::unique_lock<std::mutex> serial(g_dev_mutex, std::defer_lock);
+				if (g_dev_serialize) serial.lock();
+				rc = bwagpu_fastq_batch_bgzf(p, &w[0], nf > 1 ? &w[1] : nullptr, chunk, o.get(), info);
+			}
+			if (rc != BWAGPU_OK) { fprintf(stderr, "[E::%s] bwagpu_fastq_batch_bgzf: %s: %s\n", "main_mem", bwagpu_strerror(rc), bwagpu_fastq_last_error(p)); fflush(stderr); fflush(stdout); _exit(EXIT_FAILURE); }
+			if (o->status == BWAGPU_FQ_DAMAGED) {
+				for (int k = 0; k < nf; ++k)
+					if (info[k].damaged_at >= 0) fprintf(stderr, "[E::%s] `%s' is a damaged or truncated BGZF file (a block does not inflate to its recorded size and checksum)\n", "main_mem", path[k].c_str());
+				fflush(stderr); fflush(stdout); _exit(EXIT_FAILURE);
+			}
+			if (o->status == BWAGPU_FQ_MORE) {
+				if (all) return -1;      // (cannot be: every window ended with its file)
+				win *= 2;
+				continue;
+			}
+			break;
+		}
+		if (o->status == BWAGPU_FQ_DECLINED) return -1;
+		int64_t used = 0, inflated = 0;
+		for (int k = 0; k < nf; ++k) { used += info[k].used_comp; inflated += info[k].inflated; n_bgzf_blocks += info[k].n_blocks; }
+		if (used > 0 && inflated > 0) ratio = (double)inflated / (double)used;
+		const int n = o->n_reads;
+		if (n == 0) return 0;
+		out.seqs.clear(); out.text.clear(); out.blocks.clear();
+		out.seqs.resize((size_t)n);
+		out.text.resize((size_t)(o->name_off[n] + o->comment_off[n] + o->off[n]) + 3 * (size_t)n);
+		char *A = out.text.data();
+		const bwagpu_fastq_out_t *r = o.get();
+		// (the text exists on the device only: the fields come from the call's blobs)
+		parallel_for(n_threads < 4 ? n_threads : 4, n, [&](long i) {
+			Seq &s = out.seqs[(size_t)i];
+			s = Seq();
+			const size_t ln = (size_t)(r->name_off[i + 1] - r->name_off[i]), lc = (size_t)(r->comment_off[i + 1] - r->comment_off[i]), ls = (size_t)(r->off[i + 1] - r->off[i]);
+			size_t a = (size_t)(r->name_off[i] + r->comment_off[i] + r->off[i]) + 3 * (size_t)i;
+			s.name = a; s.l_name = (int)ln; memcpy(A + a, r->names + r->name_off[i], ln); a += ln; A[a++] = 0;
+			s.comment = a; s.has_comment = r->has_comment[i] != 0; memcpy(A + a, r->comments + r->comment_off[i], lc); a += lc; A[a] = 0;
+			s.seq = a++;
+			s.qual = a; s.l_seq = (int)ls; s.l_qual = (int)ls; s.has_qual = true; memcpy(A + a, r->quals + r->off[i], ls); A[a + ls] = 0;
+		});
+		off.assign(o->off, o->off + n + 1);
+		{ HostBuf b; b.p = o->seqs; b.cap = (size_t)o->off[n] + 1; o->seqs = nullptr; flat = std::move(b); }
+		last_comp = 0;
+		for (int k = 0; k < nf; ++k) { pos[k] += (size_t)info[k].next_coff; uoff[k] = (size_t)info[k].next_uoff; if ((size_t)info[k].next_coff > last_comp) last_comp = (size_t)info[k].next_coff; }
+		out.fq = o;
+		++n_dev_batches; n_dev_reads += n;
+		return 1;
+	}
 	static size_t window_for(int chunk) { const size_t w = (size_t)chunk * 3 + ((size_t)1 << 20); return w < ((size_t)1 << 31) - 1 ? w : ((size_t)1 << 31) - 1; }
 	// 1: a batch in out (flat / off: the codes); 0: the input has ended; -1: declined -- the caller's reader takes over at pos[]
 	int next(int chunk, Batch &out, HostBuf &flat, std::vector<int64_t> &off, int n_threads) {
+		if (bgzf) return next_bgzf(chunk, out, flat, off, n_threads);
 		size_t win = window_for(chunk);
 		std::shared_ptr<bwagpu_fastq_out_t> o(new bwagpu_fastq_out_t(), [](bwagpu_fastq_out_t *x) { bwagpu_fastq_out_free(x); delete x; });
 		memset(o.get(), 0, sizeof(bwagpu_fastq_out_t));
@@ -1108,6 +1180,7 @@ int main(int argc, char *argv[])
 	}
 	// BWAGPU_CLI_FASTQ: the device parser and its window buffers, before the suffix array below is sized against the free memory
 	if (getenv("BWAGPU_CLI_FASTQ")) g_device_fastq = atoi(getenv("BWAGPU_CLI_FASTQ"));
+	if (getenv("BWAGPU_CLI_BGZF_DEV")) g_device_bgzf = atoi(getenv("BWAGPU_CLI_BGZF_DEV"));
 	std::unique_ptr<DevInput> dev_in;
 	if (g_device_fastq && !(opt.flag & F_SMARTPE) && !getenv("BWAGPU_CLI_PARSE_ONLY")) {
 		dev_in.reset(new DevInput());
@@ -1303,6 +1376,9 @@ int main(int argc, char *argv[])
 					dev_in->fallback = true;
 					Source *rs[2] = { &r1, &r2 };
 					for (int k = 0; k < dev_in->nf; ++k)
+						if (dev_in->bgzf) {      // (from the batch's start virtual offset: the block there, less the text earlier batches took)
+							if (!rs[k]->ser.open_bgzf_at(dev_in->path[k].c_str(), parse_pool.get(), dev_in->pos[k], dev_in->uoff[k])) { fprintf(stderr, "[E::%s] fail to re-open file `%s'.\n", "main_mem", dev_in->path[k].c_str()); exit(EXIT_FAILURE); }
+						} else
 						if (!rs[k]->open(dev_in->path[k].c_str(), nullptr) || rs[k]->ser.raw_fd < 0 || lseek(rs[k]->ser.raw_fd, (off_t)dev_in->pos[k], SEEK_SET) < 0) { fprintf(stderr, "[E::%s] fail to re-open file `%s'.\n", "main_mem", dev_in->path[k].c_str()); exit(EXIT_FAILURE); }
 					if (tl_trace) fprintf(stderr, "[D::input] the device declined batch %ld: the streaming reader takes over at bytes %zu / %zu\n", no, dev_in->pos[0], dev_in->pos[1]);
 				}
@@ -1439,6 +1515,7 @@ int main(int argc, char *argv[])
 	writer.join();
 	all_done = true; watchdog.join();
 	if (dev_in && tl_trace) fprintf(stderr, "[D::input] %ld batches (%ld reads) parsed on the device, %ld by the host reader\n", dev_in->n_dev_batches, dev_in->n_dev_reads, dev_in->n_host_batches);
+	if (dev_in && dev_in->bgzf && tl_trace) fprintf(stderr, "[D::input] %ld BGZF blocks inflated on the device\n", dev_in->n_bgzf_blocks);
 	if (g_device_rescue && tl_trace && hostmem::g_pairs_merged_on_device.load() > 0)
 		fprintf(stderr, "[D::main_mem] %ld pairs merged on the device (BWAGPU_CLI_RESCUE), %ld of them with rescue alignments\n", hostmem::g_pairs_merged_on_device.load(), hostmem::g_pairs_merged_aligned.load());
 	if (g_device_pair && tl_trace) fprintf(stderr, "[D::main_mem] %ld pairs paired from device records (BWAGPU_CLI_PAIR)\n", hostmem::g_pairs_from_device.load());

@@ -644,6 +644,55 @@ void bwagpu_fastq_out_free(bwagpu_fastq_out_t *out);
 void bwagpu_fastq_end(bwagpu_fastq_parser_t *p);
 int  bwagpu_fastq_rec_size(void);   /* sizeof(bwagpu_fastq_rec_t) as compiled */
 
+/* ---- BGZF input inflated on the device (bgzip's block-compressed gzip, SAM specification 4.1), on the same parser ------------- */
+/* A window here is COMPRESSED bytes that start at a BGZF block start.  The library walks the block headers on the host: a block is a
+ * gzip member (magic 1f 8b, CM 8, FEXTRA set) with a `BC' subfield of length 2 anywhere among its extra subfields whose BSIZE is
+ * consistent with XLEN and lies within the bytes in view; its trailer holds CRC-32 and ISIZE.  Whole blocks are taken for as long as
+ * their ISIZEs sum to less than 2^31; what was not taken is as if it were not in the window (eof then does not apply to this call).
+ * A trailing partial block without eof is left for the next call; with eof, it -- or bytes that are no block -- is damage.  Empty
+ * blocks (bgzip's 28-byte end-of-file marker, anywhere) are ordinary.  The compressed bytes and a table of the blocks go up, every
+ * block is inflated by one wavefront (dev_bgzf.h) and tested as zlib's inflate(Z_FINISH) plus the trailer test it: all three block
+ * types, any number of deflate blocks, unused payload bytes behind the final one allowed; block type 3, LEN != ~NLEN, HLIT > 286,
+ * HDIST > 30, an over-subscribed or (but for zlib's one-bit exception) incomplete code, no end-of-block code, symbols 286 / 287 / 30 /
+ * 31, a distance before the block's own text, a stream that runs past the payload, text longer or shorter than ISIZE, ISIZE above
+ * 65536 and a CRC-32 that differs are damage.  A damaged block ends in a status, never in an access outside its buffers.
+ *
+ * bwagpu_bgzf_inflate: the decoder alone.  The text of the blocks taken goes to dst (host memory, dst_cap bytes): info->inflated bytes.
+ * When a block is damaged (info->damaged_at >= 0) nothing is written to dst.  Returns BWAGPU_EINVAL for NULL p / comp / dst / info, a
+ * negative length, and a dst_cap below the blocks' summed ISIZE.
+ *
+ * bwagpu_fastq_batch_bgzf: bwagpu_fastq_batch over the text of one or two BGZF windows.  The text never exists on the host: the
+ * blocks are inflated into the parser's window buffer and the text window the parse sees begins `skip' bytes into it -- skip is the
+ * part of the first block's text that earlier batches consumed, 0 <= skip <= that block's ISIZE (0 when the window holds no block), else
+ * BWAGPU_EINVAL; a window without eof that is too short for its first block is BWAGPU_FQ_MORE whatever skip is.  From there it is bwagpu_fastq_batch: the same kernels, statuses, outputs, and its two host waits behind one for the
+ * inflate's verdict.  consumed[k], declined_at and the offsets in recs are in the text window's coordinates (recs: offsets into
+ * device-side text; the blobs names / quals / comments / seqs are the content).  eof of a text window: the window's eof, unless blocks
+ * were left out by the 2^31 rule.
+ *   BWAGPU_FQ_MORE      as before: repeat the call from the same start with more compressed bytes.
+ *   BWAGPU_FQ_DAMAGED   a block taken from either window is damaged, or eof is set and the window does not end with a whole block:
+ *                       n_reads == 0, no arrays, damaged_at set in that window's info (the other's is -1 unless it is damaged too).
+ *                       DAMAGED wins over DECLINED: nothing of a window with a damaged block is interpreted.
+ * info[k] (k = 0, 1; info[1] is zeroed with damaged_at -1 for one window):
+ *   next_coff / next_uoff (CUT, END): the BGZF virtual offset of the first byte not consumed -- the block's start in comp and the byte
+ *   in that block's text; next_uoff is below that block's ISIZE, or next_coff == used_comp with next_uoff == 0 when all the text taken
+ *   was consumed.  The next call's window starts at comp + next_coff with skip = next_uoff.
+ * BWAGPU_EINVAL: NULL p / w1 / w1->comp / out / info, w2 with a NULL comp, a negative comp_len or skip, skip beyond the first block's
+ * ISIZE, chunk_size <= 0. */
+enum { BWAGPU_FQ_DAMAGED = 4 };
+typedef struct { const void *comp; int64_t comp_len; int32_t skip, eof; } bwagpu_bgzf_win_t;
+typedef struct {
+	int64_t used_comp;     /* bytes of comp covered by the whole blocks this call took */
+	int64_t inflated;      /* their ISIZEs summed */
+	int32_t n_blocks;
+	int64_t next_coff; int32_t next_uoff;   /* CUT / END: virtual offset of the first byte not consumed */
+	int64_t damaged_at;    /* offset in comp of the first block that is not a BGZF block or does not inflate to its ISIZE and CRC; else -1 */
+	float inflate_ms;      /* device time of the inflate kernel (batch_bgzf: of both windows' launches, in both infos) */
+} bwagpu_bgzf_info_t;
+int  bwagpu_bgzf_inflate(bwagpu_fastq_parser_t *p, const void *comp, int64_t comp_len, int eof,
+                         void *dst, int64_t dst_cap, bwagpu_bgzf_info_t *info);
+int  bwagpu_fastq_batch_bgzf(bwagpu_fastq_parser_t *p, const bwagpu_bgzf_win_t *w1, const bwagpu_bgzf_win_t *w2 /* NULL: one file */,
+                             int chunk_size, bwagpu_fastq_out_t *out, bwagpu_bgzf_info_t info[2]);
+
 /* ---- lifetime ------------------------------------------------------------------------------------------ */
 
 /* Create a handle on HIP device `device` and upload the index once (replaces nothing in the reference; it is
