@@ -63,7 +63,7 @@ EXPORTS = [
     "bwagpu_batch_primary", "bwagpu_primary_flat", "bwagpu_primary_limits", "bwagpu_batch_pair", "bwagpu_pair_flat", "bwagpu_pair_limits", "bwagpu_batch_rescue", "bwagpu_rescue_flat", "bwagpu_rescue_limits",
     "bwagpu_batch_pestat", "bwagpu_pestat_flat", "bwagpu_batch_pestat_hist", "bwagpu_pestat_finish", "bwagpu_pestat_limits",
     "bwagpu_batch_alns", "bwagpu_alns_flat", "bwagpu_alns_limits", "bwagpu_aln_size",
-    "bwagpu_cigars_flat", "bwagpu_cigar_limits",
+    "bwagpu_cigars_flat", "bwagpu_cigar_limits", "bwagpu_dedup_flat", "bwagpu_dedup_limits",
     "bwagpu_batch_sampe", "bwagpu_sampe_flat", "bwagpu_sampe_limits", "bwagpu_sampe_size",
     "bwagpu_set_contig_names", "bwagpu_batch_sam", "bwagpu_sam_flat", "bwagpu_sam_limits",
     "bwagpu_trim", "bwagpu_set_option", "bwagpu_get_option", "bwagpu_set_default_option", "bwagpu_clear_default_options", "bwagpu_option_name",
@@ -105,6 +105,8 @@ def load_library(path: str | None = None) -> C.CDLL:
     L.bwagpu_batch_cigar_ops.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.bwagpu_cigars_flat.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 8
     L.bwagpu_cigar_limits.restype = None
+    L.bwagpu_dedup_flat.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 8
+    L.bwagpu_dedup_limits.restype = None
     L.bwagpu_tap_intervals.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.bwagpu_tap_chains.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.bwagpu_tap_regs_raw.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -322,6 +324,28 @@ class BwaGpu:
         out = (C.c_int32 * 10)()
         self.L.bwagpu_cigar_limits(out)
         return dict(zip(("max_len", "z_small", "z_big", "max_cols", "max_ops", "tmp_ops", "md_cap", "long_max_cols", "long_max_ops", "long_qcap"), list(out)))
+
+    def dedup_flat(self, opt: MemOpt, seqs: np.ndarray, off: np.ndarray, counts: np.ndarray, regs: np.ndarray):
+        """bwagpu_dedup_flat: the de-duplication stage of run() on reads (nt4, int64 offsets) and raw region lists of the caller (read i: counts[i] records of regs)
+        -> (counts left per read, their ALNREG_DTYPE records read by read, the routine that finished each read: 0 dedup_read, 1 dedup_read_wave, 2 dedup_read_par)."""
+        seqs = np.ascontiguousarray(seqs, dtype=np.uint8)
+        off = np.ascontiguousarray(off, dtype=np.int64)
+        counts = np.ascontiguousarray(counts, dtype=np.int32)
+        regs = np.ascontiguousarray(regs, dtype=ALNREG_DTYPE)
+        assert off.shape[0] == counts.shape[0] + 1 and int(off[-1]) == seqs.shape[0] and int(counts.sum()) == regs.shape[0]
+        left = np.zeros(counts.shape[0], dtype=np.int32)
+        form = np.full(counts.shape[0], -1, dtype=np.int32)
+        p, n = C.c_void_p(), C.c_int64()
+        self._chk(self.L.bwagpu_dedup_flat(self.h, C.byref(opt), counts.shape[0], seqs.ctypes.data, off.ctypes.data, counts.ctypes.data, regs.ctypes.data,
+                                           left.ctypes.data, C.byref(p), C.byref(n), form.ctypes.data))
+        assert n.value == int(left.sum())
+        return left, self._take(p, n.value, ALNREG_DTYPE), form
+
+    def dedup_limits(self) -> dict:
+        """bwagpu_dedup_limits: the switch points of the de-duplication stage, as compiled."""
+        out = (C.c_int32 * 8)()
+        self.L.bwagpu_dedup_limits(out)
+        return dict(zip(("heavy", "stage", "net", "keysort_min", "scan_block", "draw", "ring_min", "lds_per_reg"), list(out)))
 
     def matesw(self, opt: MemOpt, pes: np.ndarray):
         """bwagpu_batch_matesw: precomputed mate-rescue alignments (MATESW_DTYPE) for the last download(); pes = PES_DTYPE[4]."""

@@ -119,6 +119,8 @@ struct bwagpu_s {
 	DevBuf d_sp[SP_N];      // bwagpu_batch_sampe / bwagpu_sampe_flat (dev_sampe.h): the pair records, the wavefront form's pair list and its length, the merged lists' region-to-read map, their CIGAR records and operation array
 	enum { CF_SEQ, CF_SEQOFF, CF_READ, CF_CIGS, CF_EXT, CF_N };
 	DevBuf d_cf[CF_N];      // bwagpu_cigars_flat: the caller's reads and their offsets, the region-to-read map, the CIGAR records and the operation array (none of them a batch's)
+	enum { DF_SEQ, DF_SEQOFF, DF_REGS, DF_REGOFF, DF_NRAW, DF_CNT, DF_FORM, DF_BLOB, DF_DPH, DF_DPE, DF_CTR, DF_N };
+	DevBuf d_df[DF_N];     // bwagpu_dedup_flat: the caller's reads, offsets, regions and counts, the counts left, the routine per read, the sorts' key scratch, DP scratch, counters (none of them a batch's)
 	i64 cigl_z_cap = 0;                          // bytes per direction matrix of the long CIGAR tier's scratch (grows with the batches)
 	DevBuf d_cigl_z, d_cigl_ops, d_cigl_md, d_cigl_list;      // scratch of the long-segment CIGAR tier (k_cigar_long): direction matrices, operations, MD strings per workgroup
 	DevBuf d_cig_ext; i64 cig_ext_n = -1;   // operation array of the last bwagpu_batch_cigars (records with 7..64 operations point into it)
@@ -529,6 +531,7 @@ extern "C" void bwagpu_destroy(bwagpu_t *h)
 	for (DevBuf &b : h->d_rs) b.release();
 	for (DevBuf &b : h->d_sp) b.release();
 	for (DevBuf &b : h->d_cf) b.release();
+	for (DevBuf &b : h->d_df) b.release();
 	for (DevBuf &b : h->d_st) b.release();
 	for (int i = 0; i < 8; ++i) if (h->ev[i]) (void)hipEventDestroy(h->ev[i]);
 	if (h->ev_wait) (void)hipEventDestroy(h->ev_wait);
@@ -1044,6 +1047,85 @@ extern "C" int bwagpu_mem_info(bwagpu_t *h, uint64_t *free_bytes, uint64_t *tota
 }
 
 namespace { struct BusyGuard { std::atomic<int> &c; int others; explicit BusyGuard(std::atomic<int> &c_) : c(c_), others(c_.fetch_add(1)) {} ~BusyGuard() { --c; } }; }
+// ---- the de-duplication stage's plan and launches (bwagpu_batch_run and bwagpu_dedup_flat) ----------------------------------------------------------------
+// heavy_min: regions from which k_dedup leaves a read to the wave-per-read launches (0: it does every read itself); rc, q_cap, lds0: the patch alignments' ring,
+// query room and their LDS bytes; cap_m / cap_b: regions the LDS arrays of the two list launches hold; blk_m / blk_b: their workgroups
+#define DEDUP_HEAVY_DEFAULT 3      // options dedup_heavy and dedup_stage left at auto
+#define DEDUP_STAGE_DEFAULT 128
+#define DEDUP_RING_MIN 256         // columns of the patch alignments' smallest ring
+struct DedupPlan { int heavy_min = 0, rc = 0, q_cap = 0, cap_m = 0, cap_b = 0; size_t lds0 = 0; long long blk_m = 0, blk_b = 0; };
+static long long share_of(long long g, bool long_batch, long long share_pct)      // option share (see bwagpu_batch_run): g workgroups fill the chip; a short-read batch launches share_pct percent of them
+{
+	if (long_batch || share_pct >= 100 || share_pct <= 0) return g;
+	const long long v = g * share_pct / 100; return v < 1 ? 1ll : v;
+}
+// The plan for n reads of up to max_len bases; dp_waves: the scratch regions dp_h / dp_e will hold.  Sizes the handle's list and staging buffers.
+static int dedup_plan(bwagpu_t *h, const bwagpu_opt_t *opt, const BwagpuConfig &cfg, int max_len, int n, bool long_batch, long long share_pct, long long dp_waves, DedupPlan &dd)
+{
+	dd = DedupPlan();
+	// k_dedup's list of the reads it leaves to the wave-per-read kernel: the seeding kernels' list of heavy reads, free again by then
+	dd.heavy_min = long_batch || cfg.dedup_wave || h->seq_len >= ((u64)1 << 47) || max_len >= (1 << 16) ? 0 : (int)(cfg.dedup_heavy < 0 ? DEDUP_HEAVY_DEFAULT : cfg.dedup_heavy);     // (the bounds: DdKey, dev_dedupp.h)
+	if (dd.heavy_min > 0) {
+		int need = 8 * opt->w + 4 + 128; if (need < max_len / 4 + 132) need = max_len / 4 + 132;
+		dd.rc = DEDUP_RING_MIN; while (dd.rc < need && dd.rc < 4096) dd.rc <<= 1;
+		dd.q_cap = (max_len + 15) & ~15;
+		if (8 * dd.rc + 32 + dd.q_cap > 65536) dd.q_cap = 0;
+		dd.lds0 = (size_t)8 * dd.rc + 32 + dd.q_cap;
+		const long long room = (65536 - (long long)dd.lds0) / (long long)DDP_LDS_PER_REG;       // regions a workgroup's LDS holds next to the ring
+		dd.cap_m = (int)(cfg.dedup_stage < 0 ? DEDUP_STAGE_DEFAULT : cfg.dedup_stage); if (dd.cap_m > room) dd.cap_m = (int)(room > 0 ? room : 0);
+		dd.cap_b = (int)(cfg.dedup_big < 0 ? room : cfg.dedup_big); if (dd.cap_b > room) dd.cap_b = (int)(room > 0 ? room : 0);
+		const long long wpc_m = (160 * 1024) / (long long)(dd.lds0 + DDW_PAR_BYTES(dd.cap_m)), wpc_b = (160 * 1024) / (long long)(dd.lds0 + DDW_PAR_BYTES(dd.cap_b));
+		dd.blk_m = share_of(256 * (wpc_m > 12 ? 12 : wpc_m), long_batch, share_pct); dd.blk_b = share_of(256 * (wpc_b > 12 ? 12 : wpc_b), long_batch, share_pct);
+		const long long cap = dp_waves > 0 ? dp_waves : 1;       // (dp_h / dp_e hold one scratch region per wave)
+		if (dd.blk_m > cap) dd.blk_m = cap; if (dd.blk_b > cap) dd.blk_b = cap;
+		if (dd.blk_m > n) dd.blk_m = n; if (dd.blk_b > n) dd.blk_b = n;
+		if (h->d_heavy.ensure((size_t)n * 4 + 16) || h->d_dd_tmp.ensure(((size_t)dd.blk_m * dd.cap_m + (size_t)dd.blk_b * dd.cap_b) * sizeof(bwagpu_alnreg_t) + 16)) { h->err = "hipMalloc failed (de-duplication lists)"; return BWAGPU_ENOMEM; }
+	}
+	return BWAGPU_OK;
+}
+// The stage's kernels on batch B (n reads of up to max_len bases; lane_blocks: workgroups of the lane-per-read kernel); sets B's dd_* fields.
+static void dedup_launch(bwagpu_t *h, const bwagpu_opt_t *opt, const BwagpuConfig &cfg, Batch &B, int max_len, int n, bool long_batch, long long share_pct, unsigned lane_blocks, const DedupPlan &dd)
+{
+	const dim3 block(BLOCK);
+	if (long_batch || cfg.dedup_wave) {     // long reads: few reads, long patch alignments -> one wavefront per read
+		// Ring of {H,E} columns for the patch alignments' band: 2 w + 132 columns, where w = max(min(.., 4 opt.w), |rlen - l_query| + 3) (bwa.c:180-187)
+		// and the length difference of two merged regions of a 10 kb read with 13 % indels runs to several hundred bases.  A band the ring
+		// cannot hold falls back to one lane with its columns in HBM -- 10^7 cells at one lane's pace: measured 0.6 s per call, 58 s of a
+		// 100-read batch's 59 (profiles/r03_longread_probe.md) -- so the ring is sized for 1/8 of the longest read and capped by what one
+		// wave's LDS share allows; wider rings mean fewer waves per workgroup (the dynamic LDS of a workgroup is 64 KiB).
+		int need = 8 * opt->w + 4 + 128; if (need < max_len / 4 + 132) need = max_len / 4 + 132;
+		int rc_ = DEDUP_RING_MIN; while (rc_ < need && rc_ < 4096) rc_ <<= 1;
+		if (cfg.dedup_ring > 0) rc_ = (int)cfg.dedup_ring;      // test hook: a power of two, 256..4096
+		if (rc_ < DEDUP_RING_MIN || rc_ > 4096 || (rc_ & (rc_ - 1))) rc_ = 1024;
+		const bool dedup_blk = (cfg.dedup_blk >= 0 ? cfg.dedup_blk : 1) != 0;   // four columns per lane in the patch alignments (wave_global2_score_ring_blk: 381 -> 207 ms per 6000 x 10 kb reads, BENCH_r03 variants); needs the segment in LDS
+		int q_cap = dedup_blk ? (max_len + 15) & ~15 : 0;      // room for a patch alignment's query segment next to the ring
+		if (8 * rc_ + 32 + q_cap > 65536) q_cap = 0;
+		int wpb = rc_ <= 1024 ? 4 : (rc_ <= 2048 ? 2 : 1);
+		while (wpb > 1 && (8 * rc_ + 32 + q_cap) * wpb > 65536) wpb >>= 1;
+		i64 nblk = ((i64)n + wpb - 1) / wpb, cap = B.dp_waves / wpb > 0 ? B.dp_waves / wpb : 1;   // dp_h/dp_e hold one scratch region per wave
+		if (dedup_blk && q_cap) hipLaunchKernelGGL(k_dedup_wave<true>, dim3((unsigned)(nblk < cap ? nblk : cap)), dim3(64 * wpb), (size_t)(8 * rc_ + 32 + q_cap) * wpb, h->stream, h->ix, *opt, B, rc_, q_cap, 0, 0, (bwagpu_alnreg_t*)nullptr);
+		else hipLaunchKernelGGL(k_dedup_wave<false>, dim3((unsigned)(nblk < cap ? nblk : cap)), dim3(64 * wpb), (size_t)(8 * rc_ + 32 + q_cap) * wpb, h->stream, h->ix, *opt, B, rc_, q_cap, 0, 0, (bwagpu_alnreg_t*)nullptr);
+	} else {
+		// Lane per read for the reads with one or two regions (nine in ten of the headline's); the others are listed by k_dedup and done by two more
+		// launches, one wavefront per read with the decisions' operands in LDS (dedup_read_par, dev_dedupp.h): the reads of up to dedup_stage regions
+		// (16.6 KB of LDS per wave, nine to a CU), then the few with more (up to dedup_big regions in 64 KB; beyond that, in place in HBM).
+		B.dd_heavy_min = dd.heavy_min; B.dd_list = h->d_heavy.as<i32>(); B.dd_prio = cfg.dedup_prio != 0; B.dd_net = (int)(cfg.dedup_net < 0 ? DEDUP_NET_DEFAULT : cfg.dedup_net);
+		B.dd_stage_cap = dd.cap_m > 0 ? dd.cap_m : 0x3fffffff;      // (no LDS arrays: one list, every read in place)
+		hipLaunchKernelGGL(k_dedup, dim3((unsigned)share_of(lane_blocks, long_batch, share_pct)), block, 0, h->stream, h->ix, *opt, B);
+		if (B.dd_heavy_min > 0) {
+			bwagpu_alnreg_t *tmp = h->d_dd_tmp.as<bwagpu_alnreg_t>();
+			const size_t lds_m = dd.lds0 + DDW_PAR_BYTES(dd.cap_m), lds_b = dd.lds0 + DDW_PAR_BYTES(dd.cap_b);
+			if (dd.q_cap) hipLaunchKernelGGL((k_dedup_wave<true, true>), dim3((unsigned)dd.blk_m), dim3(64), lds_m, h->stream, h->ix, *opt, B, dd.rc, dd.q_cap, dd.cap_m, 0, tmp);
+			else hipLaunchKernelGGL((k_dedup_wave<false, true>), dim3((unsigned)dd.blk_m), dim3(64), lds_m, h->stream, h->ix, *opt, B, dd.rc, dd.q_cap, dd.cap_m, 0, tmp);
+			if (dd.cap_m > 0) {
+				tmp += (size_t)dd.blk_m * dd.cap_m;
+				if (dd.q_cap) hipLaunchKernelGGL((k_dedup_wave<true, true>), dim3((unsigned)dd.blk_b), dim3(64), lds_b, h->stream, h->ix, *opt, B, dd.rc, dd.q_cap, dd.cap_b, 1, tmp);
+				else hipLaunchKernelGGL((k_dedup_wave<false, true>), dim3((unsigned)dd.blk_b), dim3(64), lds_b, h->stream, h->ix, *opt, B, dd.rc, dd.q_cap, dd.cap_b, 1, tmp);
+			}
+		}
+	}
+}
+
 extern "C" int bwagpu_batch_run(bwagpu_t *h, const bwagpu_opt_t *opt)
 {
 	if (!h || !opt || !h->have_batch) return BWAGPU_EINVAL;
@@ -1079,7 +1161,7 @@ extern "C" int bwagpu_batch_run(bwagpu_t *h, const bwagpu_opt_t *opt)
 	// the chip to itself while the reader is still parsing the second: 151 -> ~90 ms, `profiles/r05_e2e_reserve_results.log`).  Measured with three batches in flight (profiles/r05_share_ab.log): 108.3 ms per step at 100, 105.2-105.7 at 50 (105.1 at 40,
 	// 107.1 at 60), i.e. -2.7 %, for +10 % on a batch that has the chip to itself (131.8 -> 144.8 ms) -- round 4 measured nothing; the kernels' balance has moved.
 	const long long share_pct = cfg.share >= 0 ? cfg.share : (h->ibuf->refs.load() >= 3 && busy.others > 0 ? 50 : 100);
-	auto share = [&](long long g) { if (long_batch || share_pct >= 100 || share_pct <= 0) return g; const long long v = g * share_pct / 100; return v < 1 ? 1ll : v; };
+	auto share = [&](long long g) { return share_of(g, long_batch, share_pct); };
 	auto pick = [&](long long v, long long dflt_long) { return v >= 0 ? v : (long_batch ? dflt_long : 0); };
 	// Pass 1 of long-read batches as independent tasks (option seed_tasks; dev_seed.h, k_seed's LR): one task per read and min_seed_len-th
 	// position.  The host only says where each read's tasks begin; a task finds its read by bisection.
@@ -1118,24 +1200,8 @@ extern "C" int bwagpu_batch_run(bwagpu_t *h, const bwagpu_opt_t *opt)
 	const int heavy_lanes = heavy_tasks ? (int)(((i64)n * heavy_tpr + BLOCK - 1) / BLOCK * BLOCK < 256 * 3 * BLOCK ? ((i64)n * heavy_tpr + BLOCK - 1) / BLOCK * BLOCK : 256 * 3 * BLOCK) : 0;
 	if (heavy_tasks && (h->d_intv_n3.ensure((size_t)n * 4 + 16) || h->d_heavy.ensure((size_t)n * 4 + 16))) { h->err = "hipMalloc failed (seeding tasks)"; return BWAGPU_ENOMEM; }
 	// k_dedup's list of the reads it leaves to the wave-per-read kernel: the seeding kernels' list of heavy reads, free again by then
-	const int dd_heavy_min = long_batch || cfg.dedup_wave || h->seq_len >= ((u64)1 << 47) || h->max_len >= (1 << 16) ? 0 : (int)(cfg.dedup_heavy < 0 ? 3 : cfg.dedup_heavy);     // (the bounds: DdKey, dev_dedupp.h)
-	struct { int rc, q_cap, cap_m, cap_b; size_t lds0; long long blk_m, blk_b; } dd = { 0, 0, 0, 0, 0, 0, 0 };
-	if (dd_heavy_min > 0) {
-		int need = 8 * opt->w + 4 + 128; if (need < h->max_len / 4 + 132) need = h->max_len / 4 + 132;
-		dd.rc = 256; while (dd.rc < need && dd.rc < 4096) dd.rc <<= 1;
-		dd.q_cap = (h->max_len + 15) & ~15;
-		if (8 * dd.rc + 32 + dd.q_cap > 65536) dd.q_cap = 0;
-		dd.lds0 = (size_t)8 * dd.rc + 32 + dd.q_cap;
-		const long long room = (65536 - (long long)dd.lds0) / (long long)DDP_LDS_PER_REG;       // regions a workgroup's LDS holds next to the ring
-		dd.cap_m = (int)(cfg.dedup_stage < 0 ? 128 : cfg.dedup_stage); if (dd.cap_m > room) dd.cap_m = (int)(room > 0 ? room : 0);
-		dd.cap_b = (int)(cfg.dedup_big < 0 ? room : cfg.dedup_big); if (dd.cap_b > room) dd.cap_b = (int)(room > 0 ? room : 0);
-		const long long wpc_m = (160 * 1024) / (long long)(dd.lds0 + DDW_PAR_BYTES(dd.cap_m)), wpc_b = (160 * 1024) / (long long)(dd.lds0 + DDW_PAR_BYTES(dd.cap_b));
-		dd.blk_m = share(256 * (wpc_m > 12 ? 12 : wpc_m)); dd.blk_b = share(256 * (wpc_b > 12 ? 12 : wpc_b));
-		const long long dpw = dp_wave_count(h, n_threads), cap = dpw > 0 ? dpw : 1;       // (dp_h / dp_e hold one scratch region per wave)
-		if (dd.blk_m > cap) dd.blk_m = cap; if (dd.blk_b > cap) dd.blk_b = cap;
-		if (dd.blk_m > n) dd.blk_m = n; if (dd.blk_b > n) dd.blk_b = n;
-		if (h->d_heavy.ensure((size_t)n * 4 + 16) || h->d_dd_tmp.ensure(((size_t)dd.blk_m * dd.cap_m + (size_t)dd.blk_b * dd.cap_b) * sizeof(bwagpu_alnreg_t) + 16)) { h->err = "hipMalloc failed (de-duplication lists)"; return BWAGPU_ENOMEM; }
-	}
+	DedupPlan dd;
+	if (int rc = dedup_plan(h, opt, cfg, h->max_len, n, long_batch, share_pct, dp_wave_count(h, n_threads), dd)) return rc;
 	for (int attempt = 0; attempt < 12; ++attempt) {
 		h->phase = 20 + attempt * 100;
 		int rc = alloc_batch(h, n_threads, seed_tasks ? (int)(((size_t)task_lanes * TASK_STACK_CAP + (size_t)(h->max_len + PTAB_MAX)) / (size_t)(h->max_len + 1 + PTAB_MAX))   // (the tasks' small spill areas, in units of a full-size one)
@@ -1308,43 +1374,7 @@ extern "C" int bwagpu_batch_run(bwagpu_t *h, const bwagpu_opt_t *opt)
 			hipLaunchKernelGGL(k_extend, grid, block, 0, h->stream, h->ix, *opt, B);
 		HIPCHK(h, hipEventRecord(h->ev[5], h->stream));
 		if (dbg_sync) { hipError_t e_ = hipStreamSynchronize(h->stream); fprintf(stderr, "[bwagpu] attempt %d: %s done (%s)\n", attempt, "k_extend", hipGetErrorString(e_)); }
-		if (long_batch || cfg.dedup_wave) {     // long reads: few reads, long patch alignments -> one wavefront per read
-			// Ring of {H,E} columns for the patch alignments' band: 2 w + 132 columns, where w = max(min(.., 4 opt.w), |rlen - l_query| + 3) (bwa.c:180-187)
-			// and the length difference of two merged regions of a 10 kb read with 13 % indels runs to several hundred bases.  A band the ring
-			// cannot hold falls back to one lane with its columns in HBM -- 10^7 cells at one lane's pace: measured 0.6 s per call, 58 s of a
-			// 100-read batch's 59 (profiles/r03_longread_probe.md) -- so the ring is sized for 1/8 of the longest read and capped by what one
-			// wave's LDS share allows; wider rings mean fewer waves per workgroup (the dynamic LDS of a workgroup is 64 KiB).
-			int need = 8 * opt->w + 4 + 128; if (need < h->max_len / 4 + 132) need = h->max_len / 4 + 132;
-			int rc_ = 256; while (rc_ < need && rc_ < 4096) rc_ <<= 1;
-			if (cfg.dedup_ring > 0) rc_ = (int)cfg.dedup_ring;      // test hook: a power of two, 256..4096
-			if (rc_ < 256 || rc_ > 4096 || (rc_ & (rc_ - 1))) rc_ = 1024;
-			const bool dedup_blk = (cfg.dedup_blk >= 0 ? cfg.dedup_blk : 1) != 0;   // four columns per lane in the patch alignments (wave_global2_score_ring_blk: 381 -> 207 ms per 6000 x 10 kb reads, BENCH_r03 variants); needs the segment in LDS
-			int q_cap = dedup_blk ? (h->max_len + 15) & ~15 : 0;      // room for a patch alignment's query segment next to the ring
-			if (8 * rc_ + 32 + q_cap > 65536) q_cap = 0;
-			int wpb = rc_ <= 1024 ? 4 : (rc_ <= 2048 ? 2 : 1);
-			while (wpb > 1 && (8 * rc_ + 32 + q_cap) * wpb > 65536) wpb >>= 1;
-			i64 nblk = ((i64)n + wpb - 1) / wpb, cap = B.dp_waves / wpb > 0 ? B.dp_waves / wpb : 1;   // dp_h/dp_e hold one scratch region per wave
-			if (dedup_blk && q_cap) hipLaunchKernelGGL(k_dedup_wave<true>, dim3((unsigned)(nblk < cap ? nblk : cap)), dim3(64 * wpb), (size_t)(8 * rc_ + 32 + q_cap) * wpb, h->stream, h->ix, *opt, B, rc_, q_cap, 0, 0, (bwagpu_alnreg_t*)nullptr);
-			else hipLaunchKernelGGL(k_dedup_wave<false>, dim3((unsigned)(nblk < cap ? nblk : cap)), dim3(64 * wpb), (size_t)(8 * rc_ + 32 + q_cap) * wpb, h->stream, h->ix, *opt, B, rc_, q_cap, 0, 0, (bwagpu_alnreg_t*)nullptr);
-		} else {
-			// Lane per read for the reads with one or two regions (nine in ten of the headline's); the others are listed by k_dedup and done by two more
-			// launches, one wavefront per read with the decisions' operands in LDS (dedup_read_par, dev_dedupp.h): the reads of up to dedup_stage regions
-			// (16.6 KB of LDS per wave, nine to a CU), then the few with more (up to dedup_big regions in 64 KB; beyond that, in place in HBM).
-			B.dd_heavy_min = dd_heavy_min; B.dd_list = h->d_heavy.as<i32>(); B.dd_prio = cfg.dedup_prio != 0; B.dd_net = (int)(cfg.dedup_net < 0 ? DEDUP_NET_DEFAULT : cfg.dedup_net);
-			B.dd_stage_cap = dd.cap_m > 0 ? dd.cap_m : 0x3fffffff;      // (no LDS arrays: one list, every read in place)
-			hipLaunchKernelGGL(k_dedup, dim3((unsigned)share(grid.x)), block, 0, h->stream, h->ix, *opt, B);
-			if (B.dd_heavy_min > 0) {
-				bwagpu_alnreg_t *tmp = h->d_dd_tmp.as<bwagpu_alnreg_t>();
-				const size_t lds_m = dd.lds0 + DDW_PAR_BYTES(dd.cap_m), lds_b = dd.lds0 + DDW_PAR_BYTES(dd.cap_b);
-				if (dd.q_cap) hipLaunchKernelGGL((k_dedup_wave<true, true>), dim3((unsigned)dd.blk_m), dim3(64), lds_m, h->stream, h->ix, *opt, B, dd.rc, dd.q_cap, dd.cap_m, 0, tmp);
-				else hipLaunchKernelGGL((k_dedup_wave<false, true>), dim3((unsigned)dd.blk_m), dim3(64), lds_m, h->stream, h->ix, *opt, B, dd.rc, dd.q_cap, dd.cap_m, 0, tmp);
-				if (dd.cap_m > 0) {
-					tmp += (size_t)dd.blk_m * dd.cap_m;
-					if (dd.q_cap) hipLaunchKernelGGL((k_dedup_wave<true, true>), dim3((unsigned)dd.blk_b), dim3(64), lds_b, h->stream, h->ix, *opt, B, dd.rc, dd.q_cap, dd.cap_b, 1, tmp);
-					else hipLaunchKernelGGL((k_dedup_wave<false, true>), dim3((unsigned)dd.blk_b), dim3(64), lds_b, h->stream, h->ix, *opt, B, dd.rc, dd.q_cap, dd.cap_b, 1, tmp);
-				}
-			}
-		}
+		dedup_launch(h, opt, cfg, B, h->max_len, n, long_batch, share_pct, grid.x, dd);
 		HIPCHK(h, hipEventRecord(h->ev[6], h->stream));
 		if (dbg_sync) { hipError_t e_ = hipStreamSynchronize(h->stream); fprintf(stderr, "[bwagpu] attempt %d: %s done (%s)\n", attempt, "k_dedup", hipGetErrorString(e_)); }
 		HIPCHK(h, hipGetLastError());
@@ -1784,6 +1814,109 @@ extern "C" int bwagpu_cigars_flat(bwagpu_t *h, const bwagpu_opt_t *opt, int n_re
 	}
 	*n_cigs = F.tot; *n_ops = ext_n;
 	*cigs = res.release(); *ops = res_ops.release();
+	return BWAGPU_OK;
+}
+
+// ---- the de-duplication stage on lists of the caller (test hook) ------------------------------------------------------------------------------------------
+extern "C" void bwagpu_dedup_limits(int32_t out[8])
+{
+	const int32_t v[8] = { DEDUP_HEAVY_DEFAULT, DEDUP_STAGE_DEFAULT, DEDUP_NET_DEFAULT, DEDUP_KEYSORT_MIN, 64 /* regions dedup_read_par's scan takes at once: a wavefront */,
+						   64 /* reads k_dedup draws at once */, DEDUP_RING_MIN, (int32_t)DDP_LDS_PER_REG };
+	memcpy(out, v, sizeof v);
+}
+
+// bwagpu_batch_run's de-duplication stage -- dedup_plan and dedup_launch, as for a batch -- on the caller's reads and raw region lists, in buffers of its own: a
+// batch on the handle keeps its results (the stage's list and staging buffers are scratch there as well).
+extern "C" int bwagpu_dedup_flat(bwagpu_t *h, const bwagpu_opt_t *opt, int n_reads, const uint8_t *seqs, const int64_t *seq_off, const int32_t *counts, const bwagpu_alnreg_t *regs,
+								 int32_t *counts_out, bwagpu_alnreg_t **regs_out, int64_t *n_out, int32_t *form)
+{
+	if (!h || !opt || n_reads < 0 || !regs_out || !n_out || (n_reads > 0 && (!counts || !seq_off || !counts_out))) return BWAGPU_EINVAL;
+	if (opt->e_del <= 0 || opt->e_ins <= 0 || opt->w < 0) { h->err = "bwagpu_dedup_flat: e_del and e_ins must be positive, w not negative"; return BWAGPU_EINVAL; }
+	for (int i = 0; i < n_reads; ++i) if (counts[i] < 0) { h->err = "bwagpu_dedup_flat: a negative count"; return BWAGPU_EINVAL; }
+	FlatLists F; RegLists L;
+	if (!F.scan(h, (size_t)n_reads, counts, regs, nullptr)) { h->err = "bwagpu_dedup_flat: a count outside [0, 2^30), or counts without regions"; return BWAGPU_EINVAL; }
+	if (F.tot > 0x7fffffff) { h->err = "bwagpu_dedup_flat: more than 2^31 - 1 regions"; return BWAGPU_EINVAL; }
+	int max_len = 0;
+	for (int i = 0; i < n_reads; ++i) {
+		if (seq_off[0] != 0 || seq_off[i + 1] < seq_off[i] || seq_off[i + 1] - seq_off[i] > 0x3fffffff) { h->err = "bwagpu_dedup_flat: offsets that do not ascend"; return BWAGPU_EINVAL; }
+		max_len = std::max(max_len, (int)(seq_off[i + 1] - seq_off[i]));
+	}
+	const i64 n_bases = n_reads ? seq_off[n_reads] : 0;
+	if (n_bases > 0 && !seqs) return BWAGPU_EINVAL;
+	for (i64 k = 0; k < n_bases; ++k) if (seqs[k] > 4) { h->err = "bwagpu_dedup_flat: a base code above 4"; return BWAGPU_EINVAL; }
+	for (int i = 0; i < n_reads; ++i) {
+		const i64 len = seq_off[i + 1] - seq_off[i];
+		for (i64 k = F.off[(size_t)i]; k < F.off[(size_t)i + 1]; ++k) {
+			const bwagpu_alnreg_t &a = regs[k];
+			if (a.qb < 0 || a.qe < a.qb || a.qe > len) { h->err = "bwagpu_dedup_flat: region " + std::to_string(k) + ": qb < 0, qe < qb or qe beyond the read"; return BWAGPU_EINVAL; }
+			if (a.rb < 0 || a.re <= a.rb || a.re > 2 * h->l_pac) { h->err = "bwagpu_dedup_flat: region " + std::to_string(k) + ": rb < 0, re <= rb or re beyond 2 l_pac"; return BWAGPU_EINVAL; }
+			if (a.rb < h->l_pac && a.re > h->l_pac) { h->err = "bwagpu_dedup_flat: region " + std::to_string(k) + ": bridges l_pac"; return BWAGPU_EINVAL; }
+			if (a.rid >= h->n_seqs) { h->err = "bwagpu_dedup_flat: region " + std::to_string(k) + ": rid beyond the index's contigs"; return BWAGPU_EINVAL; }      // (the stage looks its alt flag up)
+		}
+	}
+	const BusyGuard busy(h->ibuf->busy);
+	HIPCHK(h, hipSetDevice(h->device));
+	*regs_out = nullptr; *n_out = 0;
+	if (n_reads == 0) {
+		ResultBlock<bwagpu_alnreg_t> none = result_block<bwagpu_alnreg_t>(0);
+		if (!none) return BWAGPU_ENOMEM;
+		*regs_out = none.release();
+		return BWAGPU_OK;
+	}
+	const int n = n_reads;
+	const BwagpuConfig &cfg = h->cfg;
+	const bool long_batch = max_len > WAVE_EXT_MAX_LEN;      // (as bwagpu_batch_run)
+	const long long share_pct = cfg.share >= 0 ? cfg.share : (h->ibuf->refs.load() >= 3 && busy.others > 0 ? 50 : 100);
+	// lanes of the lane-per-read kernel and the waves that own a DP scratch region (resident_threads / dp_wave_count, for these reads)
+	i64 lanes = ((i64)n + BLOCK - 1) / BLOCK * BLOCK; if (lanes > 256 * BLOCK) lanes = 256 * BLOCK;
+	int dp_waves = (int)(lanes / 64);
+	if (long_batch) { const int want = n < 1024 ? n : 1024; if (want > dp_waves) dp_waves = want; }
+	DedupPlan dd;
+	if (int rc = dedup_plan(h, opt, cfg, max_len, n, long_batch, share_pct, dp_waves, dd)) return rc;
+	DevBuf *D = h->d_df;
+	const size_t dp_bytes = (size_t)dp_waves * ((size_t)max_len + 2) * DPS * 4;
+	if (D[bwagpu_s::DF_SEQ].ensure((size_t)n_bases + 16) || D[bwagpu_s::DF_SEQOFF].ensure(((size_t)n + 1) * 8) || D[bwagpu_s::DF_REGS].ensure((size_t)(F.tot ? F.tot : 1) * sizeof(bwagpu_alnreg_t)) ||
+		D[bwagpu_s::DF_REGOFF].ensure(((size_t)n + 1) * 8) || D[bwagpu_s::DF_NRAW].ensure((size_t)n * 4 + 16) || D[bwagpu_s::DF_CNT].ensure((size_t)n * 4 + 16) || D[bwagpu_s::DF_FORM].ensure((size_t)n * 4 + 16) ||
+		D[bwagpu_s::DF_BLOB].ensure(((size_t)F.tot + 8) * SLOT_BLOB_BYTES) || D[bwagpu_s::DF_DPH].ensure(dp_bytes) || D[bwagpu_s::DF_DPE].ensure(dp_bytes) || D[bwagpu_s::DF_CTR].ensure(sizeof(Counters))) {
+		h->err = "hipMalloc failed (dedup_flat)"; return BWAGPU_ENOMEM;
+	}
+	if (n_bases) HIPCHK(h, hipMemcpyAsync(D[bwagpu_s::DF_SEQ].p, seqs, (size_t)n_bases, hipMemcpyHostToDevice, h->stream));
+	HIPCHK(h, hipMemcpyAsync(D[bwagpu_s::DF_SEQOFF].p, seq_off, ((size_t)n + 1) * 8, hipMemcpyHostToDevice, h->stream));
+	if (F.tot) HIPCHK(h, hipMemcpyAsync(D[bwagpu_s::DF_REGS].p, regs, (size_t)F.tot * sizeof(bwagpu_alnreg_t), hipMemcpyHostToDevice, h->stream));
+	HIPCHK(h, hipMemcpyAsync(D[bwagpu_s::DF_REGOFF].p, F.off.data(), ((size_t)n + 1) * 8, hipMemcpyHostToDevice, h->stream));
+	HIPCHK(h, hipMemcpyAsync(D[bwagpu_s::DF_NRAW].p, counts, (size_t)n * 4, hipMemcpyHostToDevice, h->stream));
+	HIPCHK(h, hipMemsetAsync(D[bwagpu_s::DF_CNT].p, 0, (size_t)n * 4, h->stream));
+	HIPCHK(h, hipMemsetAsync(D[bwagpu_s::DF_FORM].p, 0xff, (size_t)n * 4, h->stream));
+	HIPCHK(h, hipMemsetAsync(D[bwagpu_s::DF_CTR].p, 0, sizeof(Counters), h->stream));
+	HIPCHK(h, wait_stream(h));      // (the caller's arrays are pageable)
+	Batch B; memset(&B, 0, sizeof B);
+	B.n_reads = n; B.max_len = max_len; B.stats = h->stats_on;
+	B.seq = D[bwagpu_s::DF_SEQ].as<u8>(); B.off = D[bwagpu_s::DF_SEQOFF].as<i64>(); B.ctr = D[bwagpu_s::DF_CTR].as<Counters>();
+	B.regs = D[bwagpu_s::DF_REGS].as<bwagpu_alnreg_t>(); B.reg_cap = F.tot; B.reg_off = D[bwagpu_s::DF_REGOFF].as<i64>();
+	B.reg_n_raw = D[bwagpu_s::DF_NRAW].as<i32>(); B.reg_n = D[bwagpu_s::DF_CNT].as<i32>(); B.regs_raw = nullptr;
+	// the sorts' key scratch (dev_sort_regs_by_key): read i's block of the blob begins at slot reg_off[i] and has counts[i] slots, one 64-byte chain record -- room for a RegKey -- each
+	B.slot_blob = D[bwagpu_s::DF_BLOB].as<u8>(); B.seed_off = B.reg_off; B.seed_n = B.reg_n_raw; B.slot_cap = F.tot;
+	B.dp_h = D[bwagpu_s::DF_DPH].as<i32>(); B.dp_e = D[bwagpu_s::DF_DPE].as<i32>(); B.dp_waves = dp_waves;
+	B.dd_form = D[bwagpu_s::DF_FORM].as<i32>();
+	dedup_launch(h, opt, cfg, B, max_len, n, long_batch, share_pct, (unsigned)(lanes / BLOCK), dd);
+	HIPCHK(h, hipGetLastError());
+	std::vector<bwagpu_alnreg_t> all((size_t)(F.tot ? F.tot : 1));
+	std::vector<i32> forms((size_t)n);
+	if (F.tot) HIPCHK(h, hipMemcpyAsync(all.data(), D[bwagpu_s::DF_REGS].p, (size_t)F.tot * sizeof(bwagpu_alnreg_t), hipMemcpyDeviceToHost, h->stream));
+	HIPCHK(h, hipMemcpyAsync(counts_out, D[bwagpu_s::DF_CNT].p, (size_t)n * 4, hipMemcpyDeviceToHost, h->stream));
+	HIPCHK(h, hipMemcpyAsync(forms.data(), D[bwagpu_s::DF_FORM].p, (size_t)n * 4, hipMemcpyDeviceToHost, h->stream));
+	HIPCHK(h, wait_stream(h));
+	i64 tot_out = 0;
+	for (int i = 0; i < n; ++i) {
+		if (counts_out[i] < 0 || counts_out[i] > counts[i] || forms[(size_t)i] < 0) { h->err = "bwagpu_dedup_flat: read " + std::to_string(i) + " was not finished"; return BWAGPU_EHIP; }
+		tot_out += counts_out[i];
+	}
+	ResultBlock<bwagpu_alnreg_t> res = result_block<bwagpu_alnreg_t>((size_t)tot_out);
+	if (!res) return BWAGPU_ENOMEM;
+	i64 k = 0;
+	for (int i = 0; i < n; ++i) for (int j = 0; j < counts_out[i]; ++j) res[(size_t)k++] = all[(size_t)(F.off[(size_t)i] + j)];
+	if (form) memcpy(form, forms.data(), (size_t)n * 4);
+	*n_out = tot_out; *regs_out = res.release();
 	return BWAGPU_OK;
 }
 

@@ -199,6 +199,7 @@ struct Batch {
 	int dd_heavy_min, dd_stage_cap; // dd_heavy_min 0 = k_dedup does every read itself
 	int dd_net;                     // reads of at least this many regions finish their sorts by a sorting network instead of by counting (option dedup_net; 0: never)
 	int dd_prio;                    // the list launches' waves run at raised issue priority (option dedup_prio)
+	i32 *dd_form;                   // bwagpu_dedup_flat: per read, the routine that finished it (0 dedup_read, 1 dedup_read_wave, 2 dedup_read_par); null for a batch
 	int seed_budget;                // ... that budget (0: none)
 	i64 *p2_tasks; long long p2_cap; // pass-2 searches of the heavy reads as tasks (k_seed<LR = 3>): read << 32 | index of the pass-1 entry to re-seed
 	const i32 *vr_first;            // per read: its first task (n_reads + 1 entries)

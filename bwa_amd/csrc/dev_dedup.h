@@ -172,6 +172,7 @@ __device__ void dedup_read(const DevIndex &ix, const bwagpu_opt_t &opt, const Ba
 	for (int i = 0; i < n; ++i)   // bwamem.c:1111-1115
 		if (a[i].rid >= 0 && ix.ctg_alt[a[i].rid]) a[i].is_alt = 1;
 	B.reg_n[r] = n;
+	if (B.dd_form) B.dd_form[r] = 0;
 }
 
 __global__ void __launch_bounds__(256) k_dedup(DevIndex ix, bwagpu_opt_t opt, Batch B)

@@ -135,6 +135,7 @@ template <bool BLK> __device__ bool dedup_read_par(const DevIndex &ix, const bwa
 		if (lane == 0) {
 			if (n == 1 && ga[0].rid >= 0 && ix.ctg_alt[ga[0].rid]) ga[0].is_alt = 1;
 			B.reg_n[r] = n;
+			if (B.dd_form) B.dd_form[r] = 2;
 		}
 		wave_sync();
 		return true;
@@ -261,7 +262,7 @@ template <bool BLK> __device__ bool dedup_read_par(const DevIndex &ix, const bwa
 		u32 *ow = (u32*)ga;
 		for (int x = lane; x < nf * DDP_REG_WORDS; x += 64) ow[x] = tw[x];
 	}
-	if (lane == 0) B.reg_n[r] = nf;
+	if (lane == 0) { B.reg_n[r] = nf; if (B.dd_form) B.dd_form[r] = 2; }
 	wave_sync();
 	return true;
 }

@@ -290,6 +290,7 @@ template <bool BLK = false> __device__ void dedup_read_wave(const DevIndex &ix, 
 		for (int i = 0; i < n; ++i)   // bwamem.c:1111-1115
 			if (a[i].rid >= 0 && ix.ctg_alt[a[i].rid]) a[i].is_alt = 1;
 		B.reg_n[r] = n;
+		if (B.dd_form) B.dd_form[r] = 1;
 	}
 	wave_sync();
 }

@@ -284,6 +284,20 @@ int bwagpu_cigars_flat(bwagpu_t *h, const bwagpu_opt_t *opt, int n_reads, const 
  * segment, direction nibbles of the first and second tier, widest band, operations kept in a record, operations and MD characters a wavefront stages);
  * CIGL_MAX_COLS, CIGL_MAX_OPS, CIGL_QCAP (the long tier: widest band, most operations, query bases staged in LDS). */
 void bwagpu_cigar_limits(int32_t out[10]);
+/* Test hook: the de-duplication stage of bwagpu_batch_run (mem_sort_dedup_patch, bwamem.c:463-515) on reads (nt4 codes 0..4, n_reads + 1 offsets starting at
+ * 0) and raw region lists of the caller (read i: counts[i] records of regs).  counts_out[i]: the regions read i is left with; *regs_out: those regions, read by
+ * read in the stage's output order, *n_out of them (free with bwagpu_free); form[i] (may be NULL): the routine that finished read i -- 0 one lane (dedup_read),
+ * 1 one wavefront on the records in place (dedup_read_wave), 2 one wavefront with the regions spread over its lanes (dedup_read_par).  The routine is chosen as
+ * for a batch of these reads, from the handle's options (dedup_heavy, dedup_stage, dedup_big, dedup_net, dedup_wave, dedup_blk, dedup_ring).  Needs no batch
+ * and leaves a batch's results on the same handle alone.  BWAGPU_EINVAL (with bwagpu_last_error text): negative counts, offsets that do not ascend, base codes
+ * above 4, a region without 0 <= qb <= qe <= the read's length or 0 <= rb < re <= 2 l_pac, one that bridges l_pac, a rid beyond the index's contigs (negative
+ * ones pass), e_del <= 0, e_ins <= 0 or w < 0. */
+int bwagpu_dedup_flat(bwagpu_t *h, const bwagpu_opt_t *opt, int n_reads, const uint8_t *seqs, const int64_t *seq_off, const int32_t *counts, const bwagpu_alnreg_t *regs,
+					  int32_t *counts_out, bwagpu_alnreg_t **regs_out, int64_t *n_out, int32_t *form);
+/* The stage's switch points, as compiled: the defaults of options dedup_heavy, dedup_stage and dedup_net, DEDUP_KEYSORT_MIN (regions from which the in-place
+ * sorts move keys), the regions dedup_read_par's scan takes at once, the reads k_dedup draws at once, the smallest ring of the patch alignments,
+ * DDP_LDS_PER_REG (LDS bytes per region of dedup_read_par). */
+void bwagpu_dedup_limits(int32_t out[8]);
 
 /* After bwagpu_batch_download of a paired batch (mates interleaved 2i, 2i+1): the local alignments mem_matesw
  * (bwamem_pair.c:137-206) would run for every (anchor region, orientation) that the downloaded region lists do not already
