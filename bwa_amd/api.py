@@ -706,6 +706,12 @@ class FastqOut(C.Structure):
                 ("comments", C.c_void_p), ("comment_off", C.c_void_p), ("has_comment", C.c_void_p), ("recs", C.c_void_p), ("kernel_ms", C.c_float * 3)]
 
 
+class FastqSmart(C.Structure):
+    """bwagpu_fastq_smart_t"""
+    _fields_ = [("status", C.c_int32), ("n_reads", C.c_int32), ("consumed", C.c_int64), ("declined_at", C.c_int64), ("cls", C.c_void_p),
+                ("n_sub", C.c_int32 * 2), ("idx", C.c_void_p * 2), ("sub", FastqOut * 2), ("kernel_ms", C.c_float * 4)]
+
+
 class BgzfWin(C.Structure):
     """bwagpu_bgzf_win_t"""
     _fields_ = [("comp", C.c_void_p), ("comp_len", C.c_int64), ("skip", C.c_int32), ("eof", C.c_int32)]
@@ -732,6 +738,10 @@ class FastqParser:
         L.bwagpu_fastq_batch.argtypes = [P, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p]
         L.bwagpu_bgzf_inflate.argtypes = [P, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]
         L.bwagpu_fastq_batch_bgzf.argtypes = [P, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.bwagpu_fastq_batch_smart.argtypes = [P, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p]
+        L.bwagpu_fastq_batch_smart_bgzf.argtypes = [P, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.bwagpu_fastq_smart_free.argtypes = [C.c_void_p]
+        L.bwagpu_fastq_smart_free.restype = None
         L.bwagpu_fastq_out_free.argtypes = [C.c_void_p]
         L.bwagpu_fastq_out_free.restype = None
         L.bwagpu_fastq_end.argtypes = [P]
@@ -769,29 +779,81 @@ class FastqParser:
         self._chk(rc, "bwagpu_fastq_batch")
         return self._result(o)
 
+    @staticmethod
+    def _take(ptr, count, dtype):
+        if count == 0:
+            return np.zeros(0, dtype=dtype)
+        return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_uint8)), shape=(count * np.dtype(dtype).itemsize,)).view(dtype).copy()
+
+    def _arrays(self, o, r):
+        """copies of a FastqOut's arrays into r"""
+        n, take = int(o.n_reads), self._take
+        for k in ("off", "name_off", "comment_off"):
+            r[k] = take(getattr(o, k), n + 1, np.int64)
+        r["seqs"] = take(o.seqs, int(r["off"][n]), np.uint8)
+        r["quals"] = take(o.quals, int(r["off"][n]), np.uint8).tobytes()
+        r["names"] = take(o.names, int(r["name_off"][n]), np.uint8).tobytes()
+        r["comments"] = take(o.comments, int(r["comment_off"][n]), np.uint8).tobytes()
+        r["has_comment"] = take(o.has_comment, n, np.uint8)
+        r["recs"] = take(o.recs, n, FASTQ_REC_DTYPE)
+
     def _result(self, o) -> dict:
         """a filled FastqOut as a dict of copies; the library's arrays are released"""
         r = {"status": int(o.status), "n_reads": int(o.n_reads), "consumed": (int(o.consumed[0]), int(o.consumed[1])),
              "declined_file": int(o.declined_file), "declined_at": int(o.declined_at), "kernel_ms": tuple(float(x) for x in o.kernel_ms)}
         try:
             if o.status in (FQ_CUT, FQ_END):
-                n = int(o.n_reads)
-
-                def take(ptr, count, dtype):
-                    if count == 0:
-                        return np.zeros(0, dtype=dtype)
-                    return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_uint8)), shape=(count * np.dtype(dtype).itemsize,)).view(dtype).copy()
-
-                for k in ("off", "name_off", "comment_off"):
-                    r[k] = take(getattr(o, k), n + 1, np.int64)
-                r["seqs"] = take(o.seqs, int(r["off"][n]), np.uint8)
-                r["quals"] = take(o.quals, int(r["off"][n]), np.uint8).tobytes()
-                r["names"] = take(o.names, int(r["name_off"][n]), np.uint8).tobytes()
-                r["comments"] = take(o.comments, int(r["comment_off"][n]), np.uint8).tobytes()
-                r["has_comment"] = take(o.has_comment, n, np.uint8)
-                r["recs"] = take(o.recs, n, FASTQ_REC_DTYPE)
+                self._arrays(o, r)
         finally:
             self.L.bwagpu_fastq_out_free(C.byref(o))
+        return r
+
+    def _result_smart(self, o) -> dict:
+        """a filled FastqSmart as a dict of copies; the library's arrays are released"""
+        r = {"status": int(o.status), "n_reads": int(o.n_reads), "consumed": int(o.consumed), "declined_at": int(o.declined_at),
+             "kernel_ms": tuple(float(x) for x in o.kernel_ms)}
+        try:
+            if o.status in (FQ_CUT, FQ_END):
+                r["cls"] = self._take(o.cls, int(o.n_reads), np.uint8)
+                r["n_sub"] = (int(o.n_sub[0]), int(o.n_sub[1]))
+                r["idx"] = [self._take(o.idx[k], int(o.n_sub[k]), np.int32) for k in range(2)]
+                r["sub"] = []
+                for k in range(2):
+                    d = {"n_reads": int(o.sub[k].n_reads)}
+                    self._arrays(o.sub[k], d)
+                    r["sub"].append(d)
+        finally:
+            self.L.bwagpu_fastq_smart_free(C.byref(o))
+        return r
+
+    def batch_smart_rc(self, raw, length, eof, chunk_size, out):
+        """the bare call (tests of the error paths): returns the library's code"""
+        return self.L.bwagpu_fastq_batch_smart(self.h, raw, length, eof, chunk_size, out)
+
+    def batch_smart(self, raw, chunk_size: int = 10_000_000, eof: bool = True) -> dict:
+        """raw: a bytes-like window of ONE file of interleaved reads (`mem -p`), starting at a record start.  Returns a dict with the whole
+        batch's status (FQ_*), n_reads, consumed, declined_at, kernel_ms and -- for FQ_CUT / FQ_END -- cls (0 single, 1 first of a pair,
+        2 second), n_sub, idx (per sub-batch: the reads' places in the batch) and sub: two dicts (single reads, pairs) with n_reads and
+        batch()'s arrays."""
+        b = np.frombuffer(raw, dtype=np.uint8) if len(raw) else np.zeros(1, dtype=np.uint8)
+        o = FastqSmart()
+        self._chk(self.L.bwagpu_fastq_batch_smart(self.h, b.ctypes.data, len(raw), int(bool(eof)), int(chunk_size), C.byref(o)), "bwagpu_fastq_batch_smart")
+        return self._result_smart(o)
+
+    def batch_smart_bgzf_rc(self, w, chunk_size, out, info):
+        """the bare call (tests of the error paths): returns the library's code"""
+        return self.L.bwagpu_fastq_batch_smart_bgzf(self.h, w, chunk_size, out, info)
+
+    def batch_smart_bgzf(self, comp, skip: int = 0, chunk_size: int = 10_000_000, eof: bool = True) -> dict:
+        """comp: a bytes-like window of BGZF data that starts at a block start; skip: bytes of its first block's text that earlier batches
+        consumed.  Returns batch_smart()'s dict plus "bgzf": the window's info dict (bwagpu_bgzf_info_t's fields)."""
+        b = np.frombuffer(comp, dtype=np.uint8) if len(comp) else np.zeros(1, dtype=np.uint8)
+        w = BgzfWin(b.ctypes.data, len(comp), int(skip), int(bool(eof)))
+        o = FastqSmart()
+        info = BgzfInfo()
+        self._chk(self.L.bwagpu_fastq_batch_smart_bgzf(self.h, C.byref(w), int(chunk_size), C.byref(o), C.byref(info)), "bwagpu_fastq_batch_smart_bgzf")
+        r = self._result_smart(o)
+        r["bgzf"] = info.as_dict()
         return r
 
     def inflate_bgzf(self, data, eof: bool = True):

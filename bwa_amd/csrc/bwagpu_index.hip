@@ -41,6 +41,7 @@ typedef unsigned char u8;
 
 #include "dev_fasta.h"            // FASTA -> .pac / holes (bwagpu_fasta_*)
 #include "dev_fastq.h"            // FASTQ windows -> batches (bwagpu_fastq_*)
+#include "dev_fastq_smart.h"      // ... classified and split for `mem -p` (bwagpu_fastq_batch_smart*)
 #include "dev_bgzf.h"             // BGZF blocks -> text (bwagpu_bgzf_inflate, bwagpu_fastq_batch_bgzf)
 
 namespace {
@@ -849,10 +850,11 @@ done:
 struct bwagpu_fastq_parser_s {
 	int device = 0;
 	hipStream_t st = nullptr;
-	hipEvent_t ev[6] = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };      // (4, 5: around the BGZF inflate)
+	hipEvent_t ev[7] = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };      // (4, 5: around the BGZF inflate; 6: behind the classification)
 	Buf d_comp[2], d_blk[2], d_bzstat;      // BGZF: compressed windows, block tables, status words + the bad words of both windows
 	Buf d_buf[2], d_nl[2], d_recs[2], d_tcount, d_tbase, d_units, d_uscan, d_words, d_tmp;
 	Buf o_seqs, o_off, o_names, o_name_off, o_quals, o_com, o_com_off, o_has, o_recs;
+	Buf d_eqv, d_runs, d_cls, d_sums, d_sscan, o_idx;      // bwagpu_fastq_batch_smart: dev_fastq_smart.h's arrays
 	std::string err;
 
 	~bwagpu_fastq_parser_s()
@@ -956,8 +958,8 @@ static int fq_setup(bwagpu_fastq_parser_t *p, FqArgs &A, int nw, const u64 len[2
 	return p->ensure_shared(tiles, cap_units);
 }
 
-// everything behind the copy-up: the text windows are in place on the device (in stream order)
-static int fq_run(bwagpu_fastq_parser_t *p, const FqArgs &A, u32 tiles, u64 cap_units, int chunk_size, bwagpu_fastq_out_t *out)
+// passes 1 to 3 behind the copy-up: the text windows are in place on the device (in stream order).  Events 0, 1, 2 are recorded
+static int fq_launch(bwagpu_fastq_parser_t *p, const FqArgs &A, u32 tiles, u64 cap_units, int chunk_size)
 {
 	u64 *words = p->d_words.as<u64>();
 	FqInfo *d_info = (FqInfo*)(words + FQ_N_WORDS);
@@ -976,6 +978,15 @@ static int fq_run(bwagpu_fastq_parser_t *p, const FqArgs &A, u32 tiles, u64 cap_
 	hipLaunchKernelGGL(k_fq_cut, dim3(ugrid), dim3(FQ_BLOCK), 0, p->st, A, words, uscan, (u64)chunk_size);
 	hipLaunchKernelGGL(k_fq_decide, dim3(1), dim3(FQ_WAVE), 0, p->st, A, words, uscan, d_info);
 	(void)hipEventRecord(p->ev[2], p->st);
+	return 0;
+}
+
+// everything behind the copy-up
+static int fq_run(bwagpu_fastq_parser_t *p, const FqArgs &A, u32 tiles, u64 cap_units, int chunk_size, bwagpu_fastq_out_t *out)
+{
+	if (int rc = fq_launch(p, A, tiles, cap_units, chunk_size)) return rc;
+	FqInfo *d_info = (FqInfo*)(p->d_words.as<u64>() + FQ_N_WORDS);
+	const FqSum *uscan = p->d_uscan.as<FqSum>();
 	FqInfo info;
 	// wait 1: status, batch size, total sizes
 	if (p->hip("read back the batch's sizes", hipMemcpyAsync(&info, d_info, sizeof info, hipMemcpyDeviceToHost, p->st)) || p->hip("sync", hipStreamSynchronize(p->st))) return BWAGPU_EHIP;
@@ -1151,18 +1162,11 @@ extern "C" int bwagpu_bgzf_inflate(bwagpu_fastq_parser_t *p, const void *comp, i
 	return 0;
 }
 
-extern "C" int bwagpu_fastq_batch_bgzf(bwagpu_fastq_parser_t *p, const bwagpu_bgzf_win_t *w1, const bwagpu_bgzf_win_t *w2, int chunk_size,
-									   bwagpu_fastq_out_t *out, bwagpu_bgzf_info_t info[2])
+// bwagpu_fastq_batch_bgzf's work around the parse: the walk, the inflate into the window buffers and its verdict, then run(A, tiles,
+// cap_units) -- the parse, which leaves *status and consumed[] --, then the virtual offsets.  info: two entries
+template <class Run>
+static int bz_batch(bwagpu_fastq_parser_t *p, const bwagpu_bgzf_win_t *const w[2], int nw, bwagpu_bgzf_info_t info[2], int32_t *status, const int64_t *consumed, Run run)
 {
-	if (!p) return BWAGPU_EINVAL;
-	const bwagpu_bgzf_win_t *w[2] = { w1, w2 };
-	const int nw = w2 ? 2 : 1;
-	bool ok = w1 && out && info && chunk_size > 0;
-	for (int k = 0; ok && k < nw; ++k) ok = w[k]->comp && w[k]->comp_len >= 0 && w[k]->skip >= 0;
-	if (!ok) return p->fail(BWAGPU_EINVAL, "bwagpu_fastq_batch_bgzf: NULL argument, negative length or skip, or chunk_size <= 0");
-	memset(out, 0, sizeof *out);
-	out->declined_file = -1; out->declined_at = -1;
-	p->err.clear();
 	BzPlan P[2];
 	memset(info, 0, 2 * sizeof info[0]);
 	info[1].damaged_at = -1;
@@ -1171,7 +1175,7 @@ extern "C" int bwagpu_fastq_batch_bgzf(bwagpu_fastq_parser_t *p, const bwagpu_bg
 		bz_info(P[k], &info[k]);
 	}
 	for (int k = 0; k < nw; ++k) {
-		if (P[k].blk.empty() && w[k]->skip > 0 && !w[k]->eof && P[k].host_bad < 0) { out->status = BWAGPU_FQ_MORE; return 0; }      // (the first block is not in view yet)
+		if (P[k].blk.empty() && w[k]->skip > 0 && !w[k]->eof && P[k].host_bad < 0) { *status = BWAGPU_FQ_MORE; return 0; }      // (the first block is not in view yet)
 		if ((u32)w[k]->skip > (P[k].blk.empty() ? 0u : P[k].blk[0].isize)) return p->fail(BWAGPU_EINVAL, "bwagpu_fastq_batch_bgzf: skip is larger than the first block's ISIZE");
 	}
 	if (hipSetDevice(p->device) != hipSuccess) return p->fail(BWAGPU_ENODEV, "hipSetDevice failed");
@@ -1201,11 +1205,11 @@ extern "C" int bwagpu_fastq_batch_bgzf(bwagpu_fastq_parser_t *p, const bwagpu_bg
 	{ float ms = 0; if (hipEventElapsedTime(&ms, p->ev[4], p->ev[5]) == hipSuccess) info[0].inflate_ms = info[1].inflate_ms = ms; }
 	bool damaged = false;
 	for (int k = 0; k < nw; ++k) { info[k].damaged_at = bz_damage(p, P[k], bad[k]); damaged = damaged || info[k].damaged_at >= 0; info[k].next_coff = 0; info[k].next_uoff = w[k]->skip; }
-	if (damaged) { out->status = BWAGPU_FQ_DAMAGED; return 0; }
-	if (int rc = fq_run(p, A, tiles, cap_units, chunk_size, out)) return rc;
-	if (out->status == BWAGPU_FQ_CUT || out->status == BWAGPU_FQ_END)
+	if (damaged) { *status = BWAGPU_FQ_DAMAGED; return 0; }
+	if (int rc = run(A, tiles, cap_units)) return rc;
+	if (*status == BWAGPU_FQ_CUT || *status == BWAGPU_FQ_END)
 		for (int k = 0; k < nw; ++k) {
-			const u64 t = (u64)w[k]->skip + (u64)out->consumed[k];
+			const u64 t = (u64)w[k]->skip + (u64)consumed[k];
 			info[k].next_coff = P[k].used; info[k].next_uoff = 0;
 			// the first block whose text reaches beyond t (empty blocks at t are stepped over)
 			size_t lo = 0, hi = P[k].blk.size();
@@ -1213,4 +1217,152 @@ extern "C" int bwagpu_fastq_batch_bgzf(bwagpu_fastq_parser_t *p, const bwagpu_bg
 			if (lo < P[k].blk.size()) { info[k].next_coff = P[k].coff[lo]; info[k].next_uoff = (int32_t)(t - P[k].blk[lo].out); }
 		}
 	return 0;
+}
+
+extern "C" int bwagpu_fastq_batch_bgzf(bwagpu_fastq_parser_t *p, const bwagpu_bgzf_win_t *w1, const bwagpu_bgzf_win_t *w2, int chunk_size,
+									   bwagpu_fastq_out_t *out, bwagpu_bgzf_info_t info[2])
+{
+	if (!p) return BWAGPU_EINVAL;
+	const bwagpu_bgzf_win_t *w[2] = { w1, w2 };
+	const int nw = w2 ? 2 : 1;
+	bool ok = w1 && out && info && chunk_size > 0;
+	for (int k = 0; ok && k < nw; ++k) ok = w[k]->comp && w[k]->comp_len >= 0 && w[k]->skip >= 0;
+	if (!ok) return p->fail(BWAGPU_EINVAL, "bwagpu_fastq_batch_bgzf: NULL argument, negative length or skip, or chunk_size <= 0");
+	memset(out, 0, sizeof *out);
+	out->declined_file = -1; out->declined_at = -1;
+	p->err.clear();
+	return bz_batch(p, w, nw, info, &out->status, out->consumed, [&](const FqArgs &A, u32 tiles, u64 cap_units) { return fq_run(p, A, tiles, cap_units, chunk_size, out); });
+}
+
+// ---- one window of interleaved reads -> single reads and pairs (dev_fastq_smart.h) ------------------------------------------------
+extern "C" void bwagpu_fastq_smart_free(bwagpu_fastq_smart_t *o)
+{
+	if (!o) return;
+	bwagpu_free(o->cls); o->cls = nullptr;
+	for (int k = 0; k < 2; ++k) { bwagpu_free(o->idx[k]); o->idx[k] = nullptr; bwagpu_fastq_out_free(&o->sub[k]); }
+}
+
+static void fqs_init(bwagpu_fastq_smart_t *out)
+{
+	memset(out, 0, sizeof *out);
+	out->declined_at = -1;
+	for (int k = 0; k < 2; ++k) { out->sub[k].declined_file = -1; out->sub[k].declined_at = -1; }
+}
+
+// fq_run for one window, with passes 5 to 7 in the place of pass 4
+static int fqs_run(bwagpu_fastq_parser_t *p, const FqArgs &A, u32 tiles, u64 cap_units, int chunk_size, bwagpu_fastq_smart_t *out)
+{
+	if (p->d_eqv.ensure(cap_units * 4) || p->d_runs.ensure(cap_units * 4) || p->d_cls.ensure(cap_units) || p->d_sums.ensure(cap_units * sizeof(FqsSum)) ||
+		p->d_sscan.ensure(cap_units * sizeof(FqsSum))) return p->fail(BWAGPU_ENOMEM, "hipMalloc failed (FASTQ classification)");
+	if (int rc = fq_launch(p, A, tiles, cap_units, chunk_size)) return rc;
+	FqInfo *d_info = (FqInfo*)(p->d_words.as<u64>() + FQ_N_WORDS);
+	u32 *eqv = p->d_eqv.as<u32>(), *runs = p->d_runs.as<u32>();
+	FqsSum *sums = p->d_sums.as<FqsSum>(), *sscan = p->d_sscan.as<FqsSum>();
+	const unsigned ugrid = grid_for(cap_units) < 1024 ? grid_for(cap_units) : 1024;
+	hipLaunchKernelGGL(k_fqs_eq, dim3(ugrid), dim3(FQ_BLOCK), 0, p->st, A, (const FqInfo*)d_info, eqv);
+	if (int rc = p->scan_incl(eqv, runs, cap_units, rocprim::maximum<u32>())) return rc;
+	hipLaunchKernelGGL(k_fqs_class, dim3(ugrid), dim3(FQ_BLOCK), 0, p->st, A, (const FqInfo*)d_info, (const u32*)runs, p->d_cls.as<u8>(), sums);
+	if (int rc = p->scan_incl(sums, sscan, cap_units, FqsPlus())) return rc;
+	(void)hipEventRecord(p->ev[6], p->st);
+	FqInfo info; FqsSum tot;
+	// wait 1: status, batch size, total sizes -- and the sub-batches' (entries past the batch add nothing: the scan's last element)
+	if (p->hip("read back the batch's sizes", hipMemcpyAsync(&info, d_info, sizeof info, hipMemcpyDeviceToHost, p->st)) ||
+		p->hip("read back the sub-batches' sizes", hipMemcpyAsync(&tot, sscan + (cap_units - 1), sizeof tot, hipMemcpyDeviceToHost, p->st)) || p->hip("sync", hipStreamSynchronize(p->st))) return BWAGPU_EHIP;
+	if (p->hip("FASTQ kernels", hipGetLastError())) return BWAGPU_EHIP;
+	{
+		float ms = 0;
+		if (hipEventElapsedTime(&ms, p->ev[0], p->ev[1]) == hipSuccess) out->kernel_ms[0] = ms;
+		if (hipEventElapsedTime(&ms, p->ev[1], p->ev[2]) == hipSuccess) out->kernel_ms[1] = ms;
+		if (hipEventElapsedTime(&ms, p->ev[2], p->ev[6]) == hipSuccess) out->kernel_ms[2] = ms;
+	}
+	out->status = (int32_t)info.status;
+	if (info.status == BWAGPU_FQ_DECLINED) { out->declined_at = info.declined_at; return 0; }
+	if (info.status == BWAGPU_FQ_MORE) return 0;
+	const u64 n_reads = (u64)info.n_units;
+	if (n_reads >= (1ull << 31)) return p->fail(BWAGPU_EUNSUP, "a batch of 2^31 reads or more");
+	if ((u64)tot.n[0] + tot.n[1] != n_reads || (u64)tot.seq[0] + tot.seq[1] != info.total.seq || (u64)tot.name[0] + tot.name[1] != info.total.name ||
+		(u64)tot.com[0] + tot.com[1] != info.total.com || (tot.n[1] & 1)) return p->fail(BWAGPU_EHIP, "internal: the sub-batches do not add up to the batch");
+	out->n_reads = (int32_t)n_reads; out->consumed = info.consumed[0];
+	out->sub[0].status = out->sub[1].status = out->status;
+	int rc = 0;
+	out->cls = (uint8_t*)bwagpu_alloc_host(n_reads + 1);
+	if (!out->cls) rc = p->fail(BWAGPU_ENOMEM, "out of host memory (FASTQ batch)");
+	// device side: sub-batch 1's arrays lie behind sub-batch 0's in the parser's output buffers
+	const u64 ts = info.total.seq, tn = info.total.name, tc = info.total.com;
+	if (!rc && (p->o_seqs.ensure(ts + 1) || p->o_quals.ensure(ts + 1) || p->o_names.ensure(tn + 1) || p->o_com.ensure(tc + 1) || p->o_off.ensure((n_reads + 2) * 8) ||
+				p->o_name_off.ensure((n_reads + 2) * 8) || p->o_com_off.ensure((n_reads + 2) * 8) || p->o_has.ensure(n_reads + 1) || p->o_recs.ensure((n_reads + 1) * sizeof(bwagpu_fastq_rec_t)) ||
+				p->o_idx.ensure((n_reads + 1) * 4))) rc = p->fail(BWAGPU_ENOMEM, "hipMalloc failed (FASTQ outputs)");
+	FqsOut O; memset(&O, 0, sizeof O);
+	for (int k = 0; !rc && k < 2; ++k) {
+		bwagpu_fastq_out_t &s = out->sub[k];
+		const u64 m = tot.n[k], b_seq = k ? tot.seq[0] : 0, b_name = k ? tot.name[0] : 0, b_com = k ? tot.com[0] : 0, b_n = k ? tot.n[0] : 0;
+		out->n_sub[k] = s.n_reads = (int32_t)m;
+		out->idx[k] = (int32_t*)bwagpu_alloc_host((m + 1) * 4);
+		s.seqs = (uint8_t*)bwagpu_alloc_host((u64)tot.seq[k] + 1); s.off = (int64_t*)bwagpu_alloc_host((m + 1) * 8);
+		s.names = (char*)bwagpu_alloc_host((u64)tot.name[k] + 1); s.name_off = (int64_t*)bwagpu_alloc_host((m + 1) * 8);
+		s.quals = (char*)bwagpu_alloc_host((u64)tot.seq[k] + 1);
+		s.comments = (char*)bwagpu_alloc_host((u64)tot.com[k] + 1); s.comment_off = (int64_t*)bwagpu_alloc_host((m + 1) * 8);
+		s.has_comment = (uint8_t*)bwagpu_alloc_host(m + 1); s.recs = (bwagpu_fastq_rec_t*)bwagpu_alloc_host((m + 1) * sizeof(bwagpu_fastq_rec_t));
+		if (!out->idx[k] || !s.seqs || !s.off || !s.names || !s.name_off || !s.quals || !s.comments || !s.comment_off || !s.has_comment || !s.recs) { rc = p->fail(BWAGPU_ENOMEM, "out of host memory (FASTQ batch)"); break; }
+		s.off[0] = s.name_off[0] = s.comment_off[0] = 0;      // (an empty sub-batch: nothing else comes down)
+		FqOut &o = O.sub[k];
+		o.seqs = p->o_seqs.as<u8>() + b_seq; o.quals = p->o_quals.as<char>() + b_seq; o.names = p->o_names.as<char>() + b_name; o.comments = p->o_com.as<char>() + b_com;
+		o.off = p->o_off.as<i64>() + b_n + k; o.name_off = p->o_name_off.as<i64>() + b_n + k; o.comment_off = p->o_com_off.as<i64>() + b_n + k;
+		o.has_comment = p->o_has.as<u8>() + b_n; o.recs = p->o_recs.as<bwagpu_fastq_rec_t>() + b_n; O.idx[k] = p->o_idx.as<int32_t>() + b_n;
+	}
+	if (!rc && n_reads) {
+		const u64 eblocks = (n_reads + FQ_BLOCK / FQ_WAVE - 1) / (FQ_BLOCK / FQ_WAVE);
+		hipLaunchKernelGGL(k_fqs_emit, dim3((unsigned)(eblocks < 65536 ? eblocks : 65536)), dim3(FQ_BLOCK), 0, p->st, A, (const u8*)p->d_cls.as<u8>(), (const FqsSum*)sscan, n_reads, tot, O);
+		(void)hipEventRecord(p->ev[3], p->st);
+		auto down = [&](void *dst, const void *src, u64 bytes) { return bytes ? p->hip("download", hipMemcpyAsync(dst, src, (size_t)bytes, hipMemcpyDeviceToHost, p->st)) : 0; };
+		bool bad = down(out->cls, p->d_cls.p, n_reads) != 0;
+		for (int k = 0; !bad && k < 2; ++k) {
+			const bwagpu_fastq_out_t &s = out->sub[k]; const FqOut &o = O.sub[k];
+			const u64 m = tot.n[k];
+			if (!m) continue;
+			bad = down(s.seqs, o.seqs, tot.seq[k]) || down(s.quals, o.quals, tot.seq[k]) || down(s.names, o.names, tot.name[k]) || down(s.comments, o.comments, tot.com[k]) ||
+				  down(s.off, o.off, (m + 1) * 8) || down(s.name_off, o.name_off, (m + 1) * 8) || down(s.comment_off, o.comment_off, (m + 1) * 8) ||
+				  down(s.has_comment, o.has_comment, m) || down(s.recs, o.recs, m * sizeof(bwagpu_fastq_rec_t)) || down(out->idx[k], O.idx[k], m * 4);
+		}
+		// wait 2: the copies
+		if (bad || p->hip("sync", hipStreamSynchronize(p->st)) || p->hip("FASTQ emit kernel", hipGetLastError())) rc = BWAGPU_EHIP;
+		else { float ms = 0; if (hipEventElapsedTime(&ms, p->ev[6], p->ev[3]) == hipSuccess) out->kernel_ms[3] = ms; }
+	}
+	if (rc) { bwagpu_fastq_smart_free(out); fqs_init(out); }
+	return rc;
+}
+
+extern "C" int bwagpu_fastq_batch_smart(bwagpu_fastq_parser_t *p, const void *raw, int64_t len, int eof, int chunk_size, bwagpu_fastq_smart_t *out)
+{
+	if (!p) return BWAGPU_EINVAL;
+	if (!out || !raw || len < 0 || len >= ((int64_t)1 << 31) || chunk_size <= 0)
+		return p->fail(BWAGPU_EINVAL, "bwagpu_fastq_batch_smart: NULL argument, negative length, window of 2^31 bytes or more, or chunk_size <= 0");
+	fqs_init(out);
+	p->err.clear();
+	if (hipSetDevice(p->device) != hipSuccess) return p->fail(BWAGPU_ENODEV, "hipSetDevice failed");
+	FqArgs A;
+	const u64 lens[2] = { (u64)len, 0 }; const int eofs[2] = { eof, 1 };
+	u32 tiles = 0; u64 cap_units = 0;
+	if (int rc = fq_setup(p, A, 1, lens, eofs, &tiles, &cap_units)) return rc;
+	if (len && p->hip("copy window", hipMemcpyAsync(p->d_buf[0].p, raw, (size_t)len, hipMemcpyHostToDevice, p->st))) return BWAGPU_EHIP;
+	return fqs_run(p, A, tiles, cap_units, chunk_size, out);
+}
+
+extern "C" int bwagpu_fastq_batch_smart_bgzf(bwagpu_fastq_parser_t *p, const bwagpu_bgzf_win_t *w1, int chunk_size, bwagpu_fastq_smart_t *out, bwagpu_bgzf_info_t *info)
+{
+	if (!p) return BWAGPU_EINVAL;
+	if (!(w1 && out && info && chunk_size > 0 && w1->comp && w1->comp_len >= 0 && w1->skip >= 0))
+		return p->fail(BWAGPU_EINVAL, "bwagpu_fastq_batch_smart_bgzf: NULL argument, negative length or skip, or chunk_size <= 0");
+	fqs_init(out);
+	p->err.clear();
+	const bwagpu_bgzf_win_t *w[2] = { w1, nullptr };
+	bwagpu_bgzf_info_t both[2]; memset(both, 0, sizeof both);
+	int64_t consumed[2] = { 0, 0 };
+	const int rc = bz_batch(p, w, 1, both, &out->status, consumed, [&](const FqArgs &A, u32 tiles, u64 cap_units) {
+		const int r = fqs_run(p, A, tiles, cap_units, chunk_size, out);
+		consumed[0] = out->consumed;
+		return r;
+	});
+	*info = both[0];
+	return rc;
 }

@@ -49,8 +49,9 @@ static std::atomic<long> g_n_alns_reads(0);      // ... reads finalized from suc
 static int g_device_samtext = 0;  // BWAGPU_CLI_SAMTEXT=1: single-end batches without -5 take their SAM text from the device (bwagpu_batch_sam, after the CIGAR call, in place of bwagpu_batch_alns / bwagpu_batch_primary; device CIGARs on; same output); a read the device declines goes through the host formatter.
                                   // Paired-end batches, under BWAGPU_CLI_SAMPE's conditions (whether or not that switch is set): bwagpu_batch_sam_pe in place of every device call behind the download; a pair the device declines runs the host's mem_sam_pe on the download's lists
 static std::atomic<long> g_n_samtext_reads(0);   // ... reads written from such text
-static int g_device_bgzf = 0;     // BWAGPU_CLI_BGZF_DEV=1 (with BWAGPU_CLI_FASTQ=1): BGZF files (all of them, no -p) go to the device compressed and are inflated there (bwagpu_fastq_batch_bgzf)
-static int g_device_fastq = 0;    // BWAGPU_CLI_FASTQ=1: plain FASTQ files (one or two, no -p) are parsed on the device (bwagpu_fastq_batch): records, bseq_read's cut, base codes and the name / quality / comment
+static int g_device_bgzf = 0;     // BWAGPU_CLI_BGZF_DEV=1 (with BWAGPU_CLI_FASTQ=1): BGZF files (all of them; -p with BWAGPU_CLI_SMARTPE_DEV=1 only) go to the device compressed and are inflated there (bwagpu_fastq_batch_bgzf)
+static int g_device_smartpe = 0;  // BWAGPU_CLI_SMARTPE_DEV=1 (with BWAGPU_CLI_FASTQ=1 and -p): the interleaved file is parsed, classified (bseq_classify) and split into its single-end and paired-end sub-batches on the device (bwagpu_fastq_batch_smart; a BGZF file with BWAGPU_CLI_BGZF_DEV=1 too)
+static int g_device_fastq = 0;    // BWAGPU_CLI_FASTQ=1: plain FASTQ files (one or two; -p with BWAGPU_CLI_SMARTPE_DEV=1 only) are parsed on the device (bwagpu_fastq_batch): records, bseq_read's cut, base codes and the name / quality / comment
                                   // blobs of BWAGPU_CLI_SAMTEXT come from there; a batch the device declines, and the input behind it, goes through the reader below (same output)
 static std::string g_dev_rg_id; static bool g_dev_copy_comment = false;      // -R's id and -C for that call (set before the stages start)
 static std::atomic<long> g_n_primary_reads(0);   // ... reads finalized from such records (the BWAGPU_CLI_TRACE line at the end of the run)
@@ -262,6 +263,7 @@ struct Source {
 static void trim_readno(Seq &s, Arena &A) { char *T = s.base ? s.base : A.data(); if (s.l_name > 2 && T[s.name + s.l_name - 2] == '/' && isdigit((unsigned char)T[s.name + s.l_name - 1])) { s.l_name -= 2; T[s.name + s.l_name] = 0; } }
 
 struct Batch { Arena text; std::vector<Seq> seqs; std::vector<std::shared_ptr<ParBlock>> blocks;   /* parsed blocks the records with a base of their own lie in */
+	std::shared_ptr<bwagpu_fastq_smart_t> fqs; /* ... or, with -p, classified and split there too (BWAGPU_CLI_SMARTPE_DEV): a Sub's fq points to its sub-batch */
 	std::shared_ptr<bwagpu_fastq_out_t> fq;   /* a batch parsed on the device (BWAGPU_CLI_FASTQ): its arrays -- read i of the batch is read i there; seqs has gone to the Sub's flat */
 	const char *T(const Seq &q) const { return q.base ? q.base : text.data(); } };
 
@@ -269,7 +271,7 @@ static bool read_batch(Source &r1, Source *r2, int chunk, Batch &out)
 {
 	static long batch_no = 0;
 	const long id = batch_no++;
-	out.seqs.clear(); out.text.clear(); out.blocks.clear(); out.fq.reset();
+	out.seqs.clear(); out.text.clear(); out.blocks.clear(); out.fq.reset(); out.fqs.reset();
 	if (out.text.capacity() == 0) { out.text.reserve((size_t)chunk * 5 / 2 + (1 << 20)); out.seqs.reserve((size_t)chunk / 64 + 1024); }   // ~2.3 text bytes per base
 	long size = 0; Seq s, s2;
 	while (r1.read(s, out.text, out.blocks, id)) {
@@ -352,6 +354,7 @@ struct HostBuf {
 struct Sub {      // one mem_process_seqs call (bwamem.c:1235-1264) on the reads `idx` of its batch
 	std::vector<int> idx; bwagpu_opt_t opt; int64_t n_processed = 0;
 	HostBuf flat; std::vector<int64_t> off; std::vector<int32_t> counts; bool encoded = false;   /* flat / off came with the batch (BWAGPU_CLI_FASTQ) */
+	const bwagpu_fastq_out_t *fq = nullptr;   /* the device's sub-batch of this call (the Batch's fqs owns it): read i of the call is read i there */
 	bwagpu_alnreg_t *all = nullptr; int64_t tot = 0;
 	bwagpu_cigar_t *cigs = nullptr;           // device-side global alignments of the regions (bwagpu_batch_cigars)
 	uint32_t *cig_ops = nullptr;              // ... and the operation array its records with more than 6 operations point into
@@ -497,6 +500,66 @@ struct DevInput {
 		last_comp = 0;
 		for (int k = 0; k < nf; ++k) { pos[k] += (size_t)info[k].next_coff; uoff[k] = (size_t)info[k].next_uoff; if ((size_t)info[k].next_coff > last_comp) last_comp = (size_t)info[k].next_coff; }
 		out.fq = o;
+		++n_dev_batches; n_dev_reads += n;
+		return 1;
+	}
+	// -p (BWAGPU_CLI_SMARTPE_DEV): a batch of the one interleaved file, classified and split on the device.  next()'s contract; the batch's reads are in out.seqs in
+	// input order (the finalize stage and the by-read output index them by Sub::idx), their fields copied from the sub-batches' blobs; out.fqs holds both sub-batches
+	bool smart = false;
+	int next_smart(int chunk, Batch &out, int n_threads) {
+		size_t win = bgzf ? (last_comp ? last_comp + last_comp / 4 + ((size_t)192 << 10) : (size_t)((double)window_for(chunk) / (ratio > 1.0 ? ratio : 1.0)) + ((size_t)256 << 10)) : window_for(chunk);
+		std::shared_ptr<bwagpu_fastq_smart_t> o(new bwagpu_fastq_smart_t(), [](bwagpu_fastq_smart_t *x) { bwagpu_fastq_smart_free(x); delete x; });
+		memset(o.get(), 0, sizeof(bwagpu_fastq_smart_t));
+		bwagpu_bgzf_info_t info; memset(&info, 0, sizeof info);
+		for (;;) {
+			const size_t left = size[0] - pos[0], len = left < win ? left : win;
+			const char *at = map[0] ? map[0] + pos[0] : "";
+			int rc;
+			{
+				std::unique_lock<std::mutex> serial(g_dev_mutex, std::defer_lock);
+				if (g_dev_serialize) serial.lock();
+				if (bgzf) { bwagpu_bgzf_win_t w; w.comp = at; w.comp_len = (int64_t)len; w.skip = (int32_t)uoff[0]; w.eof = len == left; rc = bwagpu_fastq_batch_smart_bgzf(p, &w, chunk, o.get(), &info); }
+				else rc = bwagpu_fastq_batch_smart(p, at, (int64_t)len, len == left, chunk, o.get());
+			}
+			if (rc != BWAGPU_OK) { fprintf(stderr, "[E::%s] bwagpu_fastq_batch_smart: %s: %s\n", "main_mem", bwagpu_strerror(rc), bwagpu_fastq_last_error(p)); fflush(stderr); fflush(stdout); _exit(EXIT_FAILURE); }
+			if (o->status == BWAGPU_FQ_DAMAGED) {
+				fprintf(stderr, "[E::%s] `%s' is a damaged or truncated BGZF file (a block does not inflate to its recorded size and checksum)\n", "main_mem", path[0].c_str());
+				fflush(stderr); fflush(stdout); _exit(EXIT_FAILURE);
+			}
+			if (o->status == BWAGPU_FQ_MORE) {
+				if (len == left || win >= ((size_t)1 << 31) - 1) return -1;      // (a batch that does not fit the largest window: the streaming reader)
+				win = win * 2 < ((size_t)1 << 31) - 1 ? win * 2 : ((size_t)1 << 31) - 1;
+				continue;
+			}
+			break;
+		}
+		if (o->status == BWAGPU_FQ_DECLINED) return -1;
+		if (bgzf) { n_bgzf_blocks += info.n_blocks; if (info.used_comp > 0 && info.inflated > 0) ratio = (double)info.inflated / (double)info.used_comp; }
+		const int n = o->n_reads;
+		if (n == 0) return 0;
+		out.seqs.clear(); out.text.clear(); out.blocks.clear();
+		out.seqs.resize((size_t)n);
+		size_t base[2] = { 0, 0 };
+		base[1] = (size_t)(o->sub[0].name_off[o->n_sub[0]] + o->sub[0].comment_off[o->n_sub[0]] + o->sub[0].off[o->n_sub[0]]) + 3 * (size_t)o->n_sub[0];
+		out.text.resize(base[1] + (size_t)(o->sub[1].name_off[o->n_sub[1]] + o->sub[1].comment_off[o->n_sub[1]] + o->sub[1].off[o->n_sub[1]]) + 3 * (size_t)o->n_sub[1]);
+		char *A = out.text.data();
+		for (int k = 0; k < 2; ++k) {
+			const bwagpu_fastq_out_t *r = &o->sub[k];
+			const int32_t *ix = o->idx[k];
+			parallel_for(n_threads < 4 ? n_threads : 4, o->n_sub[k], [&](long i) {
+				Seq &s = out.seqs[(size_t)ix[i]];
+				s = Seq();
+				const size_t ln = (size_t)(r->name_off[i + 1] - r->name_off[i]), lc = (size_t)(r->comment_off[i + 1] - r->comment_off[i]), ls = (size_t)(r->off[i + 1] - r->off[i]);
+				size_t a = base[k] + (size_t)(r->name_off[i] + r->comment_off[i] + r->off[i]) + 3 * (size_t)i;
+				s.name = a; s.l_name = (int)ln; memcpy(A + a, r->names + r->name_off[i], ln); a += ln; A[a++] = 0;
+				s.comment = a; s.has_comment = r->has_comment[i] != 0; memcpy(A + a, r->comments + r->comment_off[i], lc); a += lc; A[a] = 0;
+				s.seq = a++;                                         // (the bases exist as codes only: an empty string here)
+				s.qual = a; s.l_seq = (int)ls; s.l_qual = (int)ls; s.has_qual = true; memcpy(A + a, r->quals + r->off[i], ls); A[a + ls] = 0;
+			});
+		}
+		if (bgzf) { pos[0] += (size_t)info.next_coff; uoff[0] = (size_t)info.next_uoff; last_comp = (size_t)info.next_coff; }
+		else pos[0] += (size_t)o->consumed;
+		out.fqs = o;
 		++n_dev_batches; n_dev_reads += n;
 		return 1;
 	}
@@ -713,8 +776,8 @@ static void device_sub(const std::vector<bwagpu_t*> &gpus, Sub &u, const RefSeqs
 			if (s.tot == 0) return;      // (no CIGAR call for this shard: its reads print the unmapped record on the host)
 			const int m = s.hi - s.lo;
 			bwagpu_sam_in_t si; memset(&si, 0, sizeof si);
-			if (in->fq && u.encoded) {      // parsed on the device: the shard is a slice of the parse's blobs (offsets need not start at 0)
-				const bwagpu_fastq_out_t &f = *in->fq;
+			if ((u.fq || in->fq) && u.encoded) {      // parsed on the device: the shard is a slice of the parse's blobs (offsets need not start at 0)
+				const bwagpu_fastq_out_t &f = u.fq ? *u.fq : *in->fq;
 				si.names = f.names; si.name_off = f.name_off + s.lo; si.quals = f.quals + u.off[s.lo];
 				if (g_dev_copy_comment) { si.comments = f.comments; si.comment_off = f.comment_off + s.lo; }
 				si.rg_id = g_dev_rg_id.c_str();
@@ -794,8 +857,8 @@ static void device_sub(const std::vector<bwagpu_t*> &gpus, Sub &u, const RefSeqs
 			const int m = s.hi - s.lo;
 			bwagpu_sam_in_t si; memset(&si, 0, sizeof si);
 			std::vector<int32_t> m_counts((size_t)m);
-			if (in->fq && u.encoded) {      // parsed on the device: slices of the parse's blobs
-				const bwagpu_fastq_out_t &f = *in->fq;
+			if ((u.fq || in->fq) && u.encoded) {      // parsed on the device: slices of the parse's blobs
+				const bwagpu_fastq_out_t &f = u.fq ? *u.fq : *in->fq;
 				for (int i = s.lo + 1; i < s.hi; i += 2) {      // (mates of different names: the finalize stage reports them as the reference does)
 					const int64_t a = f.name_off[i - 1], b = f.name_off[i], c = f.name_off[i + 1];
 					if (b - a != c - b || memcmp(f.names + a, f.names + b, (size_t)(b - a)) != 0) return;
@@ -1182,9 +1245,11 @@ int main(int argc, char *argv[])
 	if (getenv("BWAGPU_CLI_FASTQ")) g_device_fastq = atoi(getenv("BWAGPU_CLI_FASTQ"));
 	if (getenv("BWAGPU_CLI_BGZF_DEV")) g_device_bgzf = atoi(getenv("BWAGPU_CLI_BGZF_DEV"));
 	std::unique_ptr<DevInput> dev_in;
-	if (g_device_fastq && !(opt.flag & F_SMARTPE) && !getenv("BWAGPU_CLI_PARSE_ONLY")) {
+	if (getenv("BWAGPU_CLI_SMARTPE_DEV")) g_device_smartpe = atoi(getenv("BWAGPU_CLI_SMARTPE_DEV"));
+	if (g_device_fastq && (!(opt.flag & F_SMARTPE) || g_device_smartpe) && !getenv("BWAGPU_CLI_PARSE_ONLY")) {
 		dev_in.reset(new DevInput());
-		dev_in->nf = optind + 2 < argc ? 2 : 1;
+		dev_in->smart = (opt.flag & F_SMARTPE) != 0;
+		dev_in->nf = optind + 2 < argc && !dev_in->smart ? 2 : 1;      // (-p: the second query file is ignored)
 		bool ok = dev_in->open_file(0, argv[optind + 1]) && (dev_in->nf < 2 || dev_in->open_file(1, argv[optind + 2]));      // (anything but plain regular files: the switch does not apply)
 		if (ok) {
 			char eb[256];
@@ -1246,6 +1311,7 @@ int main(int argc, char *argv[])
 	Source r1, r2; Source *pr2 = nullptr;
 	if (dev_in) { if (dev_in->nf > 1) { pr2 = &r2; opt.flag |= F_PE; } }      // (the readers are opened where the device hands over, at its offsets)
 	else if (!r1.open(argv[optind + 1], parse_pool.get())) { fprintf(stderr, "[E::%s] fail to open file `%s'.\n", "main_mem", argv[optind + 1]); return 1; }
+	if (dev_in && dev_in->smart && optind + 2 < argc && g_verbose >= 2) fprintf(stderr, "[W::%s] when '-p' is in use, the second query file is ignored.\n", "main_mem");
 	if (!dev_in && optind + 2 < argc) {
 		if (opt.flag & F_PE) { if (g_verbose >= 2) fprintf(stderr, "[W::%s] when '-p' is in use, the second query file is ignored.\n", "main_mem"); }
 		else { if (!r2.open(argv[optind + 2], parse_pool.get())) { fprintf(stderr, "[E::%s] fail to open file `%s'.\n", "main_mem", argv[optind + 2]); return 1; } pr2 = &r2; opt.flag |= F_PE; }
@@ -1369,7 +1435,7 @@ int main(int argc, char *argv[])
 			const double tr = now_s();
 			HostBuf dev_flat; std::vector<int64_t> dev_off; bool from_dev = false;
 			if (dev_in && !dev_in->fallback) {
-				const int got = dev_in->next(chunk, w->in, dev_flat, dev_off, opt.n_threads);
+				const int got = dev_in->smart ? dev_in->next_smart(chunk, w->in, opt.n_threads) : dev_in->next(chunk, w->in, dev_flat, dev_off, opt.n_threads);
 				if (got == 0) break;
 				if (got > 0) from_dev = true;
 				else {      // declined: this batch and everything behind it through the streaming reader, from the batch's start
@@ -1387,7 +1453,21 @@ int main(int argc, char *argv[])
 			const int n = (int)w->in.seqs.size();
 			long bp = 0; for (auto &q : w->in.seqs) bp += (long)q.l_seq;
 			if (g_verbose >= 3) fprintf(stderr, "[M::%s] read %d sequences (%ld bp)...\n", "process", n, bp);
-			if (opt.flag & F_SMARTPE) {   // -p: adjacent records with equal names are pairs (bseq_classify, bwa.c:114-130)
+			if ((opt.flag & F_SMARTPE) && from_dev) {   // -p, classified and split on the device: the two calls take their sub-batches as they came
+				bwagpu_fastq_smart_t *f = w->in.fqs.get();
+				for (int k = 0; k < 2; ++k) {
+					if (f->n_sub[k] == 0) continue;
+					const int m = f->n_sub[k];
+					Sub u; u.idx.assign(f->idx[k], f->idx[k] + m);
+					u.opt = opt; if (k) u.opt.flag |= F_PE; else u.opt.flag &= ~F_PE;
+					u.n_processed = n_processed + (k ? (int64_t)f->n_sub[0] : 0);
+					u.off.assign(f->sub[k].off, f->sub[k].off + m + 1);
+					{ HostBuf b; b.p = f->sub[k].seqs; b.cap = (size_t)f->sub[k].off[m] + 1; f->sub[k].seqs = nullptr; u.flat = std::move(b); }      // (the codes' block goes where encode_sub's would)
+					u.counts.assign((size_t)m, 0); u.encoded = true; u.fq = &f->sub[k];
+					w->subs.push_back(std::move(u));
+				}
+				if (w->subs.size() > 1) { w->out.assign((size_t)n, std::string()); w->by_read = true; }
+			} else if (opt.flag & F_SMARTPE) {   // -p: adjacent records with equal names are pairs (bseq_classify, bwa.c:114-130)
 				Sub se, pe; bool has_last = true; int i;
 				for (i = 1; i < n; ++i) {
 					if (has_last) {
@@ -1500,7 +1580,7 @@ int main(int argc, char *argv[])
 		if (tl_trace) fprintf(stderr, "[D::timeline] batch %ld finalize %.3f .. %.3f\n", w->no, tf - t_start, now_s() - t_start);
 		{
 			std::lock_guard<std::mutex> l(pool_m);
-			w->in.blocks.clear(); w->in.fq.reset(); // (the parsed blocks go back to their pool now, not when the batch is next used)
+			w->in.blocks.clear(); w->in.fq.reset(); w->in.fqs.reset(); // (the parsed blocks go back to their pool now, not when the batch is next used)
 			if (batch_pool.size() < 4) batch_pool.push_back(std::move(w->in));
 			for (Sub &u : w->subs) if (!u.encoded && flat_pool.size() < 6) flat_pool.push_back(std::move(u.flat));      // (a device-parsed batch's codes go back to the result pool its next batch draws from)
 		}

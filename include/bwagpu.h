@@ -707,6 +707,44 @@ int  bwagpu_bgzf_inflate(bwagpu_fastq_parser_t *p, const void *comp, int64_t com
 int  bwagpu_fastq_batch_bgzf(bwagpu_fastq_parser_t *p, const bwagpu_bgzf_win_t *w1, const bwagpu_bgzf_win_t *w2 /* NULL: one file */,
                              int chunk_size, bwagpu_fastq_out_t *out, bwagpu_bgzf_info_t info[2]);
 
+/* ---- interleaved input: `mem -p' ("smart pairing"), on the same parser ------------------------------------------------------------ */
+/* bwagpu_fastq_batch_smart: bwagpu_fastq_batch on ONE window, followed on the device by bseq_classify (bwa.c:114-130) and the split
+ * fastmap.c:94-105 makes of the batch: reads whose name equals the next or the last read's form pairs, the others are single, and
+ * mem_process_seqs runs on the single reads first and on the pairs second.  The whole batch is the one a one-window bwagpu_fastq_batch
+ * reports -- the same kernels and statuses, status / n_reads / consumed / declined_at with the same meaning (BWAGPU_FQ_MORE: nothing is
+ * delivered; BWAGPU_FQ_DECLINED: no arrays) -- and for BWAGPU_FQ_CUT and BWAGPU_FQ_END the call delivers
+ *   cls[n_reads]       0: single, 1: first of a pair, 2: second of a pair.  Classification starts anew with every batch, as the
+ *                      reference's does: a run of equal names that the cut divides is classified in two parts.
+ *   n_sub[k], idx[k]   k = 0: the single reads, k = 1: the reads of pairs (mates at 2j, 2j + 1), both in input order; idx[k][j] is the
+ *                      place in the batch of sub-batch k's read j.
+ *   sub[k]             sub-batch k complete, in bwagpu_fastq_out_t's layouts and from the same pool: seqs, off, names, name_off, quals,
+ *                      comments, comment_off, has_comment, recs (n_reads == n_sub[k], status as the whole batch's; consumed, declined_*
+ *                      and kernel_ms are not used).  An empty sub-batch has valid arrays with off[0] == name_off[0] == comment_off[0] == 0.
+ *                      The first read of sub-batch 0 has the batch's first read number, the first of sub-batch 1 that number + n_sub[0].
+ * Names are compared after trim_readno and as strcmp compares them: a name may hold a NUL byte (it is no white space to kseq), and two
+ * names are equal when they agree up to and including the first NUL of either, the end of a name counting as one.  The names
+ * delivered keep all their bytes, as the reference's do.
+ * Host waits: bwagpu_fastq_batch's two and no other -- the classes are computed before the first one, whose copy brings the sub-batches'
+ * sizes along with the batch's.
+ * bwagpu_fastq_batch_smart_bgzf: the same over the text of one BGZF window (bwagpu_fastq_batch_bgzf's rules: skip, MORE for a first
+ * block not in view, BWAGPU_FQ_DAMAGED wins, next_coff / next_uoff in *info).
+ * BWAGPU_EINVAL: NULL p / raw / out, a negative length, a window of 2^31 bytes or more, chunk_size <= 0; for BGZF: NULL p / w / w->comp /
+ * out / info, a negative comp_len or skip, skip beyond the first block's ISIZE, chunk_size <= 0. */
+typedef struct {
+	int32_t status, n_reads;
+	int64_t consumed;                  /* bytes of the window that became this batch's records */
+	int64_t declined_at;               /* DECLINED: byte offset of the first record not taken, else -1 */
+	uint8_t *cls;                      /* n_reads classes */
+	int32_t n_sub[2];
+	int32_t *idx[2];                   /* n_sub[k] each */
+	bwagpu_fastq_out_t sub[2];
+	float kernel_ms[4];                /* newline + check passes, cut, classification, emit */
+} bwagpu_fastq_smart_t;
+int  bwagpu_fastq_batch_smart(bwagpu_fastq_parser_t *p, const void *raw, int64_t len, int eof, int chunk_size, bwagpu_fastq_smart_t *out);
+int  bwagpu_fastq_batch_smart_bgzf(bwagpu_fastq_parser_t *p, const bwagpu_bgzf_win_t *w, int chunk_size, bwagpu_fastq_smart_t *out,
+                                   bwagpu_bgzf_info_t *info);
+void bwagpu_fastq_smart_free(bwagpu_fastq_smart_t *out);   /* releases every array; idempotent */
+
 /* ---- lifetime ------------------------------------------------------------------------------------------ */
 
 /* Create a handle on HIP device `device` and upload the index once (replaces nothing in the reference; it is
