@@ -306,14 +306,30 @@ class BwaGpu:
         self._chk(self.L.bwagpu_batch_cigar_ops(self.h, C.byref(p), C.byref(n)))
         return self._take(p, n.value, np.dtype("<u4"))
 
+    @staticmethod
+    def _flat_reads(seqs, off, n):
+        """the reads of a *_flat call: contiguous (seqs uint8, off int64), one offset more than the n reads"""
+        seqs, off = np.ascontiguousarray(seqs, dtype=np.uint8), np.ascontiguousarray(off, dtype=np.int64)
+        assert off.shape == (n + 1,)
+        return seqs, off
+
+    @staticmethod
+    def _flat_lists(counts, regs, ids=None):
+        """the lists of a *_flat call: contiguous (counts int32, regs ALNREG_DTYPE[, ids int64, one per read]), as many regions as the counts say"""
+        counts, regs = np.ascontiguousarray(counts, dtype=np.int32), np.ascontiguousarray(regs, dtype=ALNREG_DTYPE)
+        assert int(counts.sum()) == regs.shape[0]
+        if ids is None:
+            return counts, regs
+        ids = np.ascontiguousarray(ids, dtype=np.int64)
+        assert ids.shape == counts.shape
+        return counts, regs, ids
+
     def cigars_flat(self, opt: MemOpt, seqs: np.ndarray, off: np.ndarray, counts: np.ndarray, regs: np.ndarray):
         """bwagpu_cigars_flat: the kernels of cigars() on reads (nt4, int64 offsets) and region lists of the caller (read i: counts[i] records of regs)
         -> (CIGAR_DTYPE records in the regions' order, the operation array they point into).  Leaves the last cigars() / cigar_ops() of the handle alone."""
-        seqs = np.ascontiguousarray(seqs, dtype=np.uint8)
-        off = np.ascontiguousarray(off, dtype=np.int64)
-        counts = np.ascontiguousarray(counts, dtype=np.int32)
-        regs = np.ascontiguousarray(regs, dtype=ALNREG_DTYPE)
-        assert off.shape[0] == counts.shape[0] + 1 and int(off[-1]) == seqs.shape[0] and int(counts.sum()) == regs.shape[0]
+        counts, regs = self._flat_lists(counts, regs)
+        seqs, off = self._flat_reads(seqs, off, counts.shape[0])
+        assert int(off[-1]) == seqs.shape[0]
         p, n, po, no = C.c_void_p(), C.c_int64(), C.c_void_p(), C.c_int64()
         self._chk(self.L.bwagpu_cigars_flat(self.h, C.byref(opt), counts.shape[0], seqs.ctypes.data, off.ctypes.data, counts.ctypes.data, regs.ctypes.data,
                                             C.byref(p), C.byref(n), C.byref(po), C.byref(no)))
@@ -328,11 +344,9 @@ class BwaGpu:
     def dedup_flat(self, opt: MemOpt, seqs: np.ndarray, off: np.ndarray, counts: np.ndarray, regs: np.ndarray):
         """bwagpu_dedup_flat: the de-duplication stage of run() on reads (nt4, int64 offsets) and raw region lists of the caller (read i: counts[i] records of regs)
         -> (counts left per read, their ALNREG_DTYPE records read by read, the routine that finished each read: 0 dedup_read, 1 dedup_read_wave, 2 dedup_read_par)."""
-        seqs = np.ascontiguousarray(seqs, dtype=np.uint8)
-        off = np.ascontiguousarray(off, dtype=np.int64)
-        counts = np.ascontiguousarray(counts, dtype=np.int32)
-        regs = np.ascontiguousarray(regs, dtype=ALNREG_DTYPE)
-        assert off.shape[0] == counts.shape[0] + 1 and int(off[-1]) == seqs.shape[0] and int(counts.sum()) == regs.shape[0]
+        counts, regs = self._flat_lists(counts, regs)
+        seqs, off = self._flat_reads(seqs, off, counts.shape[0])
+        assert int(off[-1]) == seqs.shape[0]
         left = np.zeros(counts.shape[0], dtype=np.int32)
         form = np.full(counts.shape[0], -1, dtype=np.int32)
         p, n = C.c_void_p(), C.c_int64()
@@ -365,10 +379,7 @@ class BwaGpu:
 
     def primary_flat(self, opt: MemOpt, counts: np.ndarray, regs: np.ndarray, ids: np.ndarray):
         """bwagpu_primary_flat: the same kernels on region lists of the caller (read i: counts[i] records of regs, id ids[i]) -> (records, n_pri, ms)."""
-        counts = np.ascontiguousarray(counts, dtype=np.int32)
-        regs = np.ascontiguousarray(regs, dtype=ALNREG_DTYPE)
-        ids = np.ascontiguousarray(ids, dtype=np.int64)
-        assert counts.shape == ids.shape and int(counts.sum()) == regs.shape[0]
+        counts, regs, ids = self._flat_lists(counts, regs, ids)
         p, ms = C.c_void_p(), C.c_float()
         n_pri = np.zeros(counts.shape[0], dtype=np.int32)
         self._chk(self.L.bwagpu_primary_flat(self.h, C.byref(opt), counts.shape[0], counts.ctypes.data, regs.ctypes.data, ids.ctypes.data, C.byref(p), n_pri.ctypes.data, C.byref(ms)))
@@ -391,13 +402,11 @@ class BwaGpu:
     def alns_flat(self, opt: MemOpt, counts: np.ndarray, regs: np.ndarray, ids: np.ndarray, read_len: np.ndarray, cigs: np.ndarray, ops: np.ndarray):
         """bwagpu_alns_flat: the same kernels on unmarked lists of the caller (read i: counts[i] records of regs, id ids[i], read_len[i] bases) with one CIGAR
         record per region (cigs) and their operation array (ops) -> (records, n_aln, marking records, n_pri, ms)."""
-        counts = np.ascontiguousarray(counts, dtype=np.int32)
-        regs = np.ascontiguousarray(regs, dtype=ALNREG_DTYPE)
-        ids = np.ascontiguousarray(ids, dtype=np.int64)
+        counts, regs, ids = self._flat_lists(counts, regs, ids)
         read_len = np.ascontiguousarray(read_len, dtype=np.int32)
         cigs = np.ascontiguousarray(cigs, dtype=CIGAR_DTYPE)
         ops = np.ascontiguousarray(ops, dtype=np.uint32)
-        assert counts.shape == ids.shape == read_len.shape and int(counts.sum()) == regs.shape[0] == cigs.shape[0]
+        assert counts.shape == read_len.shape and regs.shape[0] == cigs.shape[0]
         p, pr, ms = C.c_void_p(), C.c_void_p(), C.c_float()
         n_aln = np.zeros(counts.shape[0], dtype=np.int32); n_pri = np.zeros(counts.shape[0], dtype=np.int32)
         self._chk(self.L.bwagpu_alns_flat(self.h, C.byref(opt), counts.shape[0], counts.ctypes.data, regs.ctypes.data, ids.ctypes.data, read_len.ctypes.data,
@@ -444,14 +453,11 @@ class BwaGpu:
 
     def sam_flat(self, opt: MemOpt, seqs, off, counts, regs, ids, cigs, ops, names, quals=None, comments=None, rg_id=None, extra_flag=0):
         """bwagpu_sam_flat: the same kernels on reads (nt4 with n + 1 offsets), unmarked lists, ids, CIGAR records and operation array of the caller -> as sam()."""
-        seqs = np.ascontiguousarray(seqs, dtype=np.uint8)
-        off = np.ascontiguousarray(off, dtype=np.int64)
-        counts = np.ascontiguousarray(counts, dtype=np.int32)
-        regs = np.ascontiguousarray(regs, dtype=ALNREG_DTYPE)
-        ids = np.ascontiguousarray(ids, dtype=np.int64)
+        counts, regs, ids = self._flat_lists(counts, regs, ids)
+        seqs, off = self._flat_reads(seqs, off, counts.shape[0])
         cigs = np.ascontiguousarray(cigs, dtype=CIGAR_DTYPE)
         ops = np.ascontiguousarray(ops, dtype=np.uint32)
-        assert counts.shape == ids.shape == (off.shape[0] - 1,) and int(counts.sum()) == regs.shape[0] == cigs.shape[0]
+        assert regs.shape[0] == cigs.shape[0]
         return self._sam_call(counts.shape[0], names, quals, comments, rg_id, extra_flag,
                               lambda i, o: self.L.bwagpu_sam_flat(self.h, C.byref(opt), counts.shape[0], seqs.ctypes.data, off.ctypes.data, counts.ctypes.data, regs.ctypes.data,
                                                                   ids.ctypes.data, cigs.ctypes.data, ops.ctypes.data if ops.shape[0] else None, ops.shape[0], i, o))
@@ -476,11 +482,10 @@ class BwaGpu:
         """bwagpu_pair_flat: the pairing kernels on marked lists of the caller (reads 2p, 2p + 1: counts[] records of regs each, of which the first n_pri[]
         take part; pair p has id ids[p]) -> (PAIR_DTYPE[n pairs], ms)."""
         pes = np.ascontiguousarray(pes, dtype=PESTAT_DTYPE)
-        counts = np.ascontiguousarray(counts, dtype=np.int32)
+        counts, regs = self._flat_lists(counts, regs)
         n_pri = np.ascontiguousarray(n_pri, dtype=np.int32)
-        regs = np.ascontiguousarray(regs, dtype=ALNREG_DTYPE)
-        ids = np.ascontiguousarray(ids, dtype=np.int64)
-        assert pes.shape == (4,) and counts.shape == n_pri.shape == (2 * ids.shape[0],) and int(counts.sum()) == regs.shape[0]
+        ids = np.ascontiguousarray(ids, dtype=np.int64)      # (one per pair)
+        assert pes.shape == (4,) and counts.shape == n_pri.shape == (2 * ids.shape[0],)
         p, ms = C.c_void_p(), C.c_float()
         self._chk(self.L.bwagpu_pair_flat(self.h, C.byref(opt), pes.ctypes.data, ids.shape[0], counts.ctypes.data, n_pri.ctypes.data, regs.ctypes.data, ids.ctypes.data, C.byref(p), C.byref(ms)))
         return self._take(p, ids.shape[0], PAIR_DTYPE), ms.value
@@ -514,15 +519,14 @@ class BwaGpu:
     def rescue_flat(self, opt: MemOpt, pes: np.ndarray, seqs: np.ndarray, off: np.ndarray, counts_in: np.ndarray, regs_in: np.ndarray, ids=None, pri: bool = True, pairs: bool = True) -> dict:
         """bwagpu_rescue_flat: the same kernels on reads (nt4, read i at seqs[off[i]:off[i + 1]]) and region lists of the caller; ids: one per read (needed for pri / pairs)."""
         pes = np.ascontiguousarray(pes, dtype=PESTAT_DTYPE)
-        seqs = np.ascontiguousarray(seqs, dtype=np.uint8); off = np.ascontiguousarray(off, dtype=np.int64)
-        counts_in = np.ascontiguousarray(counts_in, dtype=np.int32); regs_in = np.ascontiguousarray(regs_in, dtype=ALNREG_DTYPE)
-        n = counts_in.shape[0]
-        assert pes.shape == (4,) and n % 2 == 0 and off.shape == (n + 1,) and int(counts_in.sum()) == regs_in.shape[0]
         if ids is None:
             pri = pairs = False
+            counts_in, regs_in = self._flat_lists(counts_in, regs_in)
         else:
-            ids = np.ascontiguousarray(ids, dtype=np.int64)
-            assert ids.shape == (n,)
+            counts_in, regs_in, ids = self._flat_lists(counts_in, regs_in, ids)
+        n = counts_in.shape[0]
+        seqs, off = self._flat_reads(seqs, off, n)
+        assert pes.shape == (4,) and n % 2 == 0
         counts, n_pri = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
         pr, ps, nr, prec, ppri, ppair, ms = C.c_void_p(), C.c_void_p(), C.c_int64(), C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_float()
         self._chk(self.L.bwagpu_rescue_flat(self.h, C.byref(opt), pes.ctypes.data, n // 2, seqs.ctypes.data, off.ctypes.data, counts_in.ctypes.data, regs_in.ctypes.data,
@@ -556,11 +560,10 @@ class BwaGpu:
     def sampe_flat(self, opt: MemOpt, pes: np.ndarray, seqs: np.ndarray, off: np.ndarray, counts_in: np.ndarray, regs_in: np.ndarray, ids: np.ndarray) -> dict:
         """bwagpu_sampe_flat: the same kernels on reads and region lists of the caller (the inputs of rescue_flat; ids: one per read)."""
         pes = np.ascontiguousarray(pes, dtype=PESTAT_DTYPE)
-        seqs = np.ascontiguousarray(seqs, dtype=np.uint8); off = np.ascontiguousarray(off, dtype=np.int64)
-        counts_in = np.ascontiguousarray(counts_in, dtype=np.int32); regs_in = np.ascontiguousarray(regs_in, dtype=ALNREG_DTYPE)
-        ids = np.ascontiguousarray(ids, dtype=np.int64)
+        counts_in, regs_in, ids = self._flat_lists(counts_in, regs_in, ids)
         n = counts_in.shape[0]
-        assert pes.shape == (4,) and n % 2 == 0 and off.shape == (n + 1,) and int(counts_in.sum()) == regs_in.shape[0] and ids.shape == (n,)
+        seqs, off = self._flat_reads(seqs, off, n)
+        assert pes.shape == (4,) and n % 2 == 0
         counts, o = np.zeros(n, dtype=np.int32), PeOut()
         self._chk(self.L.bwagpu_sampe_flat(self.h, C.byref(opt), pes.ctypes.data, n // 2, seqs.ctypes.data, off.ctypes.data, counts_in.ctypes.data, regs_in.ctypes.data, ids.ctypes.data,
                                            counts.ctypes.data, C.byref(o)))
@@ -590,11 +593,10 @@ class BwaGpu:
     def sam_pe_flat(self, opt: MemOpt, pes: np.ndarray, seqs, off, counts_in, regs_in, ids, names, quals=None, comments=None, rg_id=None, extra_flag=0, want_records=False) -> dict:
         """bwagpu_sam_pe_flat: the same kernels on reads and region lists of the caller (the inputs of sampe_flat) -> as sam_pe()."""
         pes = np.ascontiguousarray(pes, dtype=PESTAT_DTYPE)
-        seqs = np.ascontiguousarray(seqs, dtype=np.uint8); off = np.ascontiguousarray(off, dtype=np.int64)
-        counts_in = np.ascontiguousarray(counts_in, dtype=np.int32); regs_in = np.ascontiguousarray(regs_in, dtype=ALNREG_DTYPE)
-        ids = np.ascontiguousarray(ids, dtype=np.int64)
+        counts_in, regs_in, ids = self._flat_lists(counts_in, regs_in, ids)
         n = counts_in.shape[0]
-        assert pes.shape == (4,) and n % 2 == 0 and off.shape == (n + 1,) and int(counts_in.sum()) == regs_in.shape[0] and ids.shape == (n,)
+        seqs, off = self._flat_reads(seqs, off, n)
+        assert pes.shape == (4,) and n % 2 == 0
         counts, o = np.zeros(n, dtype=np.int32), PeOut()
         res = self._sam_call(n, names, quals, comments, rg_id, extra_flag,
                              lambda i, so: self.L.bwagpu_sam_pe_flat(self.h, C.byref(opt), pes.ctypes.data, n // 2, seqs.ctypes.data, off.ctypes.data, counts_in.ctypes.data, regs_in.ctypes.data,
@@ -618,9 +620,7 @@ class BwaGpu:
 
     def pestat_flat(self, opt: MemOpt, counts: np.ndarray, regs: np.ndarray):
         """bwagpu_pestat_flat: the same kernels on region lists of the caller (read i: counts[i] records of regs) -> (pes, info, ms)."""
-        counts = np.ascontiguousarray(counts, dtype=np.int32)
-        regs = np.ascontiguousarray(regs, dtype=ALNREG_DTYPE)
-        assert int(counts.sum()) == regs.shape[0]
+        counts, regs = self._flat_lists(counts, regs)
         pes, info, ms = np.zeros(4, dtype=PESTAT_DTYPE), np.zeros(1, dtype=PESTAT_INFO_DTYPE), C.c_float()
         self._chk(self.L.bwagpu_pestat_flat(self.h, C.byref(opt), counts.shape[0], counts.ctypes.data, regs.ctypes.data, pes.ctypes.data, info.ctypes.data, C.byref(ms)))
         return pes, info[0], ms.value

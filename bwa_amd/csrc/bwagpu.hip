@@ -108,19 +108,19 @@ struct bwagpu_s {
 	std::vector<double> pair_tab; bwagpu_pestat_t pair_tab_pes[4] = {}; i64 pair_tab_cap = -1; i32 pair_toff[4] = {}, pair_tlen[4] = {}; bool pair_tab_dev = false;   // the table as last filled: for these windows and this capacity; resident in d_pair_tab
 	DevBuf d_pst_hist, d_pst_out;                                                         // bwagpu_batch_pestat and its kin (dev_pestat.h): the histogram of insert sizes, four windows and the info record (PstOut) -- resident for the next device-side consumer
 	DevBuf d_aln_out, d_aln_n, d_aln_list, d_aln_ctr, d_aln_cigs, d_aln_ops, d_aln_len;                  // bwagpu_batch_alns / bwagpu_alns_flat (dev_alns.h): records, aa.n per read, the wavefront form's read list and its length; bwagpu_alns_flat's CIGAR records, operation array and read lengths
-	enum { ST_NAMES, ST_NAMEOFF, ST_QUAL, ST_COMM, ST_COMMOFF, ST_RG, ST_SEQ, ST_SEQOFF, ST_SIZE, ST_TOFF, ST_FLAGS, ST_LINES, ST_TEXT, ST_N };
-	DevBuf d_st[ST_N];      // bwagpu_batch_sam / bwagpu_sam_flat (dev_samtext.h): the reads' names, qualities, comments with their offsets, -R's id, bwagpu_sam_flat's reads; bytes per read, their prefix sums, flag words, lines per read, the text
-	DevBuf d_pf_regs, d_pf_cnt, d_pf_off, d_pf_ids;                                       // ... and the uploaded lists of the *_flat calls (FlatLists)
+	enum { ST_NAMES, ST_NAMEOFF, ST_QUAL, ST_COMM, ST_COMMOFF, ST_RG, ST_SIZE, ST_TOFF, ST_FLAGS, ST_LINES, ST_TEXT, ST_N };
+	DevBuf d_st[ST_N];      // bwagpu_batch_sam / bwagpu_sam_flat (dev_samtext.h): the reads' names, qualities, comments with their offsets, -R's id; bytes per read, their prefix sums, flag words, lines per read, the text
+	DevBuf d_pf_regs, d_pf_cnt, d_pf_off, d_pf_ids, d_pf_seq, d_pf_seqoff;                // ... and the uploaded lists (FlatLists) and reads (FlatReads) of the *_flat calls
 	std::vector<double> pri_log; i64 pri_log_dev = 0;                                      // log((double)k) by the host's libm for k < size; entries resident in d_pri_log
 	DevBuf d_msw_tasks, d_msw_out, d_msw_pes, d_msw_scratch;
-	enum { RS_X, RS_TOFF, RS_TIX, RS_ARENA, RS_ASRC, RS_ACNT, RS_POFF, RS_REGS, RS_SRC, RS_OUT, RS_LISTS, RS_CTR, RS_KEYS, RS_STAGE, RS_SEQ, RS_SEQOFF, RS_PAIRIDS, RS_N };
-	DevBuf d_rs[RS_N];      // bwagpu_batch_rescue / bwagpu_rescue_flat (dev_rescue.h): anchors x 4 per read and their prefix sums, the task table, the arena of working lists (regions, src, lengths), the packed merged lists (offsets, regions, src), records, the wavefront forms' pair lists and their lengths, HBM sort keys; bwagpu_rescue_flat's sequences, the pairs' ids
+	enum { RS_X, RS_TOFF, RS_TIX, RS_ARENA, RS_ASRC, RS_ACNT, RS_POFF, RS_REGS, RS_SRC, RS_OUT, RS_LISTS, RS_CTR, RS_KEYS, RS_STAGE, RS_PAIRIDS, RS_N };
+	DevBuf d_rs[RS_N];      // bwagpu_batch_rescue / bwagpu_rescue_flat (dev_rescue.h): anchors x 4 per read and their prefix sums, the task table, the arena of working lists (regions, src, lengths), the packed merged lists (offsets, regions, src), records, the wavefront forms' pair lists and their lengths, HBM sort keys; the pairs' ids
 	enum { SP_OUT, SP_LIST, SP_CTR, SP_READ, SP_CIGS, SP_EXT, SP_N };
 	DevBuf d_sp[SP_N];      // bwagpu_batch_sampe / bwagpu_sampe_flat (dev_sampe.h): the pair records, the wavefront form's pair list and its length, the merged lists' region-to-read map, their CIGAR records and operation array
-	enum { CF_SEQ, CF_SEQOFF, CF_READ, CF_CIGS, CF_EXT, CF_N };
-	DevBuf d_cf[CF_N];      // bwagpu_cigars_flat: the caller's reads and their offsets, the region-to-read map, the CIGAR records and the operation array (none of them a batch's)
-	enum { DF_SEQ, DF_SEQOFF, DF_REGS, DF_REGOFF, DF_NRAW, DF_CNT, DF_FORM, DF_BLOB, DF_DPH, DF_DPE, DF_CTR, DF_N };
-	DevBuf d_df[DF_N];     // bwagpu_dedup_flat: the caller's reads, offsets, regions and counts, the counts left, the routine per read, the sorts' key scratch, DP scratch, counters (none of them a batch's)
+	enum { CF_READ, CF_CIGS, CF_EXT, CF_N };
+	DevBuf d_cf[CF_N];      // bwagpu_cigars_flat: the region-to-read map, the CIGAR records and the operation array (none of them a batch's)
+	enum { DF_REGS, DF_REGOFF, DF_NRAW, DF_CNT, DF_FORM, DF_BLOB, DF_DPH, DF_DPE, DF_CTR, DF_N };
+	DevBuf d_df[DF_N];     // bwagpu_dedup_flat: the caller's regions, their offsets and counts, the counts left, the routine per read, the sorts' key scratch, DP scratch, counters (none of them a batch's)
 	i64 cigl_z_cap = 0;                          // bytes per direction matrix of the long CIGAR tier's scratch (grows with the batches)
 	DevBuf d_cigl_z, d_cigl_ops, d_cigl_md, d_cigl_list;      // scratch of the long-segment CIGAR tier (k_cigar_long): direction matrices, operations, MD strings per workgroup
 	DevBuf d_cig_ext; i64 cig_ext_n = -1;   // operation array of the last bwagpu_batch_cigars (records with 7..64 operations point into it)
@@ -524,7 +524,7 @@ extern "C" void bwagpu_destroy(bwagpu_t *h)
 		for (DevBuf *b : ib) b->release();
 		delete h->ibuf;
 	}
-	DevBuf *all[] = { &h->d_pst_hist, &h->d_pst_out, &h->d_pair_out, &h->d_pair_lists, &h->d_pair_ctr, &h->d_pair_scratch, &h->d_pair_tab, &h->d_pair_npri, &h->d_pri_out, &h->d_pri_npri, &h->d_pri_lists, &h->d_pri_ctr, &h->d_pri_scratch, &h->d_pri_log, &h->d_aln_out, &h->d_aln_n, &h->d_aln_list, &h->d_aln_ctr, &h->d_aln_cigs, &h->d_aln_ops, &h->d_aln_len, &h->d_pf_regs, &h->d_pf_cnt, &h->d_pf_off, &h->d_pf_ids, &h->d_heavy, &h->d_dd_tmp, &h->d_p2_tasks, &h->d_vr_tab, &h->d_vr_ovf, &h->d_intv_n3, &h->d_cigl_list, &h->d_cigl_z, &h->d_cigl_ops, &h->d_cigl_md, &h->d_seq_2b, &h->d_seq_flags, &h->d_cig_ext, &h->d_msw_tasks, &h->d_msw_out, &h->d_msw_pes, &h->d_msw_scratch, &h->d_pack_off, &h->d_regs_packed, &h->d_pack_read, &h->d_cigs, &h->d_seq, &h->d_seq_nib, &h->d_off, &h->d_ctr, &h->d_tmp_intv,
+	DevBuf *all[] = { &h->d_pst_hist, &h->d_pst_out, &h->d_pair_out, &h->d_pair_lists, &h->d_pair_ctr, &h->d_pair_scratch, &h->d_pair_tab, &h->d_pair_npri, &h->d_pri_out, &h->d_pri_npri, &h->d_pri_lists, &h->d_pri_ctr, &h->d_pri_scratch, &h->d_pri_log, &h->d_aln_out, &h->d_aln_n, &h->d_aln_list, &h->d_aln_ctr, &h->d_aln_cigs, &h->d_aln_ops, &h->d_aln_len, &h->d_pf_regs, &h->d_pf_cnt, &h->d_pf_off, &h->d_pf_ids, &h->d_pf_seq, &h->d_pf_seqoff, &h->d_heavy, &h->d_dd_tmp, &h->d_p2_tasks, &h->d_vr_tab, &h->d_vr_ovf, &h->d_intv_n3, &h->d_cigl_list, &h->d_cigl_z, &h->d_cigl_ops, &h->d_cigl_md, &h->d_seq_2b, &h->d_seq_flags, &h->d_cig_ext, &h->d_msw_tasks, &h->d_msw_out, &h->d_msw_pes, &h->d_msw_scratch, &h->d_pack_off, &h->d_regs_packed, &h->d_pack_read, &h->d_cigs, &h->d_seq, &h->d_seq_nib, &h->d_off, &h->d_ctr, &h->d_tmp_intv,
 		&h->d_intv_n, &h->d_intv_off, &h->d_intv, &h->d_seed_n, &h->d_seed_off, &h->d_slot_pos, &h->d_slot_qbeg, &h->d_slot_len, &h->d_slot_rid, &h->d_slot_blob, &h->d_chain_n, &h->d_node_off,
 		&h->d_order, &h->d_bin_cnt, &h->d_seed_w, &h->d_seed_order, &h->d_nodes, &h->d_reg_off, &h->d_reg_cap_r, &h->d_reg_n_raw, &h->d_reg_n, &h->d_regs, &h->d_regs_raw, &h->d_dp_h, &h->d_dp_e, &h->d_minhsp };
 	for (DevBuf *b : all) b->release();
@@ -1748,6 +1748,40 @@ struct FlatLists {
 		return BWAGPU_OK;
 	}
 };
+// The reads of a *_flat call: base codes back to back, read i at seqs[off[i] .. off[i + 1]).  scan(): what all these calls require of them -- offsets that are not
+// negative and ascend, no read of more than 2^30 - 1 bases, sequences where there are bases -- and the first offset, the end of the last read, the longest read;
+// false: BWAGPU_EINVAL.  codes_ok(): no base code above 4 in a read; false: BWAGPU_EINVAL.  upload(): seqs[0 .. n_bases) (padded as a batch's d_seq is) and the
+// offsets into the handle's d_pf_seq / d_pf_seqoff, enqueued only -- ahead of FlatLists::upload, whose wait covers them, or of a wait of the caller's.  `what`
+// names the entry point in the error text, `tag` in upload()'s as FlatLists::upload's does.
+struct FlatReads {
+	const u8 *seqs = nullptr; const i64 *off = nullptr; size_t n = 0; i64 first = 0, n_bases = 0; int max_len = 0;
+	static bool bad_offsets(bwagpu_t *h, const char *what) { h->err = std::string(what) + ": offsets that do not ascend"; return false; }
+	bool scan(bwagpu_t *h, const char *what, size_t n_, const u8 *seqs_, const i64 *off_)
+	{
+		n = n_; seqs = seqs_; off = off_;
+		if (n == 0) return true;
+		if (off[0] < 0) return bad_offsets(h, what);
+		for (size_t i = 0; i < n; ++i) {
+			if (off[i + 1] < off[i] || off[i + 1] - off[i] > 0x3fffffff) return bad_offsets(h, what);
+			max_len = std::max(max_len, (int)(off[i + 1] - off[i]));
+		}
+		first = off[0]; n_bases = off[n];
+		return n_bases == 0 || seqs;
+	}
+	bool codes_ok(bwagpu_t *h, const char *what) const
+	{
+		for (i64 k = first; k < n_bases; ++k) if (seqs[k] > 4) { h->err = std::string(what) + ": a base code above 4"; return false; }
+		return true;
+	}
+	int upload(bwagpu_t *h, const char *tag) const
+	{
+		if (n == 0) return BWAGPU_OK;
+		if (h->d_pf_seq.ensure((size_t)n_bases + 16) || h->d_pf_seqoff.ensure((n + 1) * 8)) { h->err = std::string("hipMalloc failed (") + tag + ")"; return BWAGPU_ENOMEM; }
+		if (n_bases) HIPCHK(h, hipMemcpyAsync(h->d_pf_seq.p, seqs, (size_t)n_bases, hipMemcpyHostToDevice, h->stream));
+		HIPCHK(h, hipMemcpyAsync(h->d_pf_seqoff.p, off, (n + 1) * 8, hipMemcpyHostToDevice, h->stream));
+		return BWAGPU_OK;
+	}
+};
 // ---- the CIGAR kernels on lists of the caller (test hook) ------------------------------------------------------------------------------------------------
 extern "C" void bwagpu_cigar_limits(int32_t out[10])
 {
@@ -1764,14 +1798,9 @@ extern "C" int bwagpu_cigars_flat(bwagpu_t *h, const bwagpu_opt_t *opt, int n_re
 	FlatLists F; RegLists L;
 	if (!F.scan(h, (size_t)n_reads, counts, regs, nullptr)) { h->err = "bwagpu_cigars_flat: a count outside [0, 2^30), or counts without regions"; return BWAGPU_EINVAL; }
 	if (F.tot > 0x7fffffff) { h->err = "bwagpu_cigars_flat: more than 2^31 - 1 regions"; return BWAGPU_EINVAL; }
-	int max_len = 0;
-	for (int i = 0; i < n_reads; ++i) {
-		if (seq_off[0] != 0 || seq_off[i + 1] < seq_off[i] || seq_off[i + 1] - seq_off[i] > 0x3fffffff) { h->err = "bwagpu_cigars_flat: offsets that do not ascend"; return BWAGPU_EINVAL; }
-		max_len = std::max(max_len, (int)(seq_off[i + 1] - seq_off[i]));
-	}
-	const i64 n_bases = n_reads ? seq_off[n_reads] : 0;
-	if (n_bases > 0 && !seqs) return BWAGPU_EINVAL;
-	for (i64 k = 0; k < n_bases; ++k) if (seqs[k] > 4) { h->err = "bwagpu_cigars_flat: a base code above 4"; return BWAGPU_EINVAL; }
+	FlatReads R;
+	if (!R.scan(h, "bwagpu_cigars_flat", (size_t)n_reads, seqs, seq_off) || (R.first != 0 && !R.bad_offsets(h, "bwagpu_cigars_flat"))) return BWAGPU_EINVAL;      // R.first: this call's reads begin at seqs[0] (the pair calls take any first offset)
+	if (!R.codes_ok(h, "bwagpu_cigars_flat")) return BWAGPU_EINVAL;
 	for (int i = 0; i < n_reads; ++i) {
 		const i64 len = seq_off[i + 1] - seq_off[i];
 		for (i64 k = F.off[(size_t)i]; k < F.off[(size_t)i + 1]; ++k) {
@@ -1788,19 +1817,14 @@ extern "C" int bwagpu_cigars_flat(bwagpu_t *h, const bwagpu_opt_t *opt, int n_re
 	i64 ext_n = 0;
 	DevBuf *D = h->d_cf;
 	if (F.tot > 0) {
-		const int rc = F.upload(h, "cigars_flat", counts, regs, nullptr, 0, L);
-		if (rc != BWAGPU_OK) return rc;
-		if (D[bwagpu_s::CF_SEQ].ensure((size_t)n_bases + 1) || D[bwagpu_s::CF_SEQOFF].ensure(((size_t)n_reads + 1) * 8) || D[bwagpu_s::CF_READ].ensure((size_t)F.tot * 4)) {
-			h->err = "hipMalloc failed (cigars_flat)"; return BWAGPU_ENOMEM;
-		}
-		if (n_bases) HIPCHK(h, hipMemcpyAsync(D[bwagpu_s::CF_SEQ].p, seqs, (size_t)n_bases, hipMemcpyHostToDevice, h->stream));
-		HIPCHK(h, hipMemcpyAsync(D[bwagpu_s::CF_SEQOFF].p, seq_off, ((size_t)n_reads + 1) * 8, hipMemcpyHostToDevice, h->stream));
-		HIPCHK(h, wait_stream(h));      // (the caller's arrays are pageable, as in bwagpu_alns_flat)
+		if (int rc = R.upload(h, "cigars_flat")) return rc;
+		if (int rc = F.upload(h, "cigars_flat", counts, regs, nullptr, 0, L)) return rc;
+		if (D[bwagpu_s::CF_READ].ensure((size_t)F.tot * 4)) { h->err = "hipMalloc failed (cigars_flat)"; return BWAGPU_ENOMEM; }
 		int nb = (n_reads + 3) / 4; if (nb > 8192) nb = 8192;
 		hipLaunchKernelGGL(k_sampe_reg_read, dim3(nb), dim3(BLOCK), 0, h->stream, n_reads, L.d_cnt, L.d_off, D[bwagpu_s::CF_READ].as<i32>());
 		HIPCHK(h, hipGetLastError());
 		// (the filter's table is the lists' offsets: a read's first region is its best)
-		const CigLists C = { F.tot, L.d_regs, D[bwagpu_s::CF_READ].as<i32>(), L.d_off, D[bwagpu_s::CF_SEQ].as<u8>(), D[bwagpu_s::CF_SEQOFF].as<i64>(), n_reads, max_len, n_bases,
+		const CigLists C = { F.tot, L.d_regs, D[bwagpu_s::CF_READ].as<i32>(), L.d_off, h->d_pf_seq.as<u8>(), h->d_pf_seqoff.as<i64>(), n_reads, R.max_len, R.n_bases,
 							 &D[bwagpu_s::CF_CIGS], &D[bwagpu_s::CF_EXT] };
 		float ms[2] = { 0.f, 0.f };
 		const int rcc = cigars_run(h, opt, C, res.get(), &ext_n, ms);
@@ -1836,14 +1860,10 @@ extern "C" int bwagpu_dedup_flat(bwagpu_t *h, const bwagpu_opt_t *opt, int n_rea
 	FlatLists F; RegLists L;
 	if (!F.scan(h, (size_t)n_reads, counts, regs, nullptr)) { h->err = "bwagpu_dedup_flat: a count outside [0, 2^30), or counts without regions"; return BWAGPU_EINVAL; }
 	if (F.tot > 0x7fffffff) { h->err = "bwagpu_dedup_flat: more than 2^31 - 1 regions"; return BWAGPU_EINVAL; }
-	int max_len = 0;
-	for (int i = 0; i < n_reads; ++i) {
-		if (seq_off[0] != 0 || seq_off[i + 1] < seq_off[i] || seq_off[i + 1] - seq_off[i] > 0x3fffffff) { h->err = "bwagpu_dedup_flat: offsets that do not ascend"; return BWAGPU_EINVAL; }
-		max_len = std::max(max_len, (int)(seq_off[i + 1] - seq_off[i]));
-	}
-	const i64 n_bases = n_reads ? seq_off[n_reads] : 0;
-	if (n_bases > 0 && !seqs) return BWAGPU_EINVAL;
-	for (i64 k = 0; k < n_bases; ++k) if (seqs[k] > 4) { h->err = "bwagpu_dedup_flat: a base code above 4"; return BWAGPU_EINVAL; }
+	FlatReads R;
+	if (!R.scan(h, "bwagpu_dedup_flat", (size_t)n_reads, seqs, seq_off) || (R.first != 0 && !R.bad_offsets(h, "bwagpu_dedup_flat"))) return BWAGPU_EINVAL;      // R.first: this call's reads begin at seqs[0] (the pair calls take any first offset)
+	if (!R.codes_ok(h, "bwagpu_dedup_flat")) return BWAGPU_EINVAL;
+	const int max_len = R.max_len;
 	for (int i = 0; i < n_reads; ++i) {
 		const i64 len = seq_off[i + 1] - seq_off[i];
 		for (i64 k = F.off[(size_t)i]; k < F.off[(size_t)i + 1]; ++k) {
@@ -1875,13 +1895,12 @@ extern "C" int bwagpu_dedup_flat(bwagpu_t *h, const bwagpu_opt_t *opt, int n_rea
 	if (int rc = dedup_plan(h, opt, cfg, max_len, n, long_batch, share_pct, dp_waves, dd)) return rc;
 	DevBuf *D = h->d_df;
 	const size_t dp_bytes = (size_t)dp_waves * ((size_t)max_len + 2) * DPS * 4;
-	if (D[bwagpu_s::DF_SEQ].ensure((size_t)n_bases + 16) || D[bwagpu_s::DF_SEQOFF].ensure(((size_t)n + 1) * 8) || D[bwagpu_s::DF_REGS].ensure((size_t)(F.tot ? F.tot : 1) * sizeof(bwagpu_alnreg_t)) ||
+	if (D[bwagpu_s::DF_REGS].ensure((size_t)(F.tot ? F.tot : 1) * sizeof(bwagpu_alnreg_t)) ||
 		D[bwagpu_s::DF_REGOFF].ensure(((size_t)n + 1) * 8) || D[bwagpu_s::DF_NRAW].ensure((size_t)n * 4 + 16) || D[bwagpu_s::DF_CNT].ensure((size_t)n * 4 + 16) || D[bwagpu_s::DF_FORM].ensure((size_t)n * 4 + 16) ||
 		D[bwagpu_s::DF_BLOB].ensure(((size_t)F.tot + 8) * SLOT_BLOB_BYTES) || D[bwagpu_s::DF_DPH].ensure(dp_bytes) || D[bwagpu_s::DF_DPE].ensure(dp_bytes) || D[bwagpu_s::DF_CTR].ensure(sizeof(Counters))) {
 		h->err = "hipMalloc failed (dedup_flat)"; return BWAGPU_ENOMEM;
 	}
-	if (n_bases) HIPCHK(h, hipMemcpyAsync(D[bwagpu_s::DF_SEQ].p, seqs, (size_t)n_bases, hipMemcpyHostToDevice, h->stream));
-	HIPCHK(h, hipMemcpyAsync(D[bwagpu_s::DF_SEQOFF].p, seq_off, ((size_t)n + 1) * 8, hipMemcpyHostToDevice, h->stream));
+	if (int rc = R.upload(h, "dedup_flat")) return rc;      // (this call's wait below covers the copies)
 	if (F.tot) HIPCHK(h, hipMemcpyAsync(D[bwagpu_s::DF_REGS].p, regs, (size_t)F.tot * sizeof(bwagpu_alnreg_t), hipMemcpyHostToDevice, h->stream));
 	HIPCHK(h, hipMemcpyAsync(D[bwagpu_s::DF_REGOFF].p, F.off.data(), ((size_t)n + 1) * 8, hipMemcpyHostToDevice, h->stream));
 	HIPCHK(h, hipMemcpyAsync(D[bwagpu_s::DF_NRAW].p, counts, (size_t)n * 4, hipMemcpyHostToDevice, h->stream));
@@ -1891,7 +1910,7 @@ extern "C" int bwagpu_dedup_flat(bwagpu_t *h, const bwagpu_opt_t *opt, int n_rea
 	HIPCHK(h, wait_stream(h));      // (the caller's arrays are pageable)
 	Batch B; memset(&B, 0, sizeof B);
 	B.n_reads = n; B.max_len = max_len; B.stats = h->stats_on;
-	B.seq = D[bwagpu_s::DF_SEQ].as<u8>(); B.off = D[bwagpu_s::DF_SEQOFF].as<i64>(); B.ctr = D[bwagpu_s::DF_CTR].as<Counters>();
+	B.seq = h->d_pf_seq.as<u8>(); B.off = h->d_pf_seqoff.as<i64>(); B.ctr = D[bwagpu_s::DF_CTR].as<Counters>();
 	B.regs = D[bwagpu_s::DF_REGS].as<bwagpu_alnreg_t>(); B.reg_cap = F.tot; B.reg_off = D[bwagpu_s::DF_REGOFF].as<i64>();
 	B.reg_n_raw = D[bwagpu_s::DF_NRAW].as<i32>(); B.reg_n = D[bwagpu_s::DF_CNT].as<i32>(); B.regs_raw = nullptr;
 	// the sorts' key scratch (dev_sort_regs_by_key): read i's block of the blob begins at slot reg_off[i] and has counts[i] slots, one 64-byte chain record -- room for a RegKey -- each
@@ -2516,30 +2535,6 @@ extern "C" int bwagpu_batch_rescue(bwagpu_t *h, const bwagpu_opt_t *opt, const b
 	return rescue_run(h, opt, pes, lists_of_batch(h, id0), h->d_seq.as<u8>(), h->d_off.as<i64>(), counts, regs, src, n_regs, rescue, pri, n_pri, pairs, kernel_ms);
 }
 
-// What bwagpu_rescue_flat and bwagpu_sampe_flat require of the caller's reads and lists, and their upload: the sequences into RS_SEQ / RS_SEQOFF, the lists through F into L.
-// The caller holds the handle's BusyGuard and has set the device.  (`what` names the call in an error text.)
-static bool flat_pairs_ok(const bwagpu_t *h, int n_pairs, const uint8_t *seqs, const int64_t *off, const int32_t *counts_in, const bwagpu_alnreg_t *regs_in, FlatLists &F)
-{
-	const int n_reads = 2 * n_pairs;
-	for (int i = 0; i < n_reads; ++i) if (off[i + 1] < off[i] || off[i] < 0 || off[i + 1] - off[i] > 0x3fffffff) return false;
-	if (!F.scan(h, (size_t)n_reads, counts_in, regs_in, counts_in)) return false;
-	const i64 n_bases = n_reads ? off[n_reads] : 0;
-	for (i64 k = n_reads ? off[0] : 0; k < n_bases; ++k) if (seqs[k] > 4) return false;
-	return true;
-}
-static int flat_pairs_upload(bwagpu_t *h, const char *what, int n_pairs, const uint8_t *seqs, const int64_t *off, const int32_t *counts_in, const bwagpu_alnreg_t *regs_in, const int64_t *ids, FlatLists &F, RegLists &L)
-{
-	const int n_reads = 2 * n_pairs;
-	const i64 n_bases = n_reads ? off[n_reads] : 0;
-	DevBuf *D = h->d_rs;
-	if (n_reads) {      // the sequences and their offsets (the caller's arrays, in the stream ahead of the lists: upload() waits)
-		if (D[bwagpu_s::RS_SEQ].ensure((size_t)(n_bases ? n_bases : 1)) || D[bwagpu_s::RS_SEQOFF].ensure(((size_t)n_reads + 1) * 8)) { h->err = std::string("hipMalloc failed (") + what + ")"; return BWAGPU_ENOMEM; }
-		if (n_bases) HIPCHK(h, hipMemcpyAsync(D[bwagpu_s::RS_SEQ].p, seqs, (size_t)n_bases, hipMemcpyHostToDevice, h->stream));
-		HIPCHK(h, hipMemcpyAsync(D[bwagpu_s::RS_SEQOFF].p, off, ((size_t)n_reads + 1) * 8, hipMemcpyHostToDevice, h->stream));
-	}
-	return F.upload(h, what, counts_in, regs_in, ids, (size_t)n_reads, L);
-}
-
 extern "C" int bwagpu_rescue_flat(bwagpu_t *h, const bwagpu_opt_t *opt, const bwagpu_pestat_t pes[4], int n_pairs, const uint8_t *seqs, const int64_t *off, const int32_t *counts_in,
 								  const bwagpu_alnreg_t *regs_in, const int64_t *ids, int32_t *counts, bwagpu_alnreg_t **regs, int32_t **src, int64_t *n_regs, bwagpu_rescue_t **rescue,
 								  bwagpu_primary_t **pri, int32_t *n_pri, bwagpu_pair_t **pairs, float *kernel_ms)
@@ -2547,12 +2542,13 @@ extern "C" int bwagpu_rescue_flat(bwagpu_t *h, const bwagpu_opt_t *opt, const bw
 	if (!h || !opt || !pes || n_pairs < 0 || n_pairs > 0x1fffffff || !regs || !src || !n_regs || !rescue) return BWAGPU_EINVAL;
 	if (n_pairs > 0 && (!seqs || !off || !counts_in || !counts || ((pri || pairs) && !ids))) return BWAGPU_EINVAL;
 	if (opt->e_del <= 0 || opt->e_ins <= 0 || (pairs && (opt->flag & 0x800 /* MEM_F_PRIMARY5 */))) return BWAGPU_EINVAL;
-	FlatLists F; RegLists L;
-	if (!flat_pairs_ok(h, n_pairs, seqs, off, counts_in, regs_in, F)) return BWAGPU_EINVAL;
+	FlatReads R; FlatLists F; RegLists L;
+	if (!R.scan(h, "bwagpu_rescue_flat", 2 * (size_t)n_pairs, seqs, off) || !F.scan(h, 2 * (size_t)n_pairs, counts_in, regs_in, counts_in) || !R.codes_ok(h, "bwagpu_rescue_flat")) return BWAGPU_EINVAL;
 	const BusyGuard busy(h->ibuf->busy);
 	HIPCHK(h, hipSetDevice(h->device));
-	const int rc = flat_pairs_upload(h, "rescue", n_pairs, seqs, off, counts_in, regs_in, ids, F, L);
-	return rc != BWAGPU_OK ? rc : rescue_run(h, opt, pes, L, h->d_rs[bwagpu_s::RS_SEQ].as<u8>(), h->d_rs[bwagpu_s::RS_SEQOFF].as<i64>(), counts, regs, src, n_regs, rescue, pri, n_pri, pairs, kernel_ms);
+	if (int rc = R.upload(h, "rescue")) return rc;
+	const int rc = F.upload(h, "rescue", counts_in, regs_in, ids, F.n, L);
+	return rc != BWAGPU_OK ? rc : rescue_run(h, opt, pes, L, h->d_pf_seq.as<u8>(), h->d_pf_seqoff.as<i64>(), counts, regs, src, n_regs, rescue, pri, n_pri, pairs, kernel_ms);
 }
 
 // ---- insert-size statistics on the device (dev_pestat.h) ------------------------------------------------------------------------------------------
@@ -2746,6 +2742,13 @@ static int alns_run(bwagpu_t *h, const bwagpu_opt_t *opt, const RegLists &L, i64
 	return BWAGPU_OK;
 }
 
+// the CIGAR records and operation array of the last bwagpu_batch_cigars, the batch's read offsets
+static AlnIn alnin_of_batch(const bwagpu_t *h)
+{
+	AlnIn I = {}; I.cigs = h->d_cigs.as<bwagpu_cigar_t>(); I.ops = h->d_cig_ext.as<u32>(); I.n_ops = h->cig_ext_n; I.seq_off = h->d_off.as<i64>();
+	return I;
+}
+
 extern "C" int bwagpu_batch_alns(bwagpu_t *h, const bwagpu_opt_t *opt, int64_t id0, bwagpu_aln_t **alns, int64_t *n_alns, int32_t *n_aln, bwagpu_primary_t **pri, int32_t *n_pri, float *kernel_ms)
 {
 	if (!h || !opt || !h->ran || !h->downloaded || h->cig_ext_n < 0 || !alns || !n_alns) return BWAGPU_EINVAL;
@@ -2754,10 +2757,37 @@ extern "C" int bwagpu_batch_alns(bwagpu_t *h, const bwagpu_opt_t *opt, int64_t i
 	HIPCHK(h, hipSetDevice(h->device));
 	*alns = nullptr; *n_alns = 0; if (pri) *pri = nullptr;
 	const RegLists L = lists_of_batch(h, id0);
-	AlnIn I = {}; I.cigs = h->d_cigs.as<bwagpu_cigar_t>(); I.ops = h->d_cig_ext.as<u32>(); I.n_ops = h->cig_ext_n; I.seq_off = h->d_off.as<i64>();
-	const int rc = alns_run(h, opt, L, batch_log_need(h, opt), I, alns, n_aln, pri, n_pri, kernel_ms);
+	const int rc = alns_run(h, opt, L, batch_log_need(h, opt), alnin_of_batch(h), alns, n_aln, pri, n_pri, kernel_ms);
 	if (rc == BWAGPU_OK) *n_alns = L.tot;
 	return rc;
+}
+
+// The CIGAR records of a *_flat call, one per region (tot in all), and the operation array of n_ops words they point into.  flat_cigs_ok(): an n_cigar of
+// -1 .. 32768, operations -- and, with_md, MD strings -- that are kept in the array inside it; false: BWAGPU_EINVAL (`what` names the entry point in the text).
+// flat_cigs_upload(): into d_aln_cigs / d_aln_ops and I, enqueued only: the wait is the caller's.
+static bool flat_cigs_ok(bwagpu_t *h, const char *what, const bwagpu_cigar_t *cigs, i64 tot, i64 n_ops, bool with_md)
+{
+	if (tot > 0 && !cigs) return false;
+	for (i64 k = 0; k < tot; ++k) {
+		const bwagpu_cigar_t &c = cigs[k];
+		if (c.n_cigar < -1 || c.n_cigar > 32768) { h->err = std::string(what) + ": n_cigar outside [-1, 32768]"; return false; }
+		if (c.n_cigar > 6) {
+			const u64 at = (u64)c.cigar[1] << 32 | c.cigar[0];
+			if (at > (u64)n_ops || (u64)c.n_cigar > (u64)n_ops - at) { h->err = std::string(what) + ": a CIGAR record points outside the operation array"; return false; }
+		}
+		if (with_md && c.n_cigar >= 0 && (c.md_len < 0 || (c.md_len > 8 && (c.md > (u64)n_ops || ((u64)c.md_len + 3) / 4 > (u64)n_ops - c.md)))) {
+			h->err = std::string(what) + ": an MD string outside the operation array"; return false;
+		}
+	}
+	return true;
+}
+static int flat_cigs_upload(bwagpu_t *h, const char *tag, const bwagpu_cigar_t *cigs, i64 tot, const uint32_t *ops, i64 n_ops, AlnIn &I)
+{
+	if (h->d_aln_cigs.ensure((size_t)(tot ? tot : 1) * sizeof(bwagpu_cigar_t)) || h->d_aln_ops.ensure((size_t)(n_ops ? n_ops : 1) * 4)) { h->err = std::string("hipMalloc failed (") + tag + ")"; return BWAGPU_ENOMEM; }
+	if (tot) HIPCHK(h, hipMemcpyAsync(h->d_aln_cigs.p, cigs, (size_t)tot * sizeof(bwagpu_cigar_t), hipMemcpyHostToDevice, h->stream));
+	if (n_ops) HIPCHK(h, hipMemcpyAsync(h->d_aln_ops.p, ops, (size_t)n_ops * 4, hipMemcpyHostToDevice, h->stream));
+	I.cigs = h->d_aln_cigs.as<bwagpu_cigar_t>(); I.ops = h->d_aln_ops.as<u32>();
+	return BWAGPU_OK;
 }
 
 extern "C" int bwagpu_alns_flat(bwagpu_t *h, const bwagpu_opt_t *opt, int n_reads, const int32_t *counts, const bwagpu_alnreg_t *regs, const int64_t *ids, const int32_t *read_len,
@@ -2767,31 +2797,19 @@ extern "C" int bwagpu_alns_flat(bwagpu_t *h, const bwagpu_opt_t *opt, int n_read
 	if (opt->flag & 0x800 /* MEM_F_PRIMARY5 */) return BWAGPU_EINVAL;
 	FlatLists F; RegLists L;
 	if (!F.scan(h, (size_t)n_reads, counts, regs, counts)) return BWAGPU_EINVAL;
-	if (F.tot > 0 && !cigs) return BWAGPU_EINVAL;
 	for (int i = 0; i < n_reads; ++i) if (read_len[i] < 0) return BWAGPU_EINVAL;
-	for (i64 k = 0; k < F.tot; ++k) {
-		const bwagpu_cigar_t &c = cigs[k];
-		if (c.n_cigar < -1 || c.n_cigar > 32768) { h->err = "bwagpu_alns_flat: n_cigar outside [-1, 32768]"; return BWAGPU_EINVAL; }
-		if (c.n_cigar > 6) {
-			const u64 at = (u64)c.cigar[1] << 32 | c.cigar[0];
-			if (at > (u64)n_ops || (u64)c.n_cigar > (u64)n_ops - at) { h->err = "bwagpu_alns_flat: a CIGAR record points outside the operation array"; return BWAGPU_EINVAL; }
-		}
-	}
+	if (!flat_cigs_ok(h, "bwagpu_alns_flat", cigs, F.tot, n_ops, false)) return BWAGPU_EINVAL;
 	const BusyGuard busy(h->ibuf->busy);
 	HIPCHK(h, hipSetDevice(h->device));
 	*alns = nullptr; if (pri) *pri = nullptr;
-	const int rc = F.upload(h, "alns", counts, regs, ids, (size_t)n_reads, L);
-	if (rc != BWAGPU_OK) return rc;
+	if (int rc = F.upload(h, "alns", counts, regs, ids, (size_t)n_reads, L)) return rc;
 	AlnIn I = {}; I.n_ops = n_ops;
 	if (F.tot > 0) {
-		if (h->d_aln_cigs.ensure((size_t)F.tot * sizeof(bwagpu_cigar_t)) || h->d_aln_ops.ensure((size_t)(n_ops ? n_ops : 1) * 4) || h->d_aln_len.ensure((size_t)n_reads * 4)) {
-			h->err = "hipMalloc failed (alns)"; return BWAGPU_ENOMEM;
-		}
-		HIPCHK(h, hipMemcpyAsync(h->d_aln_cigs.p, cigs, (size_t)F.tot * sizeof(bwagpu_cigar_t), hipMemcpyHostToDevice, h->stream));
-		if (n_ops) HIPCHK(h, hipMemcpyAsync(h->d_aln_ops.p, ops, (size_t)n_ops * 4, hipMemcpyHostToDevice, h->stream));
+		if (int rc = flat_cigs_upload(h, "alns", cigs, F.tot, ops, n_ops, I)) return rc;
+		if (h->d_aln_len.ensure((size_t)n_reads * 4)) { h->err = "hipMalloc failed (alns)"; return BWAGPU_ENOMEM; }
 		HIPCHK(h, hipMemcpyAsync(h->d_aln_len.p, read_len, (size_t)n_reads * 4, hipMemcpyHostToDevice, h->stream));
 		HIPCHK(h, wait_stream(h));      // (the caller's arrays are pageable: the copies are done when they return, the wait keeps that independent of the runtime)
-		I.cigs = h->d_aln_cigs.as<bwagpu_cigar_t>(); I.ops = h->d_aln_ops.as<u32>(); I.read_len = h->d_aln_len.as<i32>();
+		I.read_len = h->d_aln_len.as<i32>();
 	}
 	return alns_run(h, opt, L, pri_log_need(counts, regs, n_reads), I, alns, n_aln, pri, n_pri, kernel_ms);
 }
@@ -2923,9 +2941,7 @@ extern "C" int bwagpu_batch_sam(bwagpu_t *h, const bwagpu_opt_t *opt, int64_t id
 	if (int rc = sam_in_check(h, h->n_reads, in, "bwagpu_batch_sam")) return rc;
 	const BusyGuard busy(h->ibuf->busy);
 	HIPCHK(h, hipSetDevice(h->device));
-	const RegLists L = lists_of_batch(h, id0);
-	AlnIn I = {}; I.cigs = h->d_cigs.as<bwagpu_cigar_t>(); I.ops = h->d_cig_ext.as<u32>(); I.n_ops = h->cig_ext_n; I.seq_off = h->d_off.as<i64>();
-	return sam_run(h, opt, L, batch_log_need(h, opt), I, h->d_seq.as<u8>(), h->d_off.as<i64>(), h->n_bases, in, out);
+	return sam_run(h, opt, lists_of_batch(h, id0), batch_log_need(h, opt), alnin_of_batch(h), h->d_seq.as<u8>(), h->d_off.as<i64>(), h->n_bases, in, out);
 }
 
 extern "C" int bwagpu_sam_flat(bwagpu_t *h, const bwagpu_opt_t *opt, int n_reads, const uint8_t *seqs, const int64_t *seq_off, const int32_t *counts, const bwagpu_alnreg_t *regs,
@@ -2937,40 +2953,20 @@ extern "C" int bwagpu_sam_flat(bwagpu_t *h, const bwagpu_opt_t *opt, int n_reads
 	if (int rc = sam_in_check(h, n_reads, in, "bwagpu_sam_flat")) return rc;
 	FlatLists F; RegLists L;
 	if (!F.scan(h, (size_t)n_reads, counts, regs, counts)) return BWAGPU_EINVAL;
-	if (F.tot > 0 && !cigs) return BWAGPU_EINVAL;
-	for (int i = 0; i < n_reads; ++i)
-		if (seq_off[0] != 0 || seq_off[i + 1] < seq_off[i] || seq_off[i + 1] - seq_off[i] > 0x3fffffff) { h->err = "bwagpu_sam_flat: offsets that do not ascend"; return BWAGPU_EINVAL; }
-	const i64 n_bases = n_reads ? seq_off[n_reads] : 0;
-	if (n_bases > 0 && !seqs) return BWAGPU_EINVAL;
-	for (i64 k = 0; k < F.tot; ++k) {
-		const bwagpu_cigar_t &c = cigs[k];
-		if (c.n_cigar < -1 || c.n_cigar > 32768) { h->err = "bwagpu_sam_flat: n_cigar outside [-1, 32768]"; return BWAGPU_EINVAL; }
-		if (c.n_cigar > 6) {
-			const u64 at = (u64)c.cigar[1] << 32 | c.cigar[0];
-			if (at > (u64)n_ops || (u64)c.n_cigar > (u64)n_ops - at) { h->err = "bwagpu_sam_flat: a CIGAR record points outside the operation array"; return BWAGPU_EINVAL; }
-		}
-		if (c.n_cigar >= 0 && (c.md_len < 0 || (c.md_len > 8 && (c.md > (u64)n_ops || ((u64)c.md_len + 3) / 4 > (u64)n_ops - c.md)))) {
-			h->err = "bwagpu_sam_flat: an MD string outside the operation array"; return BWAGPU_EINVAL;
-		}
-	}
+	FlatReads R;      // (no codes_ok(): the formatter has a character for every code, sam_base in dev_samtext.h)
+	if (!R.scan(h, "bwagpu_sam_flat", (size_t)n_reads, seqs, seq_off) || (R.first != 0 && !R.bad_offsets(h, "bwagpu_sam_flat"))) return BWAGPU_EINVAL;      // R.first: this call's reads begin at seqs[0] (the pair calls take any first offset)
+	if (!flat_cigs_ok(h, "bwagpu_sam_flat", cigs, F.tot, n_ops, true)) return BWAGPU_EINVAL;
 	const BusyGuard busy(h->ibuf->busy);
 	HIPCHK(h, hipSetDevice(h->device));
-	const int rc = F.upload(h, "sam", counts, regs, ids, (size_t)n_reads, L);
-	if (rc != BWAGPU_OK) return rc;
+	if (int rc = R.upload(h, "sam")) return rc;
+	if (int rc = F.upload(h, "sam", counts, regs, ids, (size_t)n_reads, L)) return rc;
 	AlnIn I = {}; I.n_ops = n_ops;
-	DevBuf &d_seq = h->d_st[bwagpu_s::ST_SEQ], &d_seqoff = h->d_st[bwagpu_s::ST_SEQOFF];
 	if (n_reads > 0) {
-		if (h->d_aln_cigs.ensure((size_t)(F.tot ? F.tot : 1) * sizeof(bwagpu_cigar_t)) || h->d_aln_ops.ensure((size_t)(n_ops ? n_ops : 1) * 4) || d_seq.ensure((size_t)n_bases + 1) || d_seqoff.ensure(((size_t)n_reads + 1) * 8)) {
-			h->err = "hipMalloc failed (sam)"; return BWAGPU_ENOMEM;
-		}
-		if (F.tot) HIPCHK(h, hipMemcpyAsync(h->d_aln_cigs.p, cigs, (size_t)F.tot * sizeof(bwagpu_cigar_t), hipMemcpyHostToDevice, h->stream));
-		if (n_ops) HIPCHK(h, hipMemcpyAsync(h->d_aln_ops.p, ops, (size_t)n_ops * 4, hipMemcpyHostToDevice, h->stream));
-		if (n_bases) HIPCHK(h, hipMemcpyAsync(d_seq.p, seqs, (size_t)n_bases, hipMemcpyHostToDevice, h->stream));
-		HIPCHK(h, hipMemcpyAsync(d_seqoff.p, seq_off, ((size_t)n_reads + 1) * 8, hipMemcpyHostToDevice, h->stream));
+		if (int rc = flat_cigs_upload(h, "sam", cigs, F.tot, ops, n_ops, I)) return rc;
 		HIPCHK(h, wait_stream(h));      // (the caller's arrays are pageable, as in bwagpu_alns_flat)
-		I.cigs = h->d_aln_cigs.as<bwagpu_cigar_t>(); I.ops = h->d_aln_ops.as<u32>(); I.seq_off = d_seqoff.as<i64>();
+		I.seq_off = h->d_pf_seqoff.as<i64>();
 	}
-	return sam_run(h, opt, L, pri_log_need(counts, regs, n_reads), I, d_seq.as<u8>(), d_seqoff.as<i64>(), n_bases, in, out);
+	return sam_run(h, opt, L, pri_log_need(counts, regs, n_reads), I, h->d_pf_seq.as<u8>(), h->d_pf_seqoff.as<i64>(), R.n_bases, in, out);
 }
 
 // ---- a read pair decided on the device (dev_sampe.h) ----------------------------------------------------------------------------------------------------
@@ -3121,14 +3117,13 @@ extern "C" int bwagpu_sampe_flat(bwagpu_t *h, const bwagpu_opt_t *opt, const bwa
 	if (!h || !opt || !pes || n_pairs < 0 || n_pairs > 0x1fffffff || !out) return BWAGPU_EINVAL;
 	if (n_pairs > 0 && (!seqs || !off || !counts_in || !counts || !ids)) return BWAGPU_EINVAL;
 	if (opt->e_del <= 0 || opt->e_ins <= 0 || (opt->flag & 0x800 /* MEM_F_PRIMARY5 */)) return BWAGPU_EINVAL;
-	FlatLists F; RegLists L;
-	if (!flat_pairs_ok(h, n_pairs, seqs, off, counts_in, regs_in, F)) return BWAGPU_EINVAL;
-	int max_len = 0;
-	for (int i = 0; i < 2 * n_pairs; ++i) max_len = std::max(max_len, (int)(off[i + 1] - off[i]));
+	FlatReads R; FlatLists F; RegLists L;
+	if (!R.scan(h, "bwagpu_sampe_flat", 2 * (size_t)n_pairs, seqs, off) || !F.scan(h, 2 * (size_t)n_pairs, counts_in, regs_in, counts_in) || !R.codes_ok(h, "bwagpu_sampe_flat")) return BWAGPU_EINVAL;
 	const BusyGuard busy(h->ibuf->busy);
 	HIPCHK(h, hipSetDevice(h->device));
-	const int rc = flat_pairs_upload(h, "sampe", n_pairs, seqs, off, counts_in, regs_in, ids, F, L);
-	return rc != BWAGPU_OK ? rc : sampe_run(h, opt, pes, L, h->d_rs[bwagpu_s::RS_SEQ].as<u8>(), h->d_rs[bwagpu_s::RS_SEQOFF].as<i64>(), max_len, n_pairs ? off[2 * n_pairs] - off[0] : 0, counts, out);
+	if (int rc = R.upload(h, "sampe")) return rc;
+	const int rc = F.upload(h, "sampe", counts_in, regs_in, ids, F.n, L);
+	return rc != BWAGPU_OK ? rc : sampe_run(h, opt, pes, L, h->d_pf_seq.as<u8>(), h->d_pf_seqoff.as<i64>(), R.max_len, R.n_bases - R.first, counts, out);
 }
 
 // ---- paired-end SAM text on the device (dev_samtext_pe.h) ---------------------------------------------------------------------------------------------
@@ -3215,16 +3210,14 @@ extern "C" int bwagpu_sam_pe_flat(bwagpu_t *h, const bwagpu_opt_t *opt, const bw
 	if (opt->e_del <= 0 || opt->e_ins <= 0 || (opt->flag & 0x800 /* MEM_F_PRIMARY5 */)) return BWAGPU_EINVAL;
 	if (int rc = sam_in_check(h, 2 * n_pairs, in, "bwagpu_sam_pe_flat")) return rc;
 	if (int rc = sam_pe_names_check(h, n_pairs, in, "bwagpu_sam_pe_flat")) return rc;
-	FlatLists F; RegLists L;
-	if (!flat_pairs_ok(h, n_pairs, seqs, off, counts_in, regs_in, F)) return BWAGPU_EINVAL;
-	int max_len = 0;
-	for (int i = 0; i < 2 * n_pairs; ++i) max_len = std::max(max_len, (int)(off[i + 1] - off[i]));
+	FlatReads R; FlatLists F; RegLists L;
+	if (!R.scan(h, "bwagpu_sam_pe_flat", 2 * (size_t)n_pairs, seqs, off) || !F.scan(h, 2 * (size_t)n_pairs, counts_in, regs_in, counts_in) || !R.codes_ok(h, "bwagpu_sam_pe_flat")) return BWAGPU_EINVAL;
 	const BusyGuard busy(h->ibuf->busy);
 	HIPCHK(h, hipSetDevice(h->device));
-	const int rc = flat_pairs_upload(h, "sam_pe", n_pairs, seqs, off, counts_in, regs_in, ids, F, L);
+	if (int rc = R.upload(h, "sam_pe")) return rc;
+	const int rc = F.upload(h, "sam_pe", counts_in, regs_in, ids, F.n, L);
 	if (rc != BWAGPU_OK) return rc;
-	return sam_pe_run(h, opt, pes, L, h->d_rs[bwagpu_s::RS_SEQ].as<u8>(), h->d_rs[bwagpu_s::RS_SEQOFF].as<i64>(), max_len, n_pairs ? off[2 * n_pairs] - off[0] : 0, n_pairs ? off[2 * n_pairs] : 0,
-					  in, counts, pe, out);
+	return sam_pe_run(h, opt, pes, L, h->d_pf_seq.as<u8>(), h->d_pf_seqoff.as<i64>(), R.max_len, R.n_bases - R.first, R.n_bases, in, counts, pe, out);
 }
 
 extern "C" int bwagpu_align_flat(bwagpu_t *h, const bwagpu_opt_t *opt, int n, const uint8_t *seqs, const int64_t *off,
