@@ -63,7 +63,7 @@ EXPORTS = [
     "bwagpu_batch_primary", "bwagpu_primary_flat", "bwagpu_primary_limits", "bwagpu_batch_pair", "bwagpu_pair_flat", "bwagpu_pair_limits", "bwagpu_batch_rescue", "bwagpu_rescue_flat", "bwagpu_rescue_limits",
     "bwagpu_batch_pestat", "bwagpu_pestat_flat", "bwagpu_batch_pestat_hist", "bwagpu_pestat_finish", "bwagpu_pestat_limits",
     "bwagpu_batch_alns", "bwagpu_alns_flat", "bwagpu_alns_limits", "bwagpu_aln_size",
-    "bwagpu_cigars_flat", "bwagpu_cigar_limits", "bwagpu_dedup_flat", "bwagpu_dedup_limits",
+    "bwagpu_cigars_flat", "bwagpu_cigar_limits", "bwagpu_dedup_flat", "bwagpu_dedup_limits", "bwagpu_ext_limits",
     "bwagpu_batch_sampe", "bwagpu_sampe_flat", "bwagpu_sampe_limits", "bwagpu_sampe_size",
     "bwagpu_set_contig_names", "bwagpu_batch_sam", "bwagpu_sam_flat", "bwagpu_sam_limits",
     "bwagpu_trim", "bwagpu_set_option", "bwagpu_get_option", "bwagpu_set_default_option", "bwagpu_clear_default_options", "bwagpu_option_name",
@@ -107,6 +107,7 @@ def load_library(path: str | None = None) -> C.CDLL:
     L.bwagpu_cigar_limits.restype = None
     L.bwagpu_dedup_flat.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 8
     L.bwagpu_dedup_limits.restype = None
+    L.bwagpu_ext_limits.restype = None
     L.bwagpu_tap_intervals.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.bwagpu_tap_chains.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.bwagpu_tap_regs_raw.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -360,6 +361,12 @@ class BwaGpu:
         out = (C.c_int32 * 8)()
         self.L.bwagpu_dedup_limits(out)
         return dict(zip(("heavy", "stage", "net", "keysort_min", "scan_block", "draw", "ring_min", "lds_per_reg"), list(out)))
+
+    def ext_limits(self) -> dict:
+        """bwagpu_ext_limits: the switch points of the extension stage (mem_chain2aln on the device), as compiled."""
+        out = (C.c_int32 * 6)()
+        self.L.bwagpu_ext_limits(out)
+        return dict(zip(("sort_lane_max", "kept_short", "kept_ring", "covered_step", "wave_max_len", "ring_max"), list(out)))
 
     def matesw(self, opt: MemOpt, pes: np.ndarray):
         """bwagpu_batch_matesw: precomputed mate-rescue alignments (MATESW_DTYPE) for the last download(); pes = PES_DTYPE[4]."""

@@ -860,6 +860,12 @@ static int sc_max_all(const bwagpu_opt_t *opt) { int m = 1; for (int k = 0; k < 
 static const int BLOCK = 256;
 static const int MAX_RESIDENT_THREADS = 256 * 2048;   // 256 CUs x 32 waves x 64 lanes
 static const int WAVE_EXT_MAX_LEN = 1100;
+static const int EXT_RING_MAX = 2048;      // the widest ring of {H,E} columns k_extend_wave<true> takes (bands beyond it: k_extend)
+// the extension stage's switch points, as compiled (dev_extw.h, bwagpu_batch_run)
+extern "C" void bwagpu_ext_limits(int32_t out[6])
+{
+	out[0] = CHAIN_SORT_LANE_MAX; out[1] = EXT_KEPT_SHORT * 64; out[2] = EXT_KEPT_RING * 64; out[3] = SEED_COVERED_STEP; out[4] = WAVE_EXT_MAX_LEN; out[5] = EXT_RING_MAX;
+}
 static const int SEED_LDS_ENT = 10;                     // 10 x 16 B x 256 lanes = 40 KiB of LDS per block -> 4 blocks (16 waves) per CU; measured best of {4,7,10,15}               // 4 waves x (8+5) B/column must fit the 64 KiB dynamic-LDS limit
 
 // first guess of a batch's arena sizes from its shape (n_reads, n_bases, max_len); grown on overflow
@@ -1364,7 +1370,7 @@ extern "C" int bwagpu_batch_run(bwagpu_t *h, const bwagpu_opt_t *opt)
 			}
 			if (occ == 4) hipLaunchKernelGGL((k_extend_wave<false, 4>), g, block, (size_t)lds_wave * 4, h->stream, h->ix, *opt, B, lds_wave, 0);
 			else hipLaunchKernelGGL((k_extend_wave<false, 6>), g, block, (size_t)lds_wave * 4, h->stream, h->ix, *opt, B, lds_wave, 0);
-		} else if (max_score < (1 << 24) && ring_cols <= 2048) {
+		} else if (max_score < (1 << 24) && ring_cols <= EXT_RING_MAX) {
 			// the band's columns only: independent of the read length
 			const int lds_wave = 8 * ring_cols + 64;      // (the ring, the scoring matrix, the stats runs' counters)
 			int wpb = 4; while (wpb > 1 && lds_wave * wpb > 65536) wpb >>= 1;

@@ -730,12 +730,13 @@ DEVFN void wave_sort_u64(u64 *a, int n)
 }
 
 // "is the seed already covered by an earlier alignment of this read?" (bwamem.c:697-713) is an existence query -- the reference only uses
-// whether its scan stopped early -- so 64 earlier regions are tested per step
+// whether its scan stopped early -- so SEED_COVERED_STEP earlier regions (a lane each) are tested per step
+#define SEED_COVERED_STEP 64
 DEVFN bool wave_seed_covered(const bwagpu_opt_t &opt, const bwagpu_seed_t &s, int l_query, const bwagpu_alnreg_t *av, int n_av)
 {
 	const int lane = opaque_lane();
 	bool covered = false;
-	for (int base = 0; base < n_av && !covered; base += 64) {
+	for (int base = 0; base < n_av && !covered; base += SEED_COVERED_STEP) {
 		const int ii = base + lane;
 		bool hit = false;
 		if (ii < n_av) {
@@ -808,6 +809,9 @@ DEVFN void chain_sort_wave(const bwagpu_seed_t *seeds, u64 *srt, int n)
 	}
 }
 
+// registers per lane for the seeds a chain has extended (ext_chain_wave's list for the "other diagonal" rule): the list holds 64 times as many
+#define EXT_KEPT_SHORT 1
+#define EXT_KEPT_RING 2
 struct ExtPlan;
 // an extension k_ext_pack has answered ahead of time (dev_extp.h; null / false: none)
 DEVFN bool plan_result(const ExtPlan *plan, bool right, ExtRes &x);
@@ -828,7 +832,7 @@ template <bool RING> __device__ void ext_chain_wave(const DevIndex &ix, const bw
 	// zeroed entries (bwamem.c:716-717) -- for a long read's chain of ~2500 seeds, nearly all of them skipped, that walk was n^2 / 64 steps
 	// of two dependent global loads each, most of the long-read kernel's time; the extended ones are a handful.  More than KS * 64 of them: the
 	// chain falls back to the walk (srt[] is kept up to date for that).
-	constexpr int KS = RING ? 2 : 1;
+	constexpr int KS = RING ? EXT_KEPT_RING : EXT_KEPT_SHORT;
 	int kq[KS], kl[KS]; i64 kr[KS]; int n_kept = 0; bool walk = false;
 	#pragma unroll
 	for (int t_ = 0; t_ < KS; ++t_) { kq[t_] = 0; kl[t_] = 0; kr[t_] = 0; }

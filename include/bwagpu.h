@@ -298,6 +298,11 @@ int bwagpu_dedup_flat(bwagpu_t *h, const bwagpu_opt_t *opt, int n_reads, const u
  * sorts move keys), the regions dedup_read_par's scan takes at once, the reads k_dedup draws at once, the smallest ring of the patch alignments,
  * DDP_LDS_PER_REG (LDS bytes per region of dedup_read_par). */
 void bwagpu_dedup_limits(int32_t out[8]);
+/* The switch points of the extension stage (mem_chain2aln), as compiled: out[0] seeds up to which one lane sorts a chain's seeds (longer chains: the wavefront's
+ * sorting network), [1] / [2] extended seeds of a chain kept in registers for the "other diagonal" rule by the short-read / the ring form (one more: the walk
+ * over the sorted keys), [3] earlier regions of the read tested per step of the "already covered" rule, [4] the longest read of a batch that takes the
+ * short-read form, [5] the widest ring of the ring form (4 w + 132 columns, rounded up to a power of two, beyond it: the lane-per-read kernel). */
+void bwagpu_ext_limits(int32_t out[6]);
 
 /* After bwagpu_batch_download of a paired batch (mates interleaved 2i, 2i+1): the local alignments mem_matesw
  * (bwamem_pair.c:137-206) would run for every (anchor region, orientation) that the downloaded region lists do not already
