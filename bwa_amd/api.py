@@ -63,7 +63,7 @@ EXPORTS = [
     "bwagpu_batch_primary", "bwagpu_primary_flat", "bwagpu_primary_limits", "bwagpu_batch_pair", "bwagpu_pair_flat", "bwagpu_pair_limits", "bwagpu_batch_rescue", "bwagpu_rescue_flat", "bwagpu_rescue_limits",
     "bwagpu_batch_pestat", "bwagpu_pestat_flat", "bwagpu_batch_pestat_hist", "bwagpu_pestat_finish", "bwagpu_pestat_limits",
     "bwagpu_batch_alns", "bwagpu_alns_flat", "bwagpu_alns_limits", "bwagpu_aln_size",
-    "bwagpu_cigars_flat", "bwagpu_cigar_limits", "bwagpu_dedup_flat", "bwagpu_dedup_limits", "bwagpu_ext_limits",
+    "bwagpu_cigars_flat", "bwagpu_cigar_limits", "bwagpu_dedup_flat", "bwagpu_dedup_limits", "bwagpu_ext_limits", "bwagpu_seed_limits",
     "bwagpu_batch_sampe", "bwagpu_sampe_flat", "bwagpu_sampe_limits", "bwagpu_sampe_size",
     "bwagpu_set_contig_names", "bwagpu_batch_sam", "bwagpu_sam_flat", "bwagpu_sam_limits",
     "bwagpu_trim", "bwagpu_set_option", "bwagpu_get_option", "bwagpu_set_default_option", "bwagpu_clear_default_options", "bwagpu_option_name",
@@ -108,6 +108,8 @@ def load_library(path: str | None = None) -> C.CDLL:
     L.bwagpu_dedup_flat.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 8
     L.bwagpu_dedup_limits.restype = None
     L.bwagpu_ext_limits.restype = None
+    L.bwagpu_seed_limits.argtypes = [C.c_void_p, C.c_void_p]
+    L.bwagpu_seed_limits.restype = None
     L.bwagpu_tap_intervals.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.bwagpu_tap_chains.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.bwagpu_tap_regs_raw.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -367,6 +369,12 @@ class BwaGpu:
         out = (C.c_int32 * 6)()
         self.L.bwagpu_ext_limits(out)
         return dict(zip(("sort_lane_max", "kept_short", "kept_ring", "covered_step", "wave_max_len", "ring_max"), list(out)))
+
+    def seed_limits(self) -> dict:
+        """bwagpu_seed_limits: the switch points of the seeding stage (mem_collect_intv on the device), as compiled; ptab_depth as in force for this handle's index, lds_ent_run for its last run()."""
+        out = (C.c_int32 * 10)()
+        self.L.bwagpu_seed_limits(self.h, out)
+        return dict(zip(("ptab_max", "ptab_depth", "lds_ent", "rd_lds_max_len", "wave_max_len", "cand_bits", "pub_max", "task_stack_cap", "lane_lds", "lds_ent_run"), list(out)))
 
     def matesw(self, opt: MemOpt, pes: np.ndarray):
         """bwagpu_batch_matesw: precomputed mate-rescue alignments (MATESW_DTYPE) for the last download(); pes = PES_DTYPE[4]."""

@@ -128,7 +128,7 @@ struct bwagpu_s {
 	DevBuf d_heavy;                             // short-read batches: the reads the lane-per-read seeding kernel gave up (their passes 1-2 run as tasks)
 	DevBuf d_p2_tasks; double p2_factor = 1.;   // pass-2 tasks of a short-read batch's heavy reads (grown on overflow bit 5)
 	DevBuf d_vr_tab, d_vr_ovf, d_intv_n3;   // pass 1 of long-read batches as tasks (k_seed<LR>): the reads' first tasks, the list of tasks to redo on full-size stacks, pass 3's entries per read
-	DevBuf d_seq_2b, d_seq_flags; int rd_words = 0;   // per-read 2-bit copies for k_seed's LDS (k_pack_reads2b)
+	DevBuf d_seq_2b, d_seq_flags; int rd_words = 0; int seed_lds_run = 0;   // per-read 2-bit copies for k_seed's LDS (k_pack_reads2b)
 	DevBuf d_pack_off, d_regs_packed, d_pack_read, d_cigs, d_seq, d_seq_nib, d_off, d_ctr, d_tmp_intv, d_intv_n, d_intv_off, d_intv, d_seed_n, d_seed_off;
 	DevBuf d_slot_pos, d_slot_qbeg, d_slot_len, d_slot_rid, d_slot_blob;
 	DevBuf d_order, d_bin_cnt, d_seed_w, d_seed_order, d_chain_n, d_node_off, d_nodes, d_reg_off, d_reg_cap_r, d_reg_n_raw, d_reg_n, d_regs, d_regs_raw, d_dp_h, d_dp_e, d_minhsp;
@@ -868,6 +868,16 @@ extern "C" void bwagpu_ext_limits(int32_t out[6])
 }
 static const int SEED_LDS_ENT = 10;                     // 10 x 16 B x 256 lanes = 40 KiB of LDS per block -> 4 blocks (16 waves) per CU; measured best of {4,7,10,15}               // 4 waves x (8+5) B/column must fit the 64 KiB dynamic-LDS limit
 
+static const int SEED_RD_MAX_LEN = 256;                 // the longest read of a batch whose reads get a 2-bit copy for k_seed's LDS (four 16-byte pieces per read)
+static const int TASK_STACK_DFLT = 128;                 // BiIntv-sized entries of a task lane's spill area beyond PTAB_MAX (option seed_task_stack = 0)
+// the seeding stage's switch points, as compiled and -- the prefix tables' depth -- as in force for the handle's index (h may be null: the option's default)
+static const int SEED_LANE_LDS = 160;                   // LDS bytes per lane of k_seed at four blocks per CU: the read's 2-bit copy first, interval-stack entries with the rest
+extern "C" void bwagpu_seed_limits(const bwagpu_t *h, int32_t out[10])
+{
+	out[0] = PTAB_MAX; out[1] = h ? h->ix.ptab_m : (int32_t)BwagpuConfig().ptab_m; out[2] = SEED_LDS_ENT; out[3] = SEED_RD_MAX_LEN; out[4] = WAVE_EXT_MAX_LEN;
+	out[5] = SEED_CAND_BITS; out[6] = PUB_MAX; out[7] = PTAB_MAX + TASK_STACK_DFLT; out[8] = SEED_LANE_LDS; out[9] = h ? h->seed_lds_run : 0;
+}
+
 // first guess of a batch's arena sizes from its shape (n_reads, n_bases, max_len); grown on overflow
 static void size_arenas(bwagpu_t *h)
 {
@@ -934,7 +944,7 @@ extern "C" int bwagpu_batch_upload(bwagpu_t *h, int n, const uint8_t *seqs, cons
 		hipLaunchKernelGGL(k_pack_reads, dim3((unsigned)(pb < 65536 ? pb : 65536)), dim3(BLOCK), 0, h->stream, P, n_words);
 		HIPCHK(h, hipGetLastError());
 		// reads of up to 256 bases: a 2-bit copy per read for the seeding kernel's LDS
-		h->rd_words = (h->max_len <= 256 && h->cfg.seed_rd_lds != 0) ? (((h->max_len + 15) / 16 + 3) & ~3) : 0;
+		h->rd_words = (h->max_len <= SEED_RD_MAX_LEN && h->cfg.seed_rd_lds != 0) ? (((h->max_len + 15) / 16 + 3) & ~3) : 0;
 		if (h->rd_words) {
 			if (h->d_seq_2b.ensure((size_t)n * h->rd_words * 4 + 64) || h->d_seq_flags.ensure((size_t)n + 16)) { h->err = "hipMalloc failed (reads)"; return BWAGPU_ENOMEM; }
 			HIPCHK(h, hipMemsetAsync(h->d_seq_flags.p, 0, (size_t)n, h->stream));
@@ -1011,7 +1021,7 @@ extern "C" int bwagpu_batch_reserve(bwagpu_t *h, int n_reads, int64_t n_bases, i
 	size_arenas(h);
 	int bad = alloc_batch(h, resident_threads(h), 0) != 0;
 	const u64 n_words = ((u64)n_bases + 15) / 16;
-	const int rdw = max_len <= 256 ? (((max_len + 15) / 16 + 3) & ~3) : 0;
+	const int rdw = max_len <= SEED_RD_MAX_LEN ? (((max_len + 15) / 16 + 3) & ~3) : 0;
 	bad |= h->d_seq.ensure((size_t)n_bases + 16); bad |= h->d_seq_nib.ensure((size_t)(n_words + 1) * 8); bad |= h->d_off.ensure((size_t)(n_reads + 1) * 8);
 	if (rdw) { bad |= h->d_seq_2b.ensure((size_t)n_reads * rdw * 4 + 64); bad |= h->d_seq_flags.ensure((size_t)n_reads + 16); }
 	const i64 tot = (i64)n_reads * 4;        // (packed results: ~3.2 regions per read on a repeat-rich genome)
@@ -1173,7 +1183,7 @@ extern "C" int bwagpu_batch_run(bwagpu_t *h, const bwagpu_opt_t *opt)
 	// position.  The host only says where each read's tasks begin; a task finds its read by bisection.
 	bool seed_tasks = pick(cfg.seed_tasks, 1) != 0;
 	int n_vreads = 0, task_lanes = 0;
-	const int TASK_STACK_CAP = PTAB_MAX + (cfg.seed_task_stack > 0 ? (int)((cfg.seed_task_stack + 1) / 2) : 128);          // BiIntv-sized entries of a task lane's spill area (default: 256 packed entries; a full stack hands the task to the second launch)
+	const int TASK_STACK_CAP = PTAB_MAX + (cfg.seed_task_stack > 0 ? (int)((cfg.seed_task_stack + 1) / 2) : TASK_STACK_DFLT);          // BiIntv-sized entries of a task lane's spill area (default: 256 packed entries; a full stack hands the task to the second launch)
 	if (!long_batch || h->max_len >= 65536 || h->seq_len >= ((u64)1 << 37) || h->ix.occ32 == nullptr || h->ix.ptab == nullptr || h->rd_words != 0 || opt->min_seed_len < 1 || cfg.seed_pass3_inline) seed_tasks = false;
 	if (seed_tasks) {
 		std::vector<i32> first((size_t)n + 1);
@@ -1221,9 +1231,10 @@ extern "C" int bwagpu_batch_run(bwagpu_t *h, const bwagpu_opt_t *opt)
 		B.tmp_intv = h->d_tmp_intv.as<BiIntv>(); B.mem_cap = h->mem_cap;
 		B.rd_words = h->rd_words; B.seq_2b = h->d_seq_2b.as<u32>(); B.seq_flags = h->d_seq_flags.as<u8>();
 		// LDS per lane: 160 bytes at four blocks per CU -- the read's 2-bit copy first, interval-stack entries with the rest
-		const int lane_lds = 160, ent_max = SEED_LDS_ENT;
+		const int lane_lds = SEED_LANE_LDS, ent_max = SEED_LDS_ENT;
 		const int lds_ent_dflt = h->rd_words ? ((lane_lds - 4 * h->rd_words) / 16 < ent_max ? (lane_lds - 4 * h->rd_words) / 16 : ent_max) : ent_max;
 		B.seed_lds_ent = (h->seq_len < ((u64)1 << 37) && h->max_len < 65536) ? (cfg.seed_lds_ent >= 0 ? (int)cfg.seed_lds_ent : lds_ent_dflt) : 0;
+		h->seed_lds_run = B.seed_lds_ent;
 		if (((size_t)(B.seed_lds_ent ? B.seed_lds_ent : 1) * 16 + (size_t)B.rd_words * 4) * BLOCK > 65536) B.rd_words = 0;   // (an LDS_ENT override too large for both)
 		B.intv_n = h->d_intv_n.as<i32>(); B.intv_off = h->d_intv_off.as<i64>(); B.intv = h->d_intv.as<Intv3>();
 		B.seed_n = h->d_seed_n.as<i32>(); B.seed_off = h->d_seed_off.as<i64>(); B.slot_cap = h->slot_cap;

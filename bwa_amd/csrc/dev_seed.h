@@ -12,6 +12,7 @@
 #include "dev_sort.h"
 
 #define PTAB_MAX 12      // deepest prefix table
+#define SEED_CAND_BITS 64      // pass-1 entries whose pass-2 test SeedEmit::cand remembers (a u64)
 
 struct SeedEmit {        // the MEM list of the read being seeded (lane-private scratch)
 	Intv3 *intv; int r, n, cap; bool overflow;      // the list is intv[r * cap ..] (the address is rebuilt on use: two registers less per lane)
@@ -30,7 +31,7 @@ struct SeedEmit {        // the MEM list of the read being seeded (lane-private 
 			return;
 		}
 		if (n == cap) { overflow = true; return; }
-		if (end - start >= split_len && x2 <= split_width && n - base < 64) cand |= 1ull << (n - base);
+		if (end - start >= split_len && x2 <= split_width && n - base < SEED_CAND_BITS) cand |= 1ull << (n - base);
 		mem()[n++] = v;
 	}
 };
@@ -619,7 +620,7 @@ __global__ void __launch_bounds__(256, OCC) k_seed(DevIndex ix, bwagpu_opt_t opt
 						if (LR == 2) {       // pass 2 only: the tasks' entries follow pass 3's; every one of them is looked at (no emitter's bit mask: base - 64)
 							const int n3 = B.intv_n3[r];
 							if (L.em.n > L.em.cap) { atomicOr(&B.ctr->overflow, 16ull); L.em.n = n3; B.intv_n[r] = n3; }      // (a task ran out of room: the batch is redone with longer lists)
-							L.em.base = n3 - 64; L.old_n = L.em.n; L.k2 = n3;
+							L.em.base = n3 - SEED_CAND_BITS; L.old_n = L.em.n; L.k2 = n3;
 							if (L.len >= opt.min_seed_len) L.st = SS_PASS2;
 						} else
 						if (L.len >= opt.min_seed_len) { L.x = 0; L.st = SS_PASS1; }   // else mem_chain returns at once (bwamem.c:286): draw the next read
@@ -655,9 +656,9 @@ __global__ void __launch_bounds__(256, OCC) k_seed(DevIndex ix, bwagpu_opt_t opt
 					bool started = false;
 					while (L.k2 < L.old_n && !started) {
 						const int kk = L.k2 - L.em.base;          // skip the entries the emitter already found not to qualify
-						if (kk < 64) {
+						if (kk < SEED_CAND_BITS) {
 							const u64 rest = L.em.cand >> kk;
-							if (rest == 0) { L.k2 = L.em.base + 64 < L.old_n ? L.em.base + 64 : L.old_n; continue; }
+							if (rest == 0) { L.k2 = L.em.base + SEED_CAND_BITS < L.old_n ? L.em.base + SEED_CAND_BITS : L.old_n; continue; }
 							L.k2 += __ffsll((unsigned long long)rest) - 1;
 							if (L.k2 >= L.old_n) break;
 						}

@@ -303,6 +303,14 @@ void bwagpu_dedup_limits(int32_t out[8]);
  * over the sorted keys), [3] earlier regions of the read tested per step of the "already covered" rule, [4] the longest read of a batch that takes the
  * short-read form, [5] the widest ring of the ring form (4 w + 132 columns, rounded up to a power of two, beyond it: the lane-per-read kernel). */
 void bwagpu_ext_limits(int32_t out[6]);
+/* The switch points of the seeding stage (mem_collect_intv), as compiled: out[0] the deepest prefix table, [1] the depth in force for h's index (0: no tables; h may be
+ * NULL: the default of option ptab_m) -- shorter matches are a bit mask of the lane when min_seed_len exceeds it --, [2] the most interval-stack entries per lane in LDS (the
+ * default of option seed_lds_ent where the read copy leaves room: see [8], [9]), [3] the longest read of a batch whose reads are copied to LDS at 2 bits per base, [4] the longest read of a short-read batch,
+ * [5] pass-1 entries whose pass-2 test the emitter remembers (later ones are read back from the list), [6] intervals of a read the workgroup-per-read sort takes,
+ * [7] entries of a pass-1 task's interval stack in HBM, prefix-table depth included (the default of option seed_task_stack, in 32-byte units), [8] LDS bytes per lane of the seeding kernel: a short-read batch's 2-bit read copy (16 bytes per 64 bases of its
+ * longest read, in steps of 16 bytes) comes first and 16-byte stack entries, [2] at the most, take the rest, [9] the entries in force in h's last bwagpu_batch_run
+ * (0: none yet, or the stack wholly in HBM). */
+void bwagpu_seed_limits(const bwagpu_t *h, int32_t out[10]);
 
 /* After bwagpu_batch_download of a paired batch (mates interleaved 2i, 2i+1): the local alignments mem_matesw
  * (bwamem_pair.c:137-206) would run for every (anchor region, orientation) that the downloaded region lists do not already
