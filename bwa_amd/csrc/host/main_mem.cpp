@@ -55,6 +55,7 @@ static int g_device_fastq = 0;    // BWAGPU_CLI_FASTQ=1: plain FASTQ files (one 
                                   // blobs of BWAGPU_CLI_SAMTEXT come from there; a batch the device declines, and the input behind it, goes through the reader below (same output)
 static std::string g_dev_rg_id; static bool g_dev_copy_comment = false;      // -R's id and -C for that call (set before the stages start)
 static std::atomic<long> g_n_primary_reads(0);   // ... reads finalized from such records (the BWAGPU_CLI_TRACE line at the end of the run)
+static int env_int(const char *name, int dflt) { const char *v = getenv(name); return v ? atoi(v) : dflt; }      // a switch or a size from the environment
 
 // ---- options -----------------------------------------------------------------------------------------------------------
 static void fill_scmat(int a, int b, int8_t mat[25])
@@ -368,6 +369,15 @@ struct Sub {      // one mem_process_seqs call (bwamem.c:1235-1264) on the reads
 	Pestat pes[4]; bool have_pes = false;     // insert-size windows, when they had to be computed before the finalize stage
 	std::vector<bwagpu_sam_out_t> sam; std::vector<int> sam_lo;   // bwagpu_batch_sam: the text of every shard (a shard that was not formatted has a null text) and the shards' first reads
 	double t_dev = 0;
+	// Everything device_sub left above, released once the batch's text exists.  Some blocks are the library's own (a single device's results are handed over as they are),
+	// some were joined from several devices' here with malloc: bwagpu_free takes both, a block it did not hand out goes to free().
+	template <class T> static void drop(T *&p) { bwagpu_free(p); p = nullptr; }
+	void release_results() {
+		drop(all); drop(cigs); drop(cig_ops); drop(msw); drop(pri); drop(alns); drop(pairs);
+		drop(m_all); drop(m_src); drop(rescue); drop(sampe); drop(m_cigs); drop(m_ops); drop(m_alns);
+		for (bwagpu_sam_out_t &o : sam) { bwagpu_free(o.text); bwagpu_free(o.off); bwagpu_free(o.flags); bwagpu_free(o.n_lines); }
+		sam.clear(); sam_lo.clear();
+	}
 };
 struct Work { long no = 0; Batch in; std::vector<Sub> subs; std::vector<std::string> out; bool by_read = false; /* SAM text in output order: one string per chunk of reads, or (by_read, smart pairing) per read */ };
 typedef std::unique_ptr<Work> WorkP;
@@ -624,6 +634,95 @@ static void device_fail(bwagpu_t *gpu, int rc, const char *what = nullptr)
 	fflush(stderr); fflush(stdout); _exit(EXIT_FAILURE);
 }
 
+// ---- what device_sub's stages share ----------------------------------------------------------------------------------------------------
+// mem_pestat's windows in the forms the library takes them, and back
+static void pestat_of(const Pestat *pes, bwagpu_pestat_t *dp)
+{
+	memset(dp, 0, 4 * sizeof *dp);
+	for (int d = 0; d < 4; ++d) { dp[d].low = pes[d].low; dp[d].high = pes[d].high; dp[d].failed = pes[d].failed; dp[d].avg = pes[d].avg; dp[d].std = pes[d].std; }
+}
+static void pes_of(const Pestat *pes, bwagpu_pes_t *dp) { for (int d = 0; d < 4; ++d) { dp[d].low = pes[d].low; dp[d].high = pes[d].high; dp[d].failed = pes[d].failed; dp[d].pad_ = 0; } }
+static void pestat_from(const bwagpu_pestat_t *dp, Pestat *pes) { for (int d = 0; d < 4; ++d) { pes[d].low = dp[d].low; pes[d].high = dp[d].high; pes[d].failed = dp[d].failed; pes[d].avg = dp[d].avg; pes[d].std = dp[d].std; } }
+
+// CIGAR records refer to their device's operation array; behind `by` operations of other devices in a joined array the references move by as much
+static void rebase_cigars(bwagpu_cigar_t *c, int64_t n, uint64_t by)
+{
+	if (by) for (int64_t i = 0; i < n; ++i) {
+		if (c[i].n_cigar > 6) { const uint64_t at = ((uint64_t)c[i].cigar[1] << 32 | c[i].cigar[0]) + by; c[i].cigar[0] = (uint32_t)at; c[i].cigar[1] = (uint32_t)(at >> 32); }
+		if (c[i].n_cigar >= 0 && c[i].md_len > 8) c[i].md += by;
+	}
+}
+
+// a device's range of the call's reads, [lo, hi) in whole pairs, and what its device returned for them
+struct Shard {
+	int lo = 0, hi = 0; int64_t np = 0 /* pairs */; std::vector<int64_t> off;
+	bwagpu_alnreg_t *all = nullptr; int64_t tot = 0; bwagpu_cigar_t *cigs = nullptr; uint32_t *ops = nullptr; int64_t n_ops = 0; bwagpu_matesw_t *msw = nullptr; int64_t n_msw = 0;
+	bwagpu_primary_t *pri = nullptr; bwagpu_aln_t *alns = nullptr; bwagpu_pair_t *pairs = nullptr;
+	bwagpu_alnreg_t *m_all = nullptr; int32_t *m_src = nullptr; int64_t m_tot = 0; bwagpu_rescue_t *rescue = nullptr;
+	bwagpu_sampe_t *sampe = nullptr; bwagpu_cigar_t *m_cigs = nullptr; uint32_t *m_ops = nullptr; int64_t n_m_ops = 0; bwagpu_aln_t *m_alns = nullptr;
+};
+struct Nothing { template <class... A> void operator()(A&&...) const {} };
+// One array of the shards' results joined in read order: shard s holds s.*count records in s.*block, and they go behind those of the shards before it -- a per-read
+// array follows the regions, a per-pair array the pairs.  fix(first, count, shard) may then adjust the copied records.  A shard without a block -- one without regions makes no
+// call -- gets its records from fill(first, count).  The shards' blocks are released.  A single shard's block is handed over as it is: nothing is copied on one device.
+template <class T, class Fix = Nothing, class Fill = Nothing>
+static T *join_shards(std::vector<Shard> &sh, T *Shard::*block, int64_t Shard::*count, Fix fix = Fix(), Fill fill = Fill())
+{
+	if (sh.size() == 1) { T *only = sh[0].*block; sh[0].*block = nullptr; return only; }
+	int64_t total = 0, k = 0;
+	for (const Shard &s : sh) total += s.*count;
+	T *all = (T*)malloc((size_t)(total ? total : 1) * sizeof(T));
+	if (!all) { fprintf(stderr, "[E::%s] out of memory\n", "mem_process_seqs"); exit(EXIT_FAILURE); }
+	for (Shard &s : sh) {
+		const int64_t m = s.*count;
+		if (s.*block) { if (m) memcpy(all + k, s.*block, (size_t)m * sizeof(T)); fix(all + k, m, s); }
+		else fill(all + k, m);
+		k += m;
+		bwagpu_free(s.*block); s.*block = nullptr;
+	}
+	return all;
+}
+// the records of a shard without regions: pairs without a candidate, which the device's mem_sam_pe declined
+static void fill_no_pair(bwagpu_pair_t *r, int64_t m) { memset(r, 0, (size_t)m * sizeof *r); for (int64_t p = 0; p < m; ++p) r[p].z[0] = r[p].z[1] = -1; }
+static void fill_no_rescue(bwagpu_rescue_t *r, int64_t m) { memset(r, 0, (size_t)m * sizeof *r); }
+static void fill_no_sampe(bwagpu_sampe_t *r, int64_t m) { memset(r, 0, (size_t)m * sizeof *r); for (int64_t p = 0; p < m; ++p) { r[p].path = -1; r[p].flags = 1; } }      // (flags bit 0: the host route)
+
+// names, qualities and comments of the reads [lo, hi) for bwagpu_batch_sam / bwagpu_batch_sam_pe: slices of the blobs of a batch parsed on the device (offsets need not start at 0),
+// or strings packed from the host's records into `hold`, which the caller keeps until the call has returned.  false: the shard takes the host formatter -- qualities for some
+// reads only, or (pairs) mates of different names, which the finalize stage reports as the reference does
+struct SamInText { std::string names, quals, comments; std::vector<int64_t> name_off, comment_off; };
+static bool sam_in_of_shard(const Sub &u, const Batch &in, int lo, int hi, bool pairs, SamInText &hold, bwagpu_sam_in_t &si)
+{
+	memset(&si, 0, sizeof si);
+	si.rg_id = g_dev_rg_id.c_str();
+	if ((u.fq || in.fq) && u.encoded) {
+		const bwagpu_fastq_out_t &f = u.fq ? *u.fq : *in.fq;
+		if (pairs) for (int i = lo + 1; i < hi; i += 2) {
+			const int64_t a = f.name_off[i - 1], b = f.name_off[i], c = f.name_off[i + 1];
+			if (b - a != c - b || memcmp(f.names + a, f.names + b, (size_t)(b - a)) != 0) return false;
+		}
+		si.names = f.names; si.name_off = f.name_off + lo; si.quals = f.quals + u.off[lo];
+		if (g_dev_copy_comment) { si.comments = f.comments; si.comment_off = f.comment_off + lo; }
+		return true;
+	}
+	int n_qual = 0;
+	for (int i = lo; i < hi; ++i) n_qual += in.seqs[u.idx[i]].has_qual;
+	if (n_qual != 0 && n_qual != hi - lo) return false;
+	hold.name_off.assign(1, 0); hold.comment_off.assign(1, 0);
+	for (int i = lo; i < hi; ++i) {
+		const Seq &q = in.seqs[u.idx[i]];
+		const char *T = in.T(q);
+		if (pairs && (i & 1) && strcmp(T + q.name, in.T(in.seqs[u.idx[i - 1]]) + in.seqs[u.idx[i - 1]].name) != 0) return false;
+		hold.names += T + q.name; hold.name_off.push_back((int64_t)hold.names.size());
+		if (n_qual) hold.quals.append(T + q.qual, (size_t)q.l_seq);
+		if (g_dev_copy_comment && q.has_comment) hold.comments += T + q.comment;
+		hold.comment_off.push_back((int64_t)hold.comments.size());
+	}
+	si.names = hold.names.data(); si.name_off = hold.name_off.data(); si.quals = n_qual ? hold.quals.data() : nullptr;
+	if (g_dev_copy_comment) { si.comments = hold.comments.data(); si.comment_off = hold.comment_off.data(); }
+	return true;
+}
+
 // One mem_process_seqs call's device work on the GPUs of `gpus` (one handle per device).  With several devices
 // the reads are split into contiguous ranges of whole pairs, every device runs the hot path -- and the device-side CIGARs and
 // mate-rescue alignments -- on its range, and the results are concatenated in read order.  The one step that needs the whole
@@ -640,10 +739,10 @@ static void device_sub(const std::vector<bwagpu_t*> &gpus, Sub &u, const RefSeqs
 	int D = (int)gpus.size();
 	const int units = pe ? n / 2 : n, per = pe ? 2 : 1;
 	if (D > units) D = units > 0 ? units : 1;
-	struct Shard { int lo = 0, hi = 0; std::vector<int64_t> off; bwagpu_alnreg_t *all = nullptr; int64_t tot = 0; bwagpu_cigar_t *cigs = nullptr; uint32_t *ops = nullptr; int64_t n_ops = 0; bwagpu_matesw_t *msw = nullptr; int64_t n_msw = 0; bwagpu_primary_t *pri = nullptr; bwagpu_aln_t *alns = nullptr; bwagpu_pair_t *pairs = nullptr; bwagpu_alnreg_t *m_all = nullptr; int32_t *m_src = nullptr; int64_t m_tot = 0; bwagpu_rescue_t *rescue = nullptr; bwagpu_pe_out_t pe = {}; };
 	std::vector<Shard> sh((size_t)D);
 	for (int d = 0; d < D; ++d) {
 		sh[d].lo = (int)((int64_t)units * d / D) * per; sh[d].hi = d + 1 == D ? n : (int)((int64_t)units * (d + 1) / D) * per;
+		sh[d].np = (sh[d].hi - sh[d].lo) / 2;
 		sh[d].off.resize((size_t)(sh[d].hi - sh[d].lo) + 1);
 		for (int i = sh[d].lo; i <= sh[d].hi; ++i) sh[d].off[(size_t)(i - sh[d].lo)] = u.off[i] - u.off[sh[d].lo];
 	}
@@ -670,18 +769,8 @@ static void device_sub(const std::vector<bwagpu_t*> &gpus, Sub &u, const RefSeqs
 		if (rc == BWAGPU_OK) rc = bwagpu_batch_download(gpus[d], u.counts.data() + s.lo, &s.all, &s.tot);
 		if (rc != BWAGPU_OK) device_fail(gpus[d], rc);
 	});
-	if (D == 1) { u.all = sh[0].all; u.tot = sh[0].tot; }
-	else {   // gather the regions in read order
-		u.tot = 0; for (auto &s : sh) u.tot += s.tot;
-		u.all = (bwagpu_alnreg_t*)malloc((size_t)(u.tot ? u.tot : 1) * sizeof(bwagpu_alnreg_t));
-		if (!u.all) { fprintf(stderr, "[E::%s] out of memory\n", "mem_process_seqs"); exit(EXIT_FAILURE); }
-		int64_t k = 0;
-		for (auto &s : sh) {
-			if (s.tot) memcpy(u.all + k, s.all, (size_t)s.tot * sizeof(bwagpu_alnreg_t));
-			k += s.tot;
-			bwagpu_free(s.all); s.all = nullptr;
-		}
-	}
+	u.tot = 0; for (auto &s : sh) u.tot += s.tot;
+	u.all = join_shards(sh, &Shard::all, &Shard::tot);
 	// mem_pestat needs the whole batch's regions (bwamem.c:1258) and nothing else: it runs on host threads while the devices
 	// produce the CIGARs of the same regions (it used to wait for them: 26 of a batch's 377 ms in this stage)
 	const bool want_matesw = g_device_matesw && pe && !(u.opt.flag & F_NO_RESCUE) && u.tot > 0;
@@ -707,7 +796,7 @@ static void device_sub(const std::vector<bwagpu_t*> &gpus, Sub &u, const RefSeqs
 			if (rc != BWAGPU_OK) device_fail(gpus[0], rc);
 			bwagpu_free(hs[0]);
 		}
-		for (int d = 0; d < 4; ++d) { u.pes[d].low = dp[d].low; u.pes[d].high = dp[d].high; u.pes[d].failed = dp[d].failed; u.pes[d].avg = dp[d].avg; u.pes[d].std = dp[d].std; }
+		pestat_from(dp, u.pes);
 		u.have_pes = true;
 		if (g_verbose >= 3) pestat_print(info, dp);
 		t_pes = now_s() - tp;
@@ -739,26 +828,10 @@ static void device_sub(const std::vector<bwagpu_t*> &gpus, Sub &u, const RefSeqs
 		if (rc != BWAGPU_OK) device_fail(gpus[d], rc);
 	});
 	t3 = now_s();
-	if (D == 1) { u.cigs = sh[0].cigs; u.cig_ops = sh[0].ops; }
-	else if (have_cigs) {
-		u.cigs = (bwagpu_cigar_t*)malloc((size_t)u.tot * sizeof(bwagpu_cigar_t));
-		int64_t n_ops = 0; for (auto &s : sh) n_ops += s.n_ops;
-		u.cig_ops = (uint32_t*)malloc((size_t)(n_ops ? n_ops : 1) * 4);
-		if (!u.cigs || !u.cig_ops) { fprintf(stderr, "[E::%s] out of memory\n", "mem_process_seqs"); exit(EXIT_FAILURE); }
-		int64_t k = 0, ko = 0;
-		for (auto &s : sh) {
-			if (s.tot) {   // (a shard without regions has no records); offsets into the operation array move with the shard's part of it
-				memcpy(u.cigs + k, s.cigs, (size_t)s.tot * sizeof(bwagpu_cigar_t));
-				if (s.n_ops) memcpy(u.cig_ops + ko, s.ops, (size_t)s.n_ops * 4);
-				if (ko) for (int64_t i = 0; i < s.tot; ++i) {
-					bwagpu_cigar_t &c = u.cigs[k + i];
-					if (c.n_cigar > 6) { const uint64_t at = ((uint64_t)c.cigar[1] << 32 | c.cigar[0]) + (uint64_t)ko; c.cigar[0] = (uint32_t)at; c.cigar[1] = (uint32_t)(at >> 32); }
-					if (c.n_cigar >= 0 && c.md_len > 8) c.md += (uint64_t)ko;
-				}
-			}
-			k += s.tot; ko += s.n_ops;
-			bwagpu_free(s.cigs); s.cigs = nullptr; bwagpu_free(s.ops); s.ops = nullptr;
-		}
+	if (have_cigs) {      // (a shard without regions has no records); offsets into the operation array move with the shard's part of it
+		uint64_t ko = 0;
+		u.cigs = join_shards(sh, &Shard::cigs, &Shard::tot, [&](bwagpu_cigar_t *c, int64_t m, const Shard &s) { rebase_cigars(c, m, ko); ko += (uint64_t)s.n_ops; });
+		u.cig_ops = join_shards(sh, &Shard::ops, &Shard::n_ops);
 	}
 	// mem_mark_primary_se + mem_approx_mapq_se of single-end reads on the device too: read i of the batch has id n_processed + i (bwamem.c:1227).  Paired-end
 	// batches mark after the host has merged the mate-rescue hits (mem_sam_pe), so they keep the host functions.
@@ -774,32 +847,8 @@ static void device_sub(const std::vector<bwagpu_t*> &gpus, Sub &u, const RefSeqs
 			u.sam_lo[(size_t)d] = s.lo;
 			memset(&u.sam[(size_t)d], 0, sizeof(bwagpu_sam_out_t));
 			if (s.tot == 0) return;      // (no CIGAR call for this shard: its reads print the unmapped record on the host)
-			const int m = s.hi - s.lo;
-			bwagpu_sam_in_t si; memset(&si, 0, sizeof si);
-			if ((u.fq || in->fq) && u.encoded) {      // parsed on the device: the shard is a slice of the parse's blobs (offsets need not start at 0)
-				const bwagpu_fastq_out_t &f = u.fq ? *u.fq : *in->fq;
-				si.names = f.names; si.name_off = f.name_off + s.lo; si.quals = f.quals + u.off[s.lo];
-				if (g_dev_copy_comment) { si.comments = f.comments; si.comment_off = f.comment_off + s.lo; }
-				si.rg_id = g_dev_rg_id.c_str();
-				const int rc = bwagpu_batch_sam(gpus[d], &u.opt, u.n_processed + s.lo, &si, &u.sam[(size_t)d]);
-				if (rc != BWAGPU_OK) device_fail(gpus[d], rc);
-				return;
-			}
-			int n_qual = 0;
-			for (int i = s.lo; i < s.hi; ++i) n_qual += in->seqs[u.idx[i]].has_qual;
-			if (n_qual != 0 && n_qual != m) return;      // (qualities for some reads only: the host formatter)
-			std::string names, quals, comments; std::vector<int64_t> name_off(1, 0), comment_off(1, 0);
-			for (int i = s.lo; i < s.hi; ++i) {
-				const Seq &q = in->seqs[u.idx[i]];
-				const char *T = in->T(q);
-				names += T + q.name; name_off.push_back((int64_t)names.size());
-				if (n_qual) quals.append(T + q.qual, (size_t)q.l_seq);
-				if (g_dev_copy_comment && q.has_comment) comments += T + q.comment;
-				comment_off.push_back((int64_t)comments.size());
-			}
-			si.names = names.data(); si.name_off = name_off.data(); si.quals = n_qual ? quals.data() : nullptr;
-			if (g_dev_copy_comment) { si.comments = comments.data(); si.comment_off = comment_off.data(); }
-			si.rg_id = g_dev_rg_id.c_str();
+			bwagpu_sam_in_t si; SamInText hold;
+			if (!sam_in_of_shard(u, *in, s.lo, s.hi, false, hold, si)) return;
 			const int rc = bwagpu_batch_sam(gpus[d], &u.opt, u.n_processed + s.lo, &si, &u.sam[(size_t)d]);
 			if (rc != BWAGPU_OK) device_fail(gpus[d], rc);
 		});
@@ -813,16 +862,7 @@ static void device_sub(const std::vector<bwagpu_t*> &gpus, Sub &u, const RefSeqs
 			int rc = bwagpu_batch_alns(gpus[d], &u.opt, u.n_processed + s.lo, &s.alns, &na, nullptr, &s.pri, nullptr, nullptr);
 			if (rc != BWAGPU_OK || na != s.tot) device_fail(gpus[d], rc, "bwagpu_batch_alns returned another number of records than bwagpu_batch_download");
 		});
-		if (D == 1) { u.pri = sh[0].pri; u.alns = sh[0].alns; }
-		else {      // (records name regions by the index within their read: nothing moves with the shard)
-			u.pri = (bwagpu_primary_t*)malloc((size_t)u.tot * sizeof(bwagpu_primary_t)); u.alns = (bwagpu_aln_t*)malloc((size_t)u.tot * sizeof(bwagpu_aln_t));
-			if (!u.pri || !u.alns) { fprintf(stderr, "[E::%s] out of memory\n", "mem_process_seqs"); exit(EXIT_FAILURE); }
-			int64_t k = 0;
-			for (auto &s : sh) {
-				if (s.tot) { memcpy(u.pri + k, s.pri, (size_t)s.tot * sizeof(bwagpu_primary_t)); memcpy(u.alns + k, s.alns, (size_t)s.tot * sizeof(bwagpu_aln_t)); }
-				k += s.tot; bwagpu_free(s.pri); s.pri = nullptr; bwagpu_free(s.alns); s.alns = nullptr;
-			}
-		}
+		u.pri = join_shards(sh, &Shard::pri, &Shard::tot); u.alns = join_shards(sh, &Shard::alns, &Shard::tot);      // (records name regions by the index within their read: nothing moves with the shard)
 	}
 	if (!dev_alns && !dev_samtext && g_device_primary && !pe && u.tot > 0) {
 		on_devices([&](int d) {
@@ -832,13 +872,7 @@ static void device_sub(const std::vector<bwagpu_t*> &gpus, Sub &u, const RefSeqs
 			int rc = bwagpu_batch_primary(gpus[d], &u.opt, u.n_processed + s.lo, &s.pri, &np, nullptr, nullptr);
 			if (rc != BWAGPU_OK || np != s.tot) device_fail(gpus[d], rc, "bwagpu_batch_primary returned another number of records than bwagpu_batch_download");
 		});
-		if (D == 1) u.pri = sh[0].pri;
-		else {      // (a record names its region by the index within its read: nothing moves with the shard)
-			u.pri = (bwagpu_primary_t*)malloc((size_t)u.tot * sizeof(bwagpu_primary_t));
-			if (!u.pri) { fprintf(stderr, "[E::%s] out of memory\n", "mem_process_seqs"); exit(EXIT_FAILURE); }
-			int64_t k = 0;
-			for (auto &s : sh) { if (s.tot) memcpy(u.pri + k, s.pri, (size_t)s.tot * sizeof(bwagpu_primary_t)); k += s.tot; bwagpu_free(s.pri); s.pri = nullptr; }
-		}
+		u.pri = join_shards(sh, &Shard::pri, &Shard::tot);      // (a record names its region by the index within its read: nothing moves with the shard)
 	}
 	t4 = now_s();
 	if (pes_thread.joinable()) pes_thread.join();
@@ -846,46 +880,16 @@ static void device_sub(const std::vector<bwagpu_t*> &gpus, Sub &u, const RefSeqs
 	// the host, and the calls below (rescue, pairing, mate-rescue alignments) are not made.  A pair the device declines, and every pair of a shard that is not
 	// formatted, runs the host's mem_sam_pe on the download's lists.
 	if (dev_sam_pe) {
-		bwagpu_pestat_t dp[4];
-		for (int d = 0; d < 4; ++d) { memset(&dp[d], 0, sizeof dp[d]); dp[d].low = u.pes[d].low; dp[d].high = u.pes[d].high; dp[d].failed = u.pes[d].failed; dp[d].avg = u.pes[d].avg; dp[d].std = u.pes[d].std; }
+		bwagpu_pestat_t dp[4]; pestat_of(u.pes, dp);
 		u.sam.assign((size_t)D, bwagpu_sam_out_t()); u.sam_lo.assign((size_t)D, 0);
 		on_devices([&](int d) {
 			Shard &s = sh[d];
 			u.sam_lo[(size_t)d] = s.lo;
 			memset(&u.sam[(size_t)d], 0, sizeof(bwagpu_sam_out_t));
 			if (s.tot == 0) return;      // (no region: the host prints the shard's unmapped records)
-			const int m = s.hi - s.lo;
-			bwagpu_sam_in_t si; memset(&si, 0, sizeof si);
-			std::vector<int32_t> m_counts((size_t)m);
-			if ((u.fq || in->fq) && u.encoded) {      // parsed on the device: slices of the parse's blobs
-				const bwagpu_fastq_out_t &f = u.fq ? *u.fq : *in->fq;
-				for (int i = s.lo + 1; i < s.hi; i += 2) {      // (mates of different names: the finalize stage reports them as the reference does)
-					const int64_t a = f.name_off[i - 1], b = f.name_off[i], c = f.name_off[i + 1];
-					if (b - a != c - b || memcmp(f.names + a, f.names + b, (size_t)(b - a)) != 0) return;
-				}
-				si.names = f.names; si.name_off = f.name_off + s.lo; si.quals = f.quals + u.off[s.lo];
-				if (g_dev_copy_comment) { si.comments = f.comments; si.comment_off = f.comment_off + s.lo; }
-				si.rg_id = g_dev_rg_id.c_str();
-				const int rc = bwagpu_batch_sam_pe(gpus[d], &u.opt, dp, u.n_processed + s.lo, &si, m_counts.data(), nullptr, &u.sam[(size_t)d]);
-				if (rc != BWAGPU_OK) device_fail(gpus[d], rc);
-				return;
-			}
-			int n_qual = 0;
-			for (int i = s.lo; i < s.hi; ++i) n_qual += in->seqs[u.idx[i]].has_qual;
-			if (n_qual != 0 && n_qual != m) return;      // (qualities for some reads only: the host formatter)
-			std::string names, quals, comments; std::vector<int64_t> name_off(1, 0), comment_off(1, 0);
-			for (int i = s.lo; i < s.hi; ++i) {
-				const Seq &q = in->seqs[u.idx[i]];
-				const char *T = in->T(q);
-				if ((i & 1) && strcmp(T + q.name, in->T(in->seqs[u.idx[i - 1]]) + in->seqs[u.idx[i - 1]].name) != 0) return;      // (mates of different names: the finalize stage reports them as the reference does)
-				names += T + q.name; name_off.push_back((int64_t)names.size());
-				if (n_qual) quals.append(T + q.qual, (size_t)q.l_seq);
-				if (g_dev_copy_comment && q.has_comment) comments += T + q.comment;
-				comment_off.push_back((int64_t)comments.size());
-			}
-			si.names = names.data(); si.name_off = name_off.data(); si.quals = n_qual ? quals.data() : nullptr;
-			if (g_dev_copy_comment) { si.comments = comments.data(); si.comment_off = comment_off.data(); }
-			si.rg_id = g_dev_rg_id.c_str();
+			bwagpu_sam_in_t si; SamInText hold;
+			if (!sam_in_of_shard(u, *in, s.lo, s.hi, true, hold, si)) return;
+			std::vector<int32_t> m_counts((size_t)(s.hi - s.lo));
 			const int rc = bwagpu_batch_sam_pe(gpus[d], &u.opt, dp, u.n_processed + s.lo, &si, m_counts.data(), nullptr, &u.sam[(size_t)d]);
 			if (rc != BWAGPU_OK) device_fail(gpus[d], rc);
 		});
@@ -895,62 +899,33 @@ static void device_sub(const std::vector<bwagpu_t*> &gpus, Sub &u, const RefSeqs
 	// The merge of mate-rescue hits, the marking of the merged lists and mem_pair on those records in one call, under the same conditions: it stands for both blocks below.
 	const bool dev_rescue = !dev_sam_pe && (g_device_rescue || dev_sampe) && pe && u.have_pes && !(u.opt.flag & (F_PRIMARY5 | F_NOPAIRING)) && !(u.n_processed & 1) && u.tot > 0;
 	if (dev_rescue) {
-		bwagpu_pestat_t dp[4];
-		for (int d = 0; d < 4; ++d) { memset(&dp[d], 0, sizeof dp[d]); dp[d].low = u.pes[d].low; dp[d].high = u.pes[d].high; dp[d].failed = u.pes[d].failed; dp[d].avg = u.pes[d].avg; dp[d].std = u.pes[d].std; }
+		bwagpu_pestat_t dp[4]; pestat_of(u.pes, dp);
 		u.m_counts.assign((size_t)n, 0);
 		on_devices([&](int d) {
 			Shard &s = sh[d];
 			if (s.tot == 0) return;      // (no region: the merged lists are empty too)
 			int rc;
 			if (dev_sampe) {      // the same arrays and more: the pairs' decisions, CIGAR and alignment records of the merged lists
-				rc = bwagpu_batch_sampe(gpus[d], &u.opt, dp, u.n_processed + s.lo, u.m_counts.data() + s.lo, &s.pe);
-				s.m_all = s.pe.regs; s.m_src = s.pe.src; s.m_tot = s.pe.n_regs; s.rescue = s.pe.rescue; s.pri = s.pe.pri; s.pairs = s.pe.pairs;
-				bwagpu_free(s.pe.n_pri); bwagpu_free(s.pe.n_aln); s.pe.n_pri = s.pe.n_aln = nullptr;
+				bwagpu_pe_out_t o = {};
+				rc = bwagpu_batch_sampe(gpus[d], &u.opt, dp, u.n_processed + s.lo, u.m_counts.data() + s.lo, &o);
+				s.m_all = o.regs; s.m_src = o.src; s.m_tot = o.n_regs; s.rescue = o.rescue; s.pri = o.pri; s.pairs = o.pairs;
+				s.sampe = o.sampe; s.m_cigs = o.cigs; s.m_ops = o.ops; s.n_m_ops = o.n_ops; s.m_alns = o.alns;
+				bwagpu_free(o.n_pri); bwagpu_free(o.n_aln);
 			} else rc = bwagpu_batch_rescue(gpus[d], &u.opt, dp, u.n_processed + s.lo, u.m_counts.data() + s.lo, &s.m_all, &s.m_src, &s.m_tot, &s.rescue, &s.pri, nullptr, &s.pairs, nullptr);
 			if (rc != BWAGPU_OK) device_fail(gpus[d], rc);
 		});
-		int64_t mt = 0; for (auto &s : sh) mt += s.m_tot;
-		u.m_all = (bwagpu_alnreg_t*)malloc((size_t)(mt ? mt : 1) * sizeof(bwagpu_alnreg_t));
-		u.m_src = (int32_t*)malloc((size_t)(mt ? mt : 1) * 4);
-		u.pri = (bwagpu_primary_t*)malloc((size_t)(mt ? mt : 1) * sizeof(bwagpu_primary_t));
-		u.pairs = (bwagpu_pair_t*)malloc((size_t)(n / 2 + 1) * sizeof(bwagpu_pair_t));
-		u.rescue = (bwagpu_rescue_t*)malloc((size_t)(n / 2 + 1) * sizeof(bwagpu_rescue_t));
-		if (!u.m_all || !u.m_src || !u.pri || !u.pairs || !u.rescue) { fprintf(stderr, "[E::%s] out of memory\n", "mem_process_seqs"); exit(EXIT_FAILURE); }
-		if (dev_sampe) {
-			int64_t mo = 0; for (auto &s : sh) mo += s.pe.n_ops;
-			u.sampe = (bwagpu_sampe_t*)calloc((size_t)(n / 2 + 1), sizeof(bwagpu_sampe_t));
-			u.m_cigs = (bwagpu_cigar_t*)malloc((size_t)(mt ? mt : 1) * sizeof(bwagpu_cigar_t)); u.m_alns = (bwagpu_aln_t*)malloc((size_t)(mt ? mt : 1) * sizeof(bwagpu_aln_t));
-			u.m_ops = (uint32_t*)malloc((size_t)(mo ? mo : 1) * 4);
-			if (!u.sampe || !u.m_cigs || !u.m_alns || !u.m_ops) { fprintf(stderr, "[E::%s] out of memory\n", "mem_process_seqs"); exit(EXIT_FAILURE); }
-			int64_t km = 0, ko = 0;
-			for (auto &s : sh) {      // (a shard without regions: its pairs keep the zeroed record with flags bit 0 set below, and take the host route)
-				if (s.tot == 0) { for (int p = s.lo / 2; p < s.hi / 2; ++p) { u.sampe[p].path = -1; u.sampe[p].flags = 1; } continue; }
-				memcpy(u.sampe + s.lo / 2, s.pe.sampe, (size_t)((s.hi - s.lo) / 2) * sizeof(bwagpu_sampe_t));
-				if (s.m_tot) { memcpy(u.m_cigs + km, s.pe.cigs, (size_t)s.m_tot * sizeof(bwagpu_cigar_t)); memcpy(u.m_alns + km, s.pe.alns, (size_t)s.m_tot * sizeof(bwagpu_aln_t)); }
-				if (s.pe.n_ops) memcpy(u.m_ops + ko, s.pe.ops, (size_t)s.pe.n_ops * 4);
-				if (ko) for (int64_t i = 0; i < s.m_tot; ++i) {      // (the operation arrays are laid end to end: a shard's references move by what precedes it)
-					bwagpu_cigar_t &c = u.m_cigs[km + i];
-					if (c.n_cigar > 6) { const uint64_t at = ((uint64_t)c.cigar[1] << 32 | c.cigar[0]) + (uint64_t)ko; c.cigar[0] = (uint32_t)at; c.cigar[1] = (uint32_t)(at >> 32); }
-					if (c.n_cigar >= 0 && c.md_len > 8) c.md += (uint64_t)ko;
-				}
-				km += s.m_tot; ko += s.pe.n_ops;
-				bwagpu_free(s.pe.sampe); bwagpu_free(s.pe.cigs); bwagpu_free(s.pe.ops); bwagpu_free(s.pe.alns); s.pe.sampe = nullptr; s.pe.cigs = nullptr; s.pe.ops = nullptr; s.pe.alns = nullptr;
-			}
-		}
-		int64_t k = 0;
-		for (auto &s : sh) {      // (records name regions and anchors by indices within their read: nothing moves with the shard)
-			const size_t np = (size_t)((s.hi - s.lo) / 2);
-			if (s.tot) {
-				if (s.m_tot) { memcpy(u.m_all + k, s.m_all, (size_t)s.m_tot * sizeof(bwagpu_alnreg_t)); memcpy(u.pri + k, s.pri, (size_t)s.m_tot * sizeof(bwagpu_primary_t)); memcpy(u.m_src + k, s.m_src, (size_t)s.m_tot * 4); }
-				memcpy(u.pairs + s.lo / 2, s.pairs, np * sizeof(bwagpu_pair_t)); memcpy(u.rescue + s.lo / 2, s.rescue, np * sizeof(bwagpu_rescue_t));
-			} else for (int p = s.lo / 2; p < s.hi / 2; ++p) { bwagpu_pair_t &r = u.pairs[p]; memset(&r, 0, sizeof r); r.z[0] = r.z[1] = -1; memset(&u.rescue[p], 0, sizeof u.rescue[p]); }
-			k += s.m_tot;
-			bwagpu_free(s.m_all); s.m_all = nullptr; bwagpu_free(s.m_src); s.m_src = nullptr; bwagpu_free(s.rescue); s.rescue = nullptr; bwagpu_free(s.pri); s.pri = nullptr; bwagpu_free(s.pairs); s.pairs = nullptr;
+		// (records name regions and anchors by indices within their read: nothing moves with the shard)
+		u.m_all = join_shards(sh, &Shard::m_all, &Shard::m_tot); u.m_src = join_shards(sh, &Shard::m_src, &Shard::m_tot); u.pri = join_shards(sh, &Shard::pri, &Shard::m_tot);
+		u.pairs = join_shards(sh, &Shard::pairs, &Shard::np, Nothing(), fill_no_pair); u.rescue = join_shards(sh, &Shard::rescue, &Shard::np, Nothing(), fill_no_rescue);
+		if (dev_sampe) {      // (a shard without regions: its pairs take the host route; the operation arrays are laid end to end: a shard's references move by what precedes it)
+			uint64_t ko = 0;
+			u.sampe = join_shards(sh, &Shard::sampe, &Shard::np, Nothing(), fill_no_sampe);
+			u.m_cigs = join_shards(sh, &Shard::m_cigs, &Shard::m_tot, [&](bwagpu_cigar_t *c, int64_t m, const Shard &s) { rebase_cigars(c, m, ko); ko += (uint64_t)s.n_m_ops; });
+			u.m_ops = join_shards(sh, &Shard::m_ops, &Shard::n_m_ops); u.m_alns = join_shards(sh, &Shard::m_alns, &Shard::m_tot);
 		}
 	}
 	if (!dev_rescue && !dev_sam_pe && g_device_pair && pe && u.have_pes && !(u.opt.flag & (F_PRIMARY5 | F_NOPAIRING)) && !(u.n_processed & 1) && u.tot > 0) {
-		bwagpu_pestat_t dp[4];
-		for (int d = 0; d < 4; ++d) { memset(&dp[d], 0, sizeof dp[d]); dp[d].low = u.pes[d].low; dp[d].high = u.pes[d].high; dp[d].failed = u.pes[d].failed; dp[d].avg = u.pes[d].avg; dp[d].std = u.pes[d].std; }
+		bwagpu_pestat_t dp[4]; pestat_of(u.pes, dp);
 		on_devices([&](int d) {
 			Shard &s = sh[d];
 			if (s.tot == 0) return;
@@ -958,35 +933,18 @@ static void device_sub(const std::vector<bwagpu_t*> &gpus, Sub &u, const RefSeqs
 			int rc = bwagpu_batch_pair(gpus[d], &u.opt, dp, u.n_processed + s.lo, &s.pairs, &np, &s.pri, &nr, nullptr, nullptr);
 			if (rc != BWAGPU_OK || nr != s.tot || np != (s.hi - s.lo) / 2) device_fail(gpus[d], rc, "bwagpu_batch_pair returned another number of records than bwagpu_batch_download");
 		});
-		u.pri = (bwagpu_primary_t*)malloc((size_t)u.tot * sizeof(bwagpu_primary_t));
-		u.pairs = (bwagpu_pair_t*)malloc((size_t)(n / 2 + 1) * sizeof(bwagpu_pair_t));
-		if (!u.pri || !u.pairs) { fprintf(stderr, "[E::%s] out of memory\n", "mem_process_seqs"); exit(EXIT_FAILURE); }
-		int64_t k = 0;
-		for (auto &s : sh) {      // (a record names its region by the index within its read: nothing moves with the shard; a shard without regions has only pairs without a candidate)
-			if (s.tot) { memcpy(u.pri + k, s.pri, (size_t)s.tot * sizeof(bwagpu_primary_t)); memcpy(u.pairs + s.lo / 2, s.pairs, (size_t)((s.hi - s.lo) / 2) * sizeof(bwagpu_pair_t)); }
-			else for (int p = s.lo / 2; p < s.hi / 2; ++p) { bwagpu_pair_t &r = u.pairs[p]; memset(&r, 0, sizeof r); r.z[0] = r.z[1] = -1; }
-			k += s.tot; bwagpu_free(s.pri); s.pri = nullptr; bwagpu_free(s.pairs); s.pairs = nullptr;
-		}
+		// (a record names its region by the index within its read: nothing moves with the shard; a shard without regions has only pairs without a candidate)
+		u.pri = join_shards(sh, &Shard::pri, &Shard::tot); u.pairs = join_shards(sh, &Shard::pairs, &Shard::np, Nothing(), fill_no_pair);
 	}
 	if (want_matesw && !dev_rescue && !dev_sam_pe) {
-		bwagpu_pes_t dp[4];
-		for (int d = 0; d < 4; ++d) { dp[d].low = u.pes[d].low; dp[d].high = u.pes[d].high; dp[d].failed = u.pes[d].failed; dp[d].pad_ = 0; }
+		bwagpu_pes_t dp[4]; pes_of(u.pes, dp);
 		on_devices([&](int d) {
 			if (sh[d].tot == 0) return;
 			int rc = bwagpu_batch_matesw(gpus[d], &u.opt, dp, &sh[d].msw, &sh[d].n_msw);
 			if (rc != BWAGPU_OK) device_fail(gpus[d], rc);
 		});
-		if (D == 1) { u.msw = sh[0].msw; u.n_msw = sh[0].n_msw; }
-		else {
-			u.n_msw = 0; for (auto &s : sh) u.n_msw += s.n_msw;
-			u.msw = (bwagpu_matesw_t*)malloc((size_t)(u.n_msw ? u.n_msw : 1) * sizeof(bwagpu_matesw_t));
-			if (!u.msw) { fprintf(stderr, "[E::%s] out of memory\n", "mem_process_seqs"); exit(EXIT_FAILURE); }
-			int64_t k = 0;
-			for (auto &s : sh) {
-				for (int64_t i = 0; i < s.n_msw; ++i) { u.msw[k] = s.msw[i]; u.msw[k].read += s.lo; ++k; }   // read indices are relative to the device's range
-				bwagpu_free(s.msw); s.msw = nullptr;
-			}
-		}
+		u.n_msw = 0; for (auto &s : sh) u.n_msw += s.n_msw;
+		u.msw = join_shards(sh, &Shard::msw, &Shard::n_msw, [](bwagpu_matesw_t *r, int64_t m, const Shard &s) { for (int64_t i = 0; i < m; ++i) r[i].read += s.lo; });   // read indices are relative to the device's range
 	}
 	t5 = now_s();
 	u.t_dev = t5 - t0;
@@ -1052,19 +1010,12 @@ static void finalize_sub(const RefSeqs &ref, Work &w, Sub &u, const Pestat *pes0
 		finalize_batch(u.opt, ref, u.n_processed, n, reads.data(), u.all, roff.data(), pes, u.opt.n_threads, rg_id, sam, g_verbose >= 3);
 		for (int i = 0; i < n; ++i) w.out[u.idx[i]].swap(sam[i]);
 	}
-	if (u.sampe) { free(u.sampe); u.sampe = nullptr; free(u.m_cigs); u.m_cigs = nullptr; free(u.m_ops); u.m_ops = nullptr; free(u.m_alns); u.m_alns = nullptr; }
-	if (u.rescue) { free(u.rescue); u.rescue = nullptr; free(u.m_all); u.m_all = nullptr; free(u.m_src); u.m_src = nullptr; }
-	if (u.pairs) { free(u.pairs); u.pairs = nullptr; free(u.pri); u.pri = nullptr; }
-	if (!u.sam.empty()) {
-		long k = 0;
-		if (!(u.opt.flag & F_PE)) for (int i = 0; i < n; ++i) k += reads[i].dev_text != nullptr;      // (pairs are counted where they are appended: g_pairs_from_samtext)
-		g_n_samtext_reads += k;
-		for (bwagpu_sam_out_t &o : u.sam) { bwagpu_free(o.text); bwagpu_free(o.off); bwagpu_free(o.flags); bwagpu_free(o.n_lines); }
-		u.sam.clear(); u.sam_lo.clear();
-	}
-	if (u.alns) { g_n_alns_reads += n; bwagpu_free(u.alns); u.alns = nullptr; bwagpu_free(u.pri); u.pri = nullptr; }
-	if (u.pri) { g_n_primary_reads += n; bwagpu_free(u.pri); u.pri = nullptr; }
-	bwagpu_free(u.all); u.all = nullptr; bwagpu_free(u.cigs); u.cigs = nullptr; bwagpu_free(u.cig_ops); u.cig_ops = nullptr; bwagpu_free(u.msw); u.msw = nullptr;
+	long n_text = 0;
+	if (!u.sam.empty() && !(u.opt.flag & F_PE)) for (int i = 0; i < n; ++i) n_text += reads[i].dev_text != nullptr;      // (pairs are counted where they are appended: g_pairs_from_samtext)
+	g_n_samtext_reads += n_text;
+	if (u.alns) g_n_alns_reads += n;
+	else if (u.pri && !u.pairs) g_n_primary_reads += n;      // (single-end marking records; a paired-end batch's come with its pair records)
+	u.release_results();
 	if (g_verbose >= 3) fprintf(stderr, "[M::%s] Processed %d reads in %.3f real sec\n", "mem_process_seqs", n, u.t_dev + (now_s() - t0));
 }
 
@@ -1101,7 +1052,7 @@ int main(int argc, char *argv[])
 	Pestat pes[4]; memset(pes, 0, sizeof pes); for (int i = 0; i < 4; ++i) pes[i].failed = 1;
 	const Pestat *pes0 = nullptr;
 	const char *mode = nullptr; char *p;
-	int c, fixed_chunk = -1, ignore_alt = 0, copy_comment = 0, device = getenv("BWAGPU_DEVICE") ? atoi(getenv("BWAGPU_DEVICE")) : 0;
+	int c, fixed_chunk = -1, ignore_alt = 0, copy_comment = 0, device = env_int("BWAGPU_DEVICE", 0);
 	std::string hdr_line, rg_line, rg_id;
 	while ((c = getopt(argc, argv, "51qpaMCSPVYjuk:c:v:s:r:t:R:A:B:O:E:U:w:L:d:T:Q:D:m:I:N:o:f:W:x:G:h:y:K:X:H:z:")) >= 0) {
 		if (c == 'k') opt.min_seed_len = atoi(optarg), opt0.min_seed_len = 1;
@@ -1207,8 +1158,8 @@ int main(int argc, char *argv[])
 	struct Prewarm { std::vector<HostBuf> flats; std::thread th; ~Prewarm() { if (th.joinable()) th.join(); } } prewarm;
 	if (!getenv("BWAGPU_CLI_NO_PREWARM")) {
 		const int64_t chunk0 = fixed_chunk > 0 ? fixed_chunk : (int64_t)opt.chunk_size * opt.n_threads;
-		const int n_flat = getenv("BWAGPU_CLI_STREAMS") ? (atoi(getenv("BWAGPU_CLI_STREAMS")) > 0 ? atoi(getenv("BWAGPU_CLI_STREAMS")) + 1 : 2) : 4;
-		const bool par_blocks = !(getenv("BWAGPU_CLI_PARSE_THREADS") && atoi(getenv("BWAGPU_CLI_PARSE_THREADS")) <= 0);
+		const int n_flat = env_int("BWAGPU_CLI_STREAMS", 3) > 0 ? env_int("BWAGPU_CLI_STREAMS", 3) + 1 : 2;
+		const bool par_blocks = env_int("BWAGPU_CLI_PARSE_THREADS", 4) > 0;
 		prewarm.th = std::thread([&prewarm, chunk0, n_flat, par_blocks] {
 			if (chunk0 > 0 && chunk0 <= ((int64_t)1 << 31)) for (int k = 0; k < n_flat && k < 6; ++k) { HostBuf b; b.need((size_t)chunk0 + (1 << 20)); prewarm.flats.push_back(std::move(b)); }
 			if (par_blocks) {
@@ -1242,10 +1193,10 @@ int main(int argc, char *argv[])
 		if (rc != BWAGPU_OK) { fprintf(stderr, "[E::%s] %s\n", "main_mem", bwagpu_strerror(rc)); return 1; }
 	}
 	// BWAGPU_CLI_FASTQ: the device parser and its window buffers, before the suffix array below is sized against the free memory
-	if (getenv("BWAGPU_CLI_FASTQ")) g_device_fastq = atoi(getenv("BWAGPU_CLI_FASTQ"));
-	if (getenv("BWAGPU_CLI_BGZF_DEV")) g_device_bgzf = atoi(getenv("BWAGPU_CLI_BGZF_DEV"));
+	g_device_fastq = env_int("BWAGPU_CLI_FASTQ", g_device_fastq);
+	g_device_bgzf = env_int("BWAGPU_CLI_BGZF_DEV", g_device_bgzf);
 	std::unique_ptr<DevInput> dev_in;
-	if (getenv("BWAGPU_CLI_SMARTPE_DEV")) g_device_smartpe = atoi(getenv("BWAGPU_CLI_SMARTPE_DEV"));
+	g_device_smartpe = env_int("BWAGPU_CLI_SMARTPE_DEV", g_device_smartpe);
 	if (g_device_fastq && (!(opt.flag & F_SMARTPE) || g_device_smartpe) && !getenv("BWAGPU_CLI_PARSE_ONLY")) {
 		dev_in.reset(new DevInput());
 		dev_in->smart = (opt.flag & F_SMARTPE) != 0;
@@ -1263,7 +1214,7 @@ int main(int argc, char *argv[])
 		} else dev_in.reset();
 	}
 	bwagpu_set_taps(gpu, 0);
-	bwagpu_set_cigar_filter(gpu, getenv("BWAGPU_CLI_CIGAR_FILTER") ? atoi(getenv("BWAGPU_CLI_CIGAR_FILTER")) : 1);   // (clones inherit it)
+	bwagpu_set_cigar_filter(gpu, env_int("BWAGPU_CLI_CIGAR_FILTER", 1));   // (clones inherit it)
 	{	// SA look-ups walk ~31 LF steps with the reference's interval of 32; HBM has room for the full array (same values): 8 bytes per text position, 50 GB for a
 		// human genome, one look-up = one 8-byte read (k_sa 3.1 -> 0.9 ms per million reads against an interval of 4).  If that much is not to be had: the next intervals up.
 		// The array must leave room for the batches: every handle (BWAGPU_CLI_STREAMS of them per device) grows arenas for a -K batch -- about 17 GB at the
@@ -1271,8 +1222,8 @@ int main(int argc, char *argv[])
 		// full array and then fail its first batch.  So: the smallest interval whose array fits beside the handles' estimated footprint (the library's own
 		// allocation arithmetic run dry, bwagpu_batch_footprint, for reads of >= 100 bp -- shorter reads mean more reads per -K batch; + 15 % + 2 GB for the
 		// CIGAR / mate-rescue scratch that is sized by results).  BWAGPU_CLI_HBM_LIMIT_MB caps what the program takes the free memory to be.
-		const int dense = getenv("BWAGPU_CLI_DENSE_SA") ? atoi(getenv("BWAGPU_CLI_DENSE_SA")) : 1;
-		const int n_slots = getenv("BWAGPU_CLI_STREAMS") ? (atoi(getenv("BWAGPU_CLI_STREAMS")) > 1 ? atoi(getenv("BWAGPU_CLI_STREAMS")) : 1) : 3;
+		const int dense = env_int("BWAGPU_CLI_DENSE_SA", 1);
+		const int n_slots = env_int("BWAGPU_CLI_STREAMS", 3) > 1 ? env_int("BWAGPU_CLI_STREAMS", 3) : 1;
 		const int64_t chunk_est = fixed_chunk > 0 ? fixed_chunk : (int64_t)opt.chunk_size * opt.n_threads;
 		const bool long_est = mode && (strcmp(mode, "pacbio") == 0 || strcmp(mode, "pbref") == 0 || strcmp(mode, "ont2d") == 0);
 		const int len_est = long_est ? 10000 : 100;
@@ -1306,7 +1257,7 @@ int main(int argc, char *argv[])
 	bool any_bgzf = false;
 	for (int k = optind + 1; k < argc && k <= optind + 2; ++k) if (strcmp(argv[k], "-") && BgzfPipe::is_bgzf(argv[k])) any_bgzf = true;
 	// (BGZF input: the pool inflates -- ~210 MB/s of FASTQ per thread --, so it gets up to eight threads, half of -t)
-	const int n_parse = getenv("BWAGPU_CLI_PARSE_THREADS") ? atoi(getenv("BWAGPU_CLI_PARSE_THREADS")) : (any_bgzf ? (opt.n_threads / 2 > 8 ? 8 : (opt.n_threads / 2 < 4 ? 4 : opt.n_threads / 2)) : 4);
+	const int n_parse = env_int("BWAGPU_CLI_PARSE_THREADS", any_bgzf ? (opt.n_threads / 2 > 8 ? 8 : (opt.n_threads / 2 < 4 ? 4 : opt.n_threads / 2)) : 4);
 	std::unique_ptr<ParPool> parse_pool(n_parse > 0 ? new ParPool(n_parse) : nullptr);
 	Source r1, r2; Source *pr2 = nullptr;
 	if (dev_in) { if (dev_in->nf > 1) { pr2 = &r2; opt.flag |= F_PE; } }      // (the readers are opened where the device hands over, at its offsets)
@@ -1331,8 +1282,8 @@ int main(int argc, char *argv[])
 	const bool tl_trace = getenv("BWAGPU_CLI_TRACE") != nullptr;      // (with the other trace lines: when each stage held each batch, seconds since here)
 	if (getenv("BWAGPU_CLI_PARSE_ONLY")) {   // diagnostics: speed of the input stage alone
 		Batch b; long n = 0, bp = 0;
-		const bool dump = atoi(getenv("BWAGPU_CLI_PARSE_ONLY")) == 2;      // (tests: what the input stage delivers, batch by batch)
-		const bool enc = atoi(getenv("BWAGPU_CLI_PARSE_ONLY")) == 3;       // (and the encoding stage: seconds, and a digest of the codes)
+		const bool dump = env_int("BWAGPU_CLI_PARSE_ONLY", 0) == 2;      // (tests: what the input stage delivers, batch by batch)
+		const bool enc = env_int("BWAGPU_CLI_PARSE_ONLY", 0) == 3;      // (and the encoding stage: seconds, and a digest of the codes)
 		double t_enc = 0; uint64_t dig = 1469598103934665603ull;
 		while (read_batch(r1, pr2, chunk, b)) {
 			n += (long)b.seqs.size(); for (auto &q : b.seqs) bp += q.l_seq;
@@ -1351,18 +1302,18 @@ int main(int argc, char *argv[])
 		if (enc) fprintf(stderr, "[M::%s] encoded in %.3f s (%s), digest %016llx\n", "main_mem", t_enc, g_nt4_avx2 ? "AVX2" : "table", (unsigned long long)dig);
 		return 0;
 	}
-	if (getenv("BWAGPU_CLI_SERIALIZE")) g_dev_serialize = atoi(getenv("BWAGPU_CLI_SERIALIZE")) != 0;
-	if (getenv("BWAGPU_CLI_MATESW")) g_device_matesw = atoi(getenv("BWAGPU_CLI_MATESW"));
-	if (getenv("BWAGPU_CLI_CIGARS")) g_device_cigars = atoi(getenv("BWAGPU_CLI_CIGARS"));
-	if (getenv("BWAGPU_CLI_PRIMARY")) g_device_primary = atoi(getenv("BWAGPU_CLI_PRIMARY"));
-	if (getenv("BWAGPU_CLI_ALNS")) g_device_alns = atoi(getenv("BWAGPU_CLI_ALNS"));
-	if (getenv("BWAGPU_CLI_SAMTEXT")) g_device_samtext = atoi(getenv("BWAGPU_CLI_SAMTEXT"));
+	g_dev_serialize = env_int("BWAGPU_CLI_SERIALIZE", g_dev_serialize) != 0;
+	g_device_matesw = env_int("BWAGPU_CLI_MATESW", g_device_matesw);
+	g_device_cigars = env_int("BWAGPU_CLI_CIGARS", g_device_cigars);
+	g_device_primary = env_int("BWAGPU_CLI_PRIMARY", g_device_primary);
+	g_device_alns = env_int("BWAGPU_CLI_ALNS", g_device_alns);
+	g_device_samtext = env_int("BWAGPU_CLI_SAMTEXT", g_device_samtext);
 	g_dev_rg_id = rg_id; g_dev_copy_comment = copy_comment != 0;
-	if (getenv("BWAGPU_CLI_PAIR")) g_device_pair = atoi(getenv("BWAGPU_CLI_PAIR"));
-	if (getenv("BWAGPU_CLI_RESCUE")) g_device_rescue = atoi(getenv("BWAGPU_CLI_RESCUE"));
-	if (getenv("BWAGPU_CLI_SAMPE")) g_device_sampe = atoi(getenv("BWAGPU_CLI_SAMPE"));
-	if (getenv("BWAGPU_CLI_PESTAT")) g_device_pestat = atoi(getenv("BWAGPU_CLI_PESTAT"));
-	int n_dev = getenv("BWAGPU_CLI_STREAMS") ? atoi(getenv("BWAGPU_CLI_STREAMS")) : 3;      // batches in flight on the device
+	g_device_pair = env_int("BWAGPU_CLI_PAIR", g_device_pair);
+	g_device_rescue = env_int("BWAGPU_CLI_RESCUE", g_device_rescue);
+	g_device_sampe = env_int("BWAGPU_CLI_SAMPE", g_device_sampe);
+	g_device_pestat = env_int("BWAGPU_CLI_PESTAT", g_device_pestat);
+	int n_dev = env_int("BWAGPU_CLI_STREAMS", 3);      // batches in flight on the device
 	if (n_dev < 1) n_dev = 1;
 	// devices: BWAGPU_DEVICES=0,1,... (default: the one of BWAGPU_DEVICE).  The index reaches the other devices by device-to-device copies over
 	// xGMI (bwagpu_clone_to_device: one process drives all devices, so a peer copy is the direct route; the RCCL broadcast of bwa_amd/dist.py is
@@ -1409,7 +1360,7 @@ int main(int argc, char *argv[])
 	// watchdog (BWAGPU_CLI_WATCHDOG=<seconds>): if no stage makes progress for that long, say where everything is and give up
 	std::atomic<long> progress(0); std::atomic<int> dev_no[16]; std::atomic<bool> all_done(false);
 	for (auto &x : dev_no) x = -1;
-	const int wd_secs = getenv("BWAGPU_CLI_WATCHDOG") ? atoi(getenv("BWAGPU_CLI_WATCHDOG")) : 0;
+	const int wd_secs = env_int("BWAGPU_CLI_WATCHDOG", 0);
 	std::thread watchdog([&] {
 		long last = -1; int idle = 0;
 		while (wd_secs > 0 && !all_done.load()) {
@@ -1527,7 +1478,7 @@ int main(int argc, char *argv[])
 		// while the reader parses the first batch: the arenas of a batch of -K bases of short reads (150 bp assumed; anything else grows them
 		// later).  Not for the long-read presets: the short-read shape asks for ~4 GB per handle that a long-read run never uses and -- device
 		// buffers only ever grow -- never gets back.
-		if (!g_dev_serialize && !long_preset && !(getenv("BWAGPU_CLI_RESERVE") && atoi(getenv("BWAGPU_CLI_RESERVE")) == 0))      // (not under the mock runtime of the CPU tests)
+		if (!g_dev_serialize && !long_preset && env_int("BWAGPU_CLI_RESERVE", 1) != 0)      // (not under the mock runtime of the CPU tests)
 			for (bwagpu_t *hh : workers[(size_t)d]) {
 				const int rc = bwagpu_batch_reserve(hh, (int)((int64_t)chunk / 150 / (int64_t)workers[(size_t)d].size()) + 1024, (int64_t)chunk / (int64_t)workers[(size_t)d].size() + (1 << 20), 256);
 				if (rc != BWAGPU_OK && g_verbose >= 2) fprintf(stderr, "[W::%s] could not reserve the batch arenas ahead of the first batch (%s: %s); they are grown batch by batch instead\n", "main_mem", bwagpu_strerror(rc), bwagpu_last_error(hh));
