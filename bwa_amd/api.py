@@ -753,6 +753,10 @@ class FastqParser:
         L.bwagpu_fastq_batch.argtypes = [P, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p]
         L.bwagpu_bgzf_inflate.argtypes = [P, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]
         L.bwagpu_fastq_batch_bgzf.argtypes = [P, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.bwagpu_fastq_batch_fasta.argtypes = L.bwagpu_fastq_batch.argtypes
+        L.bwagpu_fastq_batch_fasta_bgzf.argtypes = L.bwagpu_fastq_batch_bgzf.argtypes
+        L.bwagpu_fasta_reads_limits.argtypes = [C.c_void_p]
+        L.bwagpu_fasta_reads_limits.restype = None
         L.bwagpu_fastq_batch_smart.argtypes = [P, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p]
         L.bwagpu_fastq_batch_smart_bgzf.argtypes = [P, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         L.bwagpu_fastq_smart_free.argtypes = [C.c_void_p]
@@ -782,16 +786,30 @@ class FastqParser:
         """the bare call (tests of the error paths): returns the library's code"""
         return self.L.bwagpu_fastq_batch(self.h, raw1, len1, eof1, raw2, len2, eof2, chunk_size, out)
 
-    def batch(self, raw1, raw2=None, chunk_size: int = 10_000_000, eof=(True, True)) -> dict:
+    def batch_fasta_rc(self, raw1, len1, eof1, raw2, len2, eof2, chunk_size, out):
+        """the bare call (tests of the error paths): returns the library's code"""
+        return self.L.bwagpu_fastq_batch_fasta(self.h, raw1, len1, eof1, raw2, len2, eof2, chunk_size, out)
+
+    def batch_fasta(self, raw1, raw2=None, chunk_size: int = 10_000_000, eof=(True, True)) -> dict:
+        """batch() for windows of FASTA text, each starting at a '>' (bwagpu_fastq_batch_fasta).  The same dict; quals is None."""
+        return self.batch(raw1, raw2, chunk_size, eof, _call="bwagpu_fastq_batch_fasta")
+
+    def fasta_reads_limits(self) -> dict:
+        """bwagpu_fasta_reads_limits: the sizes at which the FASTA reader's kernels change their step, as compiled."""
+        out = (C.c_int32 * 4)()
+        self.L.bwagpu_fasta_reads_limits(out)
+        return dict(zip(("tile_bytes", "lane_bytes", "emit_step_bytes"), list(out)))
+
+    def batch(self, raw1, raw2=None, chunk_size: int = 10_000_000, eof=(True, True), _call="bwagpu_fastq_batch") -> dict:
         """raw1 / raw2: bytes-like windows, each starting at a record start (raw2 None: one file).  Returns a dict with status (FQ_*),
         n_reads, consumed, declined_file, declined_at, kernel_ms and -- for FQ_CUT / FQ_END -- copies of the arrays: seqs (nt4), off,
         names, name_off, quals, comments, comment_off, has_comment, recs."""
         b1 = np.frombuffer(raw1, dtype=np.uint8) if len(raw1) else np.zeros(1, dtype=np.uint8)
         b2 = None if raw2 is None else (np.frombuffer(raw2, dtype=np.uint8) if len(raw2) else np.zeros(1, dtype=np.uint8))
         o = FastqOut()
-        rc = self.L.bwagpu_fastq_batch(self.h, b1.ctypes.data, len(raw1), int(bool(eof[0])), None if b2 is None else b2.ctypes.data,
-                                       0 if raw2 is None else len(raw2), int(bool(eof[1])), int(chunk_size), C.byref(o))
-        self._chk(rc, "bwagpu_fastq_batch")
+        rc = getattr(self.L, _call)(self.h, b1.ctypes.data, len(raw1), int(bool(eof[0])), None if b2 is None else b2.ctypes.data,
+                                    0 if raw2 is None else len(raw2), int(bool(eof[1])), int(chunk_size), C.byref(o))
+        self._chk(rc, _call)
         return self._result(o)
 
     @staticmethod
@@ -806,7 +824,7 @@ class FastqParser:
         for k in ("off", "name_off", "comment_off"):
             r[k] = take(getattr(o, k), n + 1, np.int64)
         r["seqs"] = take(o.seqs, int(r["off"][n]), np.uint8)
-        r["quals"] = take(o.quals, int(r["off"][n]), np.uint8).tobytes()
+        r["quals"] = take(o.quals, int(r["off"][n]), np.uint8).tobytes() if o.quals else None      # (None: FASTA reads)
         r["names"] = take(o.names, int(r["name_off"][n]), np.uint8).tobytes()
         r["comments"] = take(o.comments, int(r["comment_off"][n]), np.uint8).tobytes()
         r["has_comment"] = take(o.has_comment, n, np.uint8)
@@ -893,7 +911,15 @@ class FastqParser:
         """the bare call (tests of the error paths): returns the library's code"""
         return self.L.bwagpu_fastq_batch_bgzf(self.h, w1, w2, chunk_size, out, info)
 
-    def batch_bgzf(self, c1, c2=None, skip=(0, 0), chunk_size: int = 10_000_000, eof=(True, True)) -> dict:
+    def batch_fasta_bgzf_rc(self, w1, w2, chunk_size, out, info):
+        """the bare call (tests of the error paths): returns the library's code"""
+        return self.L.bwagpu_fastq_batch_fasta_bgzf(self.h, w1, w2, chunk_size, out, info)
+
+    def batch_fasta_bgzf(self, c1, c2=None, skip=(0, 0), chunk_size: int = 10_000_000, eof=(True, True)) -> dict:
+        """batch_bgzf() for BGZF windows of FASTA text (bwagpu_fastq_batch_fasta_bgzf).  The same dict; quals is None."""
+        return self.batch_bgzf(c1, c2, skip, chunk_size, eof, _call="bwagpu_fastq_batch_fasta_bgzf")
+
+    def batch_bgzf(self, c1, c2=None, skip=(0, 0), chunk_size: int = 10_000_000, eof=(True, True), _call="bwagpu_fastq_batch_bgzf") -> dict:
         """c1 / c2: bytes-like windows of BGZF data, each starting at a block start (c2 None: one file); skip[k]: bytes of window k's first
         block's text that earlier batches consumed.  Returns batch()'s dict plus "bgzf": one info dict per window (bwagpu_bgzf_info_t's
         fields).  consumed, declined_at and recs refer to the text window, which exists on the device only."""
@@ -907,8 +933,8 @@ class FastqParser:
             wins.append(BgzfWin(b.ctypes.data, len(c), int(skip[k]), int(bool(eof[k]))))
         o = FastqOut()
         info = (BgzfInfo * 2)()
-        rc = self.L.bwagpu_fastq_batch_bgzf(self.h, C.byref(wins[0]), None if wins[1] is None else C.byref(wins[1]), int(chunk_size), C.byref(o), info)
-        self._chk(rc, "bwagpu_fastq_batch_bgzf")
+        rc = getattr(self.L, _call)(self.h, C.byref(wins[0]), None if wins[1] is None else C.byref(wins[1]), int(chunk_size), C.byref(o), info)
+        self._chk(rc, _call)
         r = self._result(o)
         r["bgzf"] = [info[k].as_dict() for k in range(1 if c2 is None else 2)]
         return r

@@ -41,6 +41,7 @@ typedef unsigned char u8;
 
 #include "dev_fasta.h"            // FASTA -> .pac / holes (bwagpu_fasta_*)
 #include "dev_fastq.h"            // FASTQ windows -> batches (bwagpu_fastq_*)
+#include "dev_fasta_reads.h"      // FASTA read windows -> batches (bwagpu_fastq_batch_fasta*)
 #include "dev_fastq_smart.h"      // ... classified and split for `mem -p` (bwagpu_fastq_batch_smart*)
 #include "dev_bgzf.h"             // BGZF blocks -> text (bwagpu_bgzf_inflate, bwagpu_fastq_batch_bgzf)
 
@@ -855,6 +856,7 @@ struct bwagpu_fastq_parser_s {
 	Buf d_buf[2], d_nl[2], d_recs[2], d_tcount, d_tbase, d_units, d_uscan, d_words, d_tmp;
 	Buf o_seqs, o_off, o_names, o_name_off, o_quals, o_com, o_com_off, o_has, o_recs;
 	Buf d_eqv, d_runs, d_cls, d_sums, d_sscan, o_idx;      // bwagpu_fastq_batch_smart: dev_fastq_smart.h's arrays
+	Buf d_lflag[2], d_lines[2], d_lscan[2], d_hline[2], d_bend[2];      // bwagpu_fastq_batch_fasta: dev_fasta_reads.h's arrays
 	std::string err;
 
 	~bwagpu_fastq_parser_s()
@@ -981,10 +983,62 @@ static int fq_launch(bwagpu_fastq_parser_t *p, const FqArgs &A, u32 tiles, u64 c
 	return 0;
 }
 
-// everything behind the copy-up
-static int fq_run(bwagpu_fastq_parser_t *p, const FqArgs &A, u32 tiles, u64 cap_units, int chunk_size, bwagpu_fastq_out_t *out)
+// FASTA records in the windows fq_setup laid out (dev_fasta_reads.h): a newline slot for every byte, a record slot for every two, and
+// the per-line and per-record arrays
+static int fr_setup(bwagpu_fastq_parser_t *p, FqArgs &A, FrArgs &X, u64 *n_units)
 {
-	if (int rc = fq_launch(p, A, tiles, cap_units, chunk_size)) return rc;
+	memset(&X, 0, sizeof X);
+	u64 cap_units = ~0ull;
+	for (int k = 0; k < A.nw; ++k) {
+		FqWin &W = A.w[k];
+		const u64 cap_lines = ((u64)W.n + 1 + 3) & ~3ull, cap_recs = ((u64)W.n >> 1) + 2;
+		if (p->d_nl[k].ensure(cap_lines * 4) || p->d_recs[k].ensure(cap_recs * sizeof(bwagpu_fastq_rec_t)) || p->d_lflag[k].ensure(cap_lines) ||
+			p->d_lines[k].ensure(cap_lines * sizeof(FrLine)) || p->d_lscan[k].ensure(cap_lines * sizeof(FrLine)) || p->d_hline[k].ensure((cap_recs + 1) * 4) ||
+			p->d_bend[k].ensure(cap_recs * 4)) return p->fail(BWAGPU_ENOMEM, "hipMalloc failed (FASTA window)");
+		W.nl = p->d_nl[k].as<u32>(); W.nl_cap = (u32)cap_lines; W.recs = p->d_recs[k].as<bwagpu_fastq_rec_t>(); W.rec_cap = (u32)cap_recs;
+		FrWin &Y = X.x[k];
+		Y.lflag = p->d_lflag[k].as<u8>(); Y.lines = p->d_lines[k].as<FrLine>(); Y.lscan = p->d_lscan[k].as<FrLine>(); Y.hline = p->d_hline[k].as<u32>(); Y.bend = p->d_bend[k].as<u32>();
+		if (cap_lines > X.cap_lines) X.cap_lines = (u32)cap_lines;
+		if (cap_recs < cap_units) cap_units = cap_recs;
+	}
+	A.cap_units = (u32)cap_units;
+	*n_units = cap_units;
+	return p->ensure_shared(A.w[A.nw - 1].tile0 + A.w[A.nw - 1].n_tiles, cap_units);
+}
+
+// fq_launch for FASTA records
+static int fr_launch(bwagpu_fastq_parser_t *p, const FqArgs &A, const FrArgs &X, u32 tiles, u64 cap_units, int chunk_size)
+{
+	u64 *words = p->d_words.as<u64>();
+	FqInfo *d_info = (FqInfo*)(words + FQ_N_WORDS);
+	FqSum *units = p->d_units.as<FqSum>(), *uscan = p->d_uscan.as<FqSum>();
+	FrFmt F; F.X = X;
+	if (p->hip("memset", hipMemsetAsync(words, 0, FQ_N_WORDS * 8, p->st))) return BWAGPU_EHIP;
+	for (int k = 0; k < A.nw; ++k) if (p->hip("memset", hipMemsetAsync(X.x[k].lflag, 0, A.w[k].nl_cap, p->st))) return BWAGPU_EHIP;
+	(void)hipEventRecord(p->ev[0], p->st);
+	if (tiles) {
+		hipLaunchKernelGGL(k_fq_count, dim3(tiles), dim3(FQ_BLOCK), 0, p->st, A, p->d_tcount.as<u64>());
+		if (int rc = p->scan_excl(p->d_tcount.as<u64>(), p->d_tbase.as<u64>(), tiles)) return rc;
+		hipLaunchKernelGGL(k_fr_index, dim3(tiles), dim3(FQ_BLOCK), 0, p->st, A, X, p->d_tbase.as<u64>(), words);
+	}
+	const unsigned lgrid = grid_for(X.cap_lines) < 1024 ? grid_for(X.cap_lines) : 1024;
+	hipLaunchKernelGGL(k_fr_lines, dim3(lgrid), dim3(FQ_BLOCK), 0, p->st, A, X, (const u64*)words);
+	for (int k = 0; k < A.nw; ++k) if (int rc = p->scan_incl(X.x[k].lines, X.x[k].lscan, A.w[k].nl_cap, FrLinePlus())) return rc;
+	hipLaunchKernelGGL(k_fr_place, dim3(lgrid), dim3(FQ_BLOCK), 0, p->st, A, X, words);
+	const unsigned ugrid = grid_for(cap_units) < 1024 ? grid_for(cap_units) : 1024;
+	hipLaunchKernelGGL(k_fr_records, dim3(ugrid), dim3(FQ_BLOCK), 0, p->st, A, F, words, units);
+	(void)hipEventRecord(p->ev[1], p->st);
+	if (int rc = p->scan_incl(units, uscan, cap_units, FqPlus())) return rc;
+	hipLaunchKernelGGL(k_fr_cut, dim3(ugrid), dim3(FQ_BLOCK), 0, p->st, A, F, words, uscan, (u64)chunk_size);
+	hipLaunchKernelGGL(k_fr_decide, dim3(1), dim3(FQ_WAVE), 0, p->st, A, F, (const u64*)words, uscan, d_info);
+	(void)hipEventRecord(p->ev[2], p->st);
+	return 0;
+}
+
+// everything behind the copy-up.  X: the windows hold FASTA records (fr_setup has run): no qualities, and dev_fasta_reads.h's passes
+static int fq_run(bwagpu_fastq_parser_t *p, const FqArgs &A, u32 tiles, u64 cap_units, int chunk_size, bwagpu_fastq_out_t *out, const FrArgs *X = nullptr)
+{
+	if (int rc = X ? fr_launch(p, A, *X, tiles, cap_units, chunk_size) : fq_launch(p, A, tiles, cap_units, chunk_size)) return rc;
 	FqInfo *d_info = (FqInfo*)(p->d_words.as<u64>() + FQ_N_WORDS);
 	const FqSum *uscan = p->d_uscan.as<FqSum>();
 	FqInfo info;
@@ -1001,14 +1055,14 @@ static int fq_run(bwagpu_fastq_parser_t *p, const FqArgs &A, u32 tiles, u64 cap_
 	const u64 ts = info.total.seq, tn = info.total.name, tc = info.total.com;
 	out->seqs = (uint8_t*)bwagpu_alloc_host(ts + 1); out->off = (int64_t*)bwagpu_alloc_host((n_reads + 1) * 8);
 	out->names = (char*)bwagpu_alloc_host(tn + 1); out->name_off = (int64_t*)bwagpu_alloc_host((n_reads + 1) * 8);
-	out->quals = (char*)bwagpu_alloc_host(ts + 1);
+	out->quals = X ? nullptr : (char*)bwagpu_alloc_host(ts + 1);
 	out->comments = (char*)bwagpu_alloc_host(tc + 1); out->comment_off = (int64_t*)bwagpu_alloc_host((n_reads + 1) * 8);
 	out->has_comment = (uint8_t*)bwagpu_alloc_host(n_reads + 1); out->recs = (bwagpu_fastq_rec_t*)bwagpu_alloc_host((n_reads + 1) * sizeof(bwagpu_fastq_rec_t));
 	int rc = 0;
-	if (!out->seqs || !out->off || !out->names || !out->name_off || !out->quals || !out->comments || !out->comment_off || !out->has_comment || !out->recs)
+	if (!out->seqs || !out->off || !out->names || !out->name_off || (!out->quals && !X) || !out->comments || !out->comment_off || !out->has_comment || !out->recs)
 		rc = p->fail(BWAGPU_ENOMEM, "out of host memory (FASTQ batch)");
 	if (!rc && n_reads == 0) { out->off[0] = out->name_off[0] = out->comment_off[0] = 0; return 0; }
-	if (!rc && (p->o_seqs.ensure(ts + 1) || p->o_quals.ensure(ts + 1) || p->o_names.ensure(tn + 1) || p->o_com.ensure(tc + 1) || p->o_off.ensure((n_reads + 1) * 8) ||
+	if (!rc && (p->o_seqs.ensure(ts + 1) || (!X && p->o_quals.ensure(ts + 1)) || p->o_names.ensure(tn + 1) || p->o_com.ensure(tc + 1) || p->o_off.ensure((n_reads + 1) * 8) ||
 				p->o_name_off.ensure((n_reads + 1) * 8) || p->o_com_off.ensure((n_reads + 1) * 8) || p->o_has.ensure(n_reads) || p->o_recs.ensure(n_reads * sizeof(bwagpu_fastq_rec_t))))
 		rc = p->fail(BWAGPU_ENOMEM, "hipMalloc failed (FASTQ outputs)");
 	if (!rc) {
@@ -1016,11 +1070,13 @@ static int fq_run(bwagpu_fastq_parser_t *p, const FqArgs &A, u32 tiles, u64 cap_
 		o.seqs = p->o_seqs.as<u8>(); o.off = p->o_off.as<i64>(); o.names = p->o_names.as<char>(); o.name_off = p->o_name_off.as<i64>(); o.quals = p->o_quals.as<char>();
 		o.comments = p->o_com.as<char>(); o.comment_off = p->o_com_off.as<i64>(); o.has_comment = p->o_has.as<u8>(); o.recs = p->o_recs.as<bwagpu_fastq_rec_t>();
 		const u64 eblocks = (n_reads + FQ_BLOCK / FQ_WAVE - 1) / (FQ_BLOCK / FQ_WAVE);
-		hipLaunchKernelGGL(k_fq_emit, dim3((unsigned)(eblocks < 65536 ? eblocks : 65536)), dim3(FQ_BLOCK), 0, p->st, A, uscan, n_reads, info.total, o);
+		const dim3 egrid((unsigned)(eblocks < 65536 ? eblocks : 65536));
+		if (X) hipLaunchKernelGGL(k_fr_emit, egrid, dim3(FQ_BLOCK), 0, p->st, A, *X, uscan, n_reads, info.total, o);
+		else hipLaunchKernelGGL(k_fq_emit, egrid, dim3(FQ_BLOCK), 0, p->st, A, uscan, n_reads, info.total, o);
 		(void)hipEventRecord(p->ev[3], p->st);
 		auto down = [&](void *dst, const Buf &src, u64 bytes) { return bytes ? p->hip("download", hipMemcpyAsync(dst, src.p, (size_t)bytes, hipMemcpyDeviceToHost, p->st)) : 0; };
 		// wait 2: the copies
-		if (down(out->seqs, p->o_seqs, ts) || down(out->quals, p->o_quals, ts) || down(out->names, p->o_names, tn) || down(out->comments, p->o_com, tc) ||
+		if (down(out->seqs, p->o_seqs, ts) || (!X && down(out->quals, p->o_quals, ts)) || down(out->names, p->o_names, tn) || down(out->comments, p->o_com, tc) ||
 			down(out->off, p->o_off, (n_reads + 1) * 8) || down(out->name_off, p->o_name_off, (n_reads + 1) * 8) || down(out->comment_off, p->o_com_off, (n_reads + 1) * 8) ||
 			down(out->has_comment, p->o_has, n_reads) || down(out->recs, p->o_recs, n_reads * sizeof(bwagpu_fastq_rec_t)) || p->hip("sync", hipStreamSynchronize(p->st)) ||
 			p->hip("FASTQ emit kernel", hipGetLastError())) rc = BWAGPU_EHIP;
@@ -1030,24 +1086,43 @@ static int fq_run(bwagpu_fastq_parser_t *p, const FqArgs &A, u32 tiles, u64 cap_
 	return rc;
 }
 
-extern "C" int bwagpu_fastq_batch(bwagpu_fastq_parser_t *p, const void *raw1, int64_t len1, int eof1, const void *raw2, int64_t len2, int eof2,
-								  int chunk_size, bwagpu_fastq_out_t *out)
+// bwagpu_fastq_batch and bwagpu_fastq_batch_fasta: `what` names the call in the error text
+static int fq_batch(bwagpu_fastq_parser_t *p, const char *what, bool fasta, const void *raw1, int64_t len1, int eof1, const void *raw2, int64_t len2, int eof2,
+					int chunk_size, bwagpu_fastq_out_t *out)
 {
 	const int64_t lim = (int64_t)1 << 31;
 	if (!p) return BWAGPU_EINVAL;
 	if (!out || !raw1 || len1 < 0 || len2 < 0 || len1 >= lim || len2 >= lim || chunk_size <= 0 || (!raw2 && len2 != 0))
-		return p->fail(BWAGPU_EINVAL, "bwagpu_fastq_batch: NULL argument, negative length, window of 2^31 bytes or more, chunk_size <= 0, or a length without a second window");
+		return p->fail(BWAGPU_EINVAL, std::string(what) + ": NULL argument, negative length, window of 2^31 bytes or more, chunk_size <= 0, or a length without a second window");
 	memset(out, 0, sizeof *out);
 	out->declined_file = -1; out->declined_at = -1;
 	p->err.clear();
 	if (hipSetDevice(p->device) != hipSuccess) return p->fail(BWAGPU_ENODEV, "hipSetDevice failed");      // (the caller's thread may be another one than bwagpu_fastq_begin's)
-	FqArgs A;
+	FqArgs A; FrArgs X;
 	const void *raw[2] = { raw1, raw2 }; const u64 len[2] = { (u64)len1, (u64)len2 }; const int eof[2] = { eof1, eof2 };
 	u32 tiles = 0; u64 cap_units = 0;
 	if (int rc = fq_setup(p, A, raw2 ? 2 : 1, len, eof, &tiles, &cap_units)) return rc;
+	if (fasta) if (int rc = fr_setup(p, A, X, &cap_units)) return rc;
 	for (int k = 0; k < A.nw; ++k)
 		if (len[k] && p->hip("copy window", hipMemcpyAsync(p->d_buf[k].p, raw[k], (size_t)len[k], hipMemcpyHostToDevice, p->st))) return BWAGPU_EHIP;
-	return fq_run(p, A, tiles, cap_units, chunk_size, out);
+	return fq_run(p, A, tiles, cap_units, chunk_size, out, fasta ? &X : nullptr);
+}
+
+extern "C" int bwagpu_fastq_batch(bwagpu_fastq_parser_t *p, const void *raw1, int64_t len1, int eof1, const void *raw2, int64_t len2, int eof2,
+								  int chunk_size, bwagpu_fastq_out_t *out)
+{
+	return fq_batch(p, "bwagpu_fastq_batch", false, raw1, len1, eof1, raw2, len2, eof2, chunk_size, out);
+}
+
+extern "C" int bwagpu_fastq_batch_fasta(bwagpu_fastq_parser_t *p, const void *raw1, int64_t len1, int eof1, const void *raw2, int64_t len2, int eof2,
+										int chunk_size, bwagpu_fastq_out_t *out)
+{
+	return fq_batch(p, "bwagpu_fastq_batch_fasta", true, raw1, len1, eof1, raw2, len2, eof2, chunk_size, out);
+}
+
+extern "C" void bwagpu_fasta_reads_limits(int32_t out[4])
+{
+	out[0] = FQ_TILE; out[1] = FQ_SEG; out[2] = FR_STEP; out[3] = 0;
 }
 
 // ---- BGZF windows -> text (dev_bgzf.h) ---------------------------------------------------------------------------------------------
@@ -1219,19 +1294,37 @@ static int bz_batch(bwagpu_fastq_parser_t *p, const bwagpu_bgzf_win_t *const w[2
 	return 0;
 }
 
-extern "C" int bwagpu_fastq_batch_bgzf(bwagpu_fastq_parser_t *p, const bwagpu_bgzf_win_t *w1, const bwagpu_bgzf_win_t *w2, int chunk_size,
-									   bwagpu_fastq_out_t *out, bwagpu_bgzf_info_t info[2])
+// bwagpu_fastq_batch_bgzf and bwagpu_fastq_batch_fasta_bgzf
+static int fq_batch_bgzf(bwagpu_fastq_parser_t *p, const char *what, bool fasta, const bwagpu_bgzf_win_t *w1, const bwagpu_bgzf_win_t *w2, int chunk_size,
+						 bwagpu_fastq_out_t *out, bwagpu_bgzf_info_t info[2])
 {
 	if (!p) return BWAGPU_EINVAL;
 	const bwagpu_bgzf_win_t *w[2] = { w1, w2 };
 	const int nw = w2 ? 2 : 1;
 	bool ok = w1 && out && info && chunk_size > 0;
 	for (int k = 0; ok && k < nw; ++k) ok = w[k]->comp && w[k]->comp_len >= 0 && w[k]->skip >= 0;
-	if (!ok) return p->fail(BWAGPU_EINVAL, "bwagpu_fastq_batch_bgzf: NULL argument, negative length or skip, or chunk_size <= 0");
+	if (!ok) return p->fail(BWAGPU_EINVAL, std::string(what) + ": NULL argument, negative length or skip, or chunk_size <= 0");
 	memset(out, 0, sizeof *out);
 	out->declined_file = -1; out->declined_at = -1;
 	p->err.clear();
-	return bz_batch(p, w, nw, info, &out->status, out->consumed, [&](const FqArgs &A, u32 tiles, u64 cap_units) { return fq_run(p, A, tiles, cap_units, chunk_size, out); });
+	return bz_batch(p, w, nw, info, &out->status, out->consumed, [&](const FqArgs &A, u32 tiles, u64 cap_units) {
+		if (!fasta) return fq_run(p, A, tiles, cap_units, chunk_size, out);
+		FqArgs B = A; FrArgs X;
+		if (int rc = fr_setup(p, B, X, &cap_units)) return rc;
+		return fq_run(p, B, tiles, cap_units, chunk_size, out, &X);
+	});
+}
+
+extern "C" int bwagpu_fastq_batch_bgzf(bwagpu_fastq_parser_t *p, const bwagpu_bgzf_win_t *w1, const bwagpu_bgzf_win_t *w2, int chunk_size,
+									   bwagpu_fastq_out_t *out, bwagpu_bgzf_info_t info[2])
+{
+	return fq_batch_bgzf(p, "bwagpu_fastq_batch_bgzf", false, w1, w2, chunk_size, out, info);
+}
+
+extern "C" int bwagpu_fastq_batch_fasta_bgzf(bwagpu_fastq_parser_t *p, const bwagpu_bgzf_win_t *w1, const bwagpu_bgzf_win_t *w2, int chunk_size,
+											 bwagpu_fastq_out_t *out, bwagpu_bgzf_info_t info[2])
+{
+	return fq_batch_bgzf(p, "bwagpu_fastq_batch_fasta_bgzf", true, w1, w2, chunk_size, out, info);
 }
 
 // ---- one window of interleaved reads -> single reads and pairs (dev_fastq_smart.h) ------------------------------------------------

@@ -166,6 +166,11 @@ IDX_DEVFN u64 fq_n_good(const FqArgs &A, const u64 *words, int k, bool *has_bad)
 }
 // window offset at which record g of window k starts
 IDX_DEVFN u32 fq_start(const FqWin &W, u64 g) { return g ? W.nl[4 * g - 1] + 1u : 0u; }
+// how the cut and the status see a window of plain FASTQ records (dev_fasta_reads.h has the FASTA one)
+struct FqPlainFmt {
+	IDX_DEVFN u64 n_good(const FqArgs &A, const u64 *words, int k, bool *has_bad) const { return fq_n_good(A, words, k, has_bad); }
+	IDX_DEVFN u32 start(const FqArgs &A, const u64 *, int k, u64 g) const { return fq_start(A.w[k], g); }
+};
 
 // pass 2: one lane per unit (record i of every window).  units[i]: the lengths its records add to the batch (zero past the last
 // complete candidate of any window, so that the scan may run over cap_units entries)
@@ -205,19 +210,22 @@ __global__ void __launch_bounds__(FQ_BLOCK) k_fq_records(FqArgs A, u64 *words, F
 
 // pass 3a: the unit behind which bseq_read closes the batch (bwa.c:104): the first one with sum(l_seq) >= chunk -- at an even
 // read count, which two windows always have.  uscan: inclusive scan of units.  Sums do not decrease, so exactly one lane finds it.
-__global__ void __launch_bounds__(FQ_BLOCK) k_fq_cut(FqArgs A, u64 *words, const FqSum *uscan, u64 chunk)
+template <class Fmt>
+IDX_DEVFN void fq_cut_unit(const FqArgs &A, const Fmt &F, u64 *words, const FqSum *uscan, u64 chunk)
 {
 	u64 P = ~0ull;
-	for (int k = 0; k < A.nw; ++k) { const u64 g = fq_n_good(A, words, k, nullptr); if (g < P) P = g; }
+	for (int k = 0; k < A.nw; ++k) { const u64 g = F.n_good(A, words, k, nullptr); if (g < P) P = g; }
 	for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < P; i += (u64)gridDim.x * blockDim.x) {
 		if (uscan[i].seq < chunk || (i && uscan[i - 1].seq >= chunk)) continue;
 		const u64 c = (A.nw > 1 || (i & 1)) ? i : i + 1;
 		if (c < P) words[FQ_W_CUT] = c + 1;
 	}
 }
+__global__ void __launch_bounds__(FQ_BLOCK) k_fq_cut(FqArgs A, u64 *words, const FqSum *uscan, u64 chunk) { fq_cut_unit(A, FqPlainFmt(), words, uscan, chunk); }
 
 // pass 3b (one lane): status, batch size and totals
-__global__ void __launch_bounds__(FQ_WAVE) k_fq_decide(FqArgs A, const u64 *words, const FqSum *uscan, FqInfo *info)
+template <class Fmt>
+IDX_DEVFN void fq_decide_status(const FqArgs &A, const Fmt &F, const u64 *words, const FqSum *uscan, FqInfo *info)
 {
 	if (blockIdx.x || threadIdx.x) return;
 	enum { HAS, BAD, SHORT, ENDED };
@@ -225,31 +233,33 @@ __global__ void __launch_bounds__(FQ_WAVE) k_fq_decide(FqArgs A, const u64 *word
 	o.status = BWAGPU_FQ_MORE; o.n_units = 0; o.consumed[0] = o.consumed[1] = 0; o.declined_file = -1; o.declined_at = -1;
 	o.total.seq = o.total.name = o.total.com = 0;
 	u64 good[2] = { 0, 0 }, P = ~0ull;
-	bool has_bad[2] = { false, false };
-	for (int k = 0; k < A.nw; ++k) { good[k] = fq_n_good(A, words, k, &has_bad[k]); if (good[k] < P) P = good[k]; }
+	for (int k = 0; k < A.nw; ++k) { good[k] = F.n_good(A, words, k, nullptr); if (good[k] < P) P = good[k]; }
 	if (words[FQ_W_CUT]) { o.status = BWAGPU_FQ_CUT; o.n_units = (i64)words[FQ_W_CUT]; }
 	else {
 		int st[2] = { ENDED, ENDED };
 		for (int k = 0; k < A.nw; ++k) {
 			const FqWin &W = A.w[k];
+			bool has_bad = false;
+			(void)F.n_good(A, words, k, &has_bad);
 			if (good[k] > P) st[k] = HAS;
-			else if (has_bad[k]) st[k] = BAD;
-			else if (W.n - fq_start(W, P) > 0) st[k] = W.eof ? BAD : SHORT;      // an incomplete last record
+			else if (has_bad) st[k] = BAD;
+			else if (W.n - F.start(A, words, k, P) > 0) st[k] = W.eof ? BAD : SHORT;      // an incomplete last record
 			else st[k] = W.eof ? ENDED : SHORT;
 		}
 		int decl = -1;
 		for (int k = A.nw - 1; k >= 0; --k) if (st[k] == BAD) decl = k;
 		if (decl < 0 && st[0] != SHORT && st[1] != SHORT && A.nw > 1 && st[0] != st[1]) decl = st[0] == HAS ? 0 : 1;   // one file ended, the other has records left
-		if (decl >= 0) { o.status = BWAGPU_FQ_DECLINED; o.declined_file = decl; o.declined_at = (i64)fq_start(A.w[decl], P); }
+		if (decl >= 0) { o.status = BWAGPU_FQ_DECLINED; o.declined_file = decl; o.declined_at = (i64)F.start(A, words, decl, P); }
 		else if (st[0] == SHORT || (A.nw > 1 && st[1] == SHORT)) o.status = BWAGPU_FQ_MORE;
 		else { o.status = BWAGPU_FQ_END; o.n_units = (i64)P; }
 	}
 	if (o.n_units) {
 		o.total = uscan[o.n_units - 1];
-		for (int k = 0; k < A.nw; ++k) o.consumed[k] = (i64)fq_start(A.w[k], (u64)o.n_units);
+		for (int k = 0; k < A.nw; ++k) o.consumed[k] = (i64)F.start(A, words, k, (u64)o.n_units);
 	}
 	*info = o;
 }
+__global__ void __launch_bounds__(FQ_WAVE) k_fq_decide(FqArgs A, const u64 *words, const FqSum *uscan, FqInfo *info) { fq_decide_status(A, FqPlainFmt(), words, uscan, info); }
 
 // where pass 4 writes
 struct FqOut {

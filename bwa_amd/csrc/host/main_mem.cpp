@@ -50,6 +50,7 @@ static int g_device_samtext = 0;  // BWAGPU_CLI_SAMTEXT=1: single-end batches wi
                                   // Paired-end batches, under BWAGPU_CLI_SAMPE's conditions (whether or not that switch is set): bwagpu_batch_sam_pe in place of every device call behind the download; a pair the device declines runs the host's mem_sam_pe on the download's lists
 static std::atomic<long> g_n_samtext_reads(0);   // ... reads written from such text
 static int g_device_bgzf = 0;     // BWAGPU_CLI_BGZF_DEV=1 (with BWAGPU_CLI_FASTQ=1): BGZF files (all of them; -p with BWAGPU_CLI_SMARTPE_DEV=1 only) go to the device compressed and are inflated there (bwagpu_fastq_batch_bgzf)
+static int g_device_fasta = 0;    // BWAGPU_CLI_FASTA_DEV=1 (with BWAGPU_CLI_FASTQ=1, not with -p): files whose text starts with '>' (all of them; BGZF ones with BWAGPU_CLI_BGZF_DEV=1) are FASTA read files, parsed on the device as well (bwagpu_fastq_batch_fasta): no qualities
 static int g_device_smartpe = 0;  // BWAGPU_CLI_SMARTPE_DEV=1 (with BWAGPU_CLI_FASTQ=1 and -p): the interleaved file is parsed, classified (bseq_classify) and split into its single-end and paired-end sub-batches on the device (bwagpu_fastq_batch_smart; a BGZF file with BWAGPU_CLI_BGZF_DEV=1 too)
 static int g_device_fastq = 0;    // BWAGPU_CLI_FASTQ=1: plain FASTQ files (one or two; -p with BWAGPU_CLI_SMARTPE_DEV=1 only) are parsed on the device (bwagpu_fastq_batch): records, bseq_read's cut, base codes and the name / quality / comment
                                   // blobs of BWAGPU_CLI_SAMTEXT come from there; a batch the device declines, and the input behind it, goes through the reader below (same output)
@@ -423,6 +424,27 @@ struct DevInput {
 	bwagpu_fastq_parser_t *p = nullptr;
 	int nf = 0; std::string path[2]; int fd[2] = { -1, -1 }; const char *map[2] = { nullptr, nullptr }; size_t size[2] = { 0, 0 }, pos[2] = { 0, 0 };
 	bool fallback = false;
+	bool fasta = false;      // BWAGPU_CLI_FASTA_DEV: the files are FASTA (every one starts with '>'): the batches come from bwagpu_fastq_batch_fasta / _bgzf, without qualities
+	// the first byte of a BGZF file's text (-1: none, or a first block that does not inflate)
+	static int bgzf_first_byte(const unsigned char *m, size_t n) {
+		for (size_t o = 0; o < n;) {
+			const size_t bl = BgzfPipe::block_len(m + o, n - o);
+			if (!bl) return -1;
+			const size_t xlen = m[o + 10] | (size_t)m[o + 11] << 8;
+			if (m[o + bl - 4] | m[o + bl - 3] | m[o + bl - 2] | m[o + bl - 1]) {      // ISIZE > 0
+				z_stream z; memset(&z, 0, sizeof z);
+				if (inflateInit2(&z, -15) != Z_OK) return -1;
+				unsigned char c = 0;
+				z.next_in = const_cast<unsigned char*>(m + o + 12 + xlen); z.avail_in = (uInt)(bl - 12 - xlen - 8); z.next_out = &c; z.avail_out = 1;
+				(void)inflate(&z, Z_SYNC_FLUSH);
+				const bool got = z.avail_out == 0;
+				inflateEnd(&z);
+				return got ? (int)c : -1;
+			}
+			o += bl;
+		}
+		return -1;
+	}
 	// BWAGPU_CLI_BGZF_DEV: the files are BGZF.  The position of a file is a BGZF virtual offset -- pos[k]: a block's offset in the file, uoff[k]: the byte in that block's text --, a
 	// window is compressed bytes from pos[k]: the chunk's three text bytes per base divided by the compression ratio (the first batch), then what the last batch took and a quarter, plus slack for the blocks at both ends, doubled on MORE
 	bool bgzf = false; size_t uoff[2] = { 0, 0 }, last_comp = 0; double ratio = 3.0; long n_bgzf_blocks = 0;
@@ -447,6 +469,10 @@ struct DevInput {
 			map[k] = (const char*)mp;
 			ParFile::guard_mapped_input(map[k], size[k]);
 		}
+		// FASTA or FASTQ, all of one kind (a mix stays with the host reader)
+		const bool fa = g_device_fasta && !smart && size[k] > 0 && (z ? bgzf_first_byte((const unsigned char*)map[k], size[k]) : (int)(unsigned char)map[k][0]) == '>';
+		if (k > 0 && fa != fasta) { munmap((void*)map[k], size[k]); map[k] = nullptr; ::close(f); return false; }
+		fasta = fa;
 		fd[k] = f; path[k] = fn;
 		return true;
 	}
@@ -468,7 +494,7 @@ struct DevInput {
 			{
 				std::unique_lock<std::mutex> serial(g_dev_mutex, std::defer_lock);
 				if (g_dev_serialize) serial.lock();
-				rc = bwagpu_fastq_batch_bgzf(p, &w[0], nf > 1 ? &w[1] : nullptr, chunk, o.get(), info);
+				rc = (fasta ? bwagpu_fastq_batch_fasta_bgzf : bwagpu_fastq_batch_bgzf)(p, &w[0], nf > 1 ? &w[1] : nullptr, chunk, o.get(), info);
 			}
 			if (rc != BWAGPU_OK) { fprintf(stderr, "[E::%s] bwagpu_fastq_batch_bgzf: %s: %s\n", "main_mem", bwagpu_strerror(rc), bwagpu_fastq_last_error(p)); fflush(stderr); fflush(stdout); _exit(EXIT_FAILURE); }
 			if (o->status == BWAGPU_FQ_DAMAGED) {
@@ -503,7 +529,9 @@ struct DevInput {
 			s.name = a; s.l_name = (int)ln; memcpy(A + a, r->names + r->name_off[i], ln); a += ln; A[a++] = 0;
 			s.comment = a; s.has_comment = r->has_comment[i] != 0; memcpy(A + a, r->comments + r->comment_off[i], lc); a += lc; A[a] = 0;
 			s.seq = a++;
-			s.qual = a; s.l_seq = (int)ls; s.l_qual = (int)ls; s.has_qual = true; memcpy(A + a, r->quals + r->off[i], ls); A[a + ls] = 0;
+			s.qual = a; s.l_seq = (int)ls;
+			if (r->quals) { s.l_qual = (int)ls; s.has_qual = true; memcpy(A + a, r->quals + r->off[i], ls); A[a + ls] = 0; }
+			else { s.l_qual = 0; s.has_qual = false; A[a] = 0; }      // (FASTA)
 		});
 		off.assign(o->off, o->off + n + 1);
 		{ HostBuf b; b.p = o->seqs; b.cap = (size_t)o->off[n] + 1; o->seqs = nullptr; flat = std::move(b); }
@@ -587,7 +615,7 @@ struct DevInput {
 			{
 				std::unique_lock<std::mutex> serial(g_dev_mutex, std::defer_lock);
 				if (g_dev_serialize) serial.lock();
-				rc = bwagpu_fastq_batch(p, map[0] ? map[0] + pos[0] : "", (int64_t)len[0], eof[0], nf > 1 ? (map[1] ? map[1] + pos[1] : "") : nullptr, (int64_t)len[1], eof[1], chunk, o.get());
+				rc = (fasta ? bwagpu_fastq_batch_fasta : bwagpu_fastq_batch)(p, map[0] ? map[0] + pos[0] : "", (int64_t)len[0], eof[0], nf > 1 ? (map[1] ? map[1] + pos[1] : "") : nullptr, (int64_t)len[1], eof[1], chunk, o.get());
 			}
 			if (rc != BWAGPU_OK) { fprintf(stderr, "[E::%s] bwagpu_fastq_batch: %s: %s\n", "main_mem", bwagpu_strerror(rc), bwagpu_fastq_last_error(p)); fflush(stderr); fflush(stdout); _exit(EXIT_FAILURE); }
 			if (o->status == BWAGPU_FQ_MORE) {
@@ -615,7 +643,7 @@ struct DevInput {
 			s.name = a; s.l_name = e.l_name; memcpy(A + a, src + e.name, (size_t)e.l_name); a += (size_t)e.l_name; A[a++] = 0;
 			s.comment = a; s.has_comment = e.has_comment != 0; memcpy(A + a, src + e.comment, (size_t)e.l_comment); a += (size_t)e.l_comment; A[a] = 0;
 			s.seq = a++;                                         // (the bases exist as codes only: an empty string here)
-			s.qual = a; s.l_seq = e.l_seq; s.l_qual = e.l_qual; s.has_qual = true; memcpy(A + a, src + e.qual, (size_t)e.l_qual); A[a + (size_t)e.l_qual] = 0;
+			s.qual = a; s.l_seq = e.l_seq; s.l_qual = e.l_qual; s.has_qual = e.qual >= 0; if (s.has_qual) memcpy(A + a, src + e.qual, (size_t)e.l_qual); A[a + (size_t)e.l_qual] = 0;      // (FASTA: qual -1, l_qual 0)
 		});
 		off.assign(o->off, o->off + n + 1);
 		{ HostBuf b; b.p = o->seqs; b.cap = (size_t)o->off[n] + 1; o->seqs = nullptr; flat = std::move(b); }      // (the codes' block goes where encode_sub's would: bwagpu_alloc_host's pool either way)
@@ -701,7 +729,7 @@ static bool sam_in_of_shard(const Sub &u, const Batch &in, int lo, int hi, bool 
 			const int64_t a = f.name_off[i - 1], b = f.name_off[i], c = f.name_off[i + 1];
 			if (b - a != c - b || memcmp(f.names + a, f.names + b, (size_t)(b - a)) != 0) return false;
 		}
-		si.names = f.names; si.name_off = f.name_off + lo; si.quals = f.quals + u.off[lo];
+		si.names = f.names; si.name_off = f.name_off + lo; si.quals = f.quals ? f.quals + u.off[lo] : nullptr;      // (no qualities: FASTA reads)
 		if (g_dev_copy_comment) { si.comments = f.comments; si.comment_off = f.comment_off + lo; }
 		return true;
 	}
@@ -1195,6 +1223,7 @@ int main(int argc, char *argv[])
 	// BWAGPU_CLI_FASTQ: the device parser and its window buffers, before the suffix array below is sized against the free memory
 	g_device_fastq = env_int("BWAGPU_CLI_FASTQ", g_device_fastq);
 	g_device_bgzf = env_int("BWAGPU_CLI_BGZF_DEV", g_device_bgzf);
+	g_device_fasta = env_int("BWAGPU_CLI_FASTA_DEV", g_device_fasta);
 	std::unique_ptr<DevInput> dev_in;
 	g_device_smartpe = env_int("BWAGPU_CLI_SMARTPE_DEV", g_device_smartpe);
 	if (g_device_fastq && (!(opt.flag & F_SMARTPE) || g_device_smartpe) && !getenv("BWAGPU_CLI_PARSE_ONLY")) {

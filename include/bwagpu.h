@@ -721,6 +721,39 @@ int  bwagpu_fastq_batch_bgzf(bwagpu_fastq_parser_t *p, const bwagpu_bgzf_win_t *
                              int chunk_size, bwagpu_fastq_out_t *out, bwagpu_bgzf_info_t info[2]);
 
 /* ---- interleaved input: `mem -p' ("smart pairing"), on the same parser ------------------------------------------------------------ */
+/* ---- FASTA read files on the same parser (the FASTA half of kseq_read, kseq.h:175-204) ---------------------------------------- */
+/* bwagpu_fastq_batch_fasta: bwagpu_fastq_batch for windows of FASTA text -- the same arguments, BWAGPU_EINVAL cases, statuses,
+ * consumed, declined_file / declined_at, result pool and two host waits; bwagpu_fastq_batch_fasta_bgzf is its BGZF twin, with
+ * bwagpu_fastq_batch_bgzf's arguments, BWAGPU_FQ_DAMAGED and third wait.  A window starts at a record start, a '>'; the call returns the
+ * batch bseq_read(chunk_size) would cut from there.  The existing entry points are unchanged: they decline every '>' record.
+ * The rule for FASTA records.  A line is what lies between two '\n', or between one '\n' and the end of the window; its first byte
+ * says what it is:
+ *   '>'        a header: the name up to the first isspace() byte (trim_readno applied); when there is such a byte, the comment is the
+ *              rest of the line, less one trailing '\r' if it is longer than one byte (ks_getuntil2, kseq.h:140);
+ *   no byte    an empty line: skipped (kseq.h:193);
+ *   '@'        the start of a FASTQ record: that record is declined;
+ *   '+'        the record holding the line is declined;
+ *   any other  a sequence line of the record whose header precedes it: its bytes are bases, less a '\r' at its end when the line has two
+ *              bytes or more.  A NUL, a byte >= 0x80 or a byte <= ' ' anywhere else in it declines the record.
+ * A record ends where the next header line starts, or at the window's end with eof; empty lines behind its bases belong to it, so that
+ * consumed at BWAGPU_FQ_END is the window's length.  Declined as well: a record without bases (a '>' with nothing behind it at eof
+ * included) and a window that does not start with '>' (at offset 0).  A line that is only "\r": behind a base of its record and before a
+ * '\n' it adds nothing, as in the reference (a CRLF file's empty line); as its record's first sequence line, or as the stream's last
+ * line without a '\n', the reference keeps the '\r' as a base, and the device declines the record.  A last line of one base without a
+ * '\n' is read like any other line.
+ * BWAGPU_FQ_CUT needs the end of the batch's last record in view -- the next header line's first byte, or eof -- otherwise the status is
+ * BWAGPU_FQ_MORE.  Two windows must both be FASTA.
+ * Output: bwagpu_fastq_out_t as it is, with quals == NULL (bseq_read leaves qual NULL, SAM prints '*').  In recs, qual = -1 and
+ * l_qual = 0; seq is the window offset of the read's first base byte and l_seq the number of bases: the bases are the window's bytes
+ * from seq on, line ends skipped.  kernel_ms: line passes, cut, emit.
+ * bwagpu_fasta_reads_limits: bytes per tile, bytes per lane of the byte passes, body bytes per step of the emit pass, 0. */
+int  bwagpu_fastq_batch_fasta(bwagpu_fastq_parser_t *p, const void *raw1, int64_t len1, int eof1,
+                              const void *raw2 /* NULL: one file */, int64_t len2, int eof2,
+                              int chunk_size, bwagpu_fastq_out_t *out);
+int  bwagpu_fastq_batch_fasta_bgzf(bwagpu_fastq_parser_t *p, const bwagpu_bgzf_win_t *w1, const bwagpu_bgzf_win_t *w2 /* NULL: one file */,
+                                   int chunk_size, bwagpu_fastq_out_t *out, bwagpu_bgzf_info_t info[2]);
+void bwagpu_fasta_reads_limits(int32_t out[4]);
+
 /* bwagpu_fastq_batch_smart: bwagpu_fastq_batch on ONE window, followed on the device by bseq_classify (bwa.c:114-130) and the split
  * fastmap.c:94-105 makes of the batch: reads whose name equals the next or the last read's form pairs, the others are single, and
  * mem_process_seqs runs on the single reads first and on the pairs second.  The whole batch is the one a one-window bwagpu_fastq_batch
