@@ -37,6 +37,8 @@ DEVFN int opaque_lane() { int l = (int)(threadIdx.x & 63); DEV_KEEP(l); return l
 #define DPP_WAVE_SHR1 0x138
 
 DEVFN int imax(int a, int b) { return a > b ? a : b; }
+DEVFN int wmin(int a, int b) { return a < b ? a : b; }
+DEVFN u32 umin32(u32 a, u32 b) { return a < b ? a : b; }
 // Sums and differences over columns a lane merely reads along with the live ones (the {H,E} slots past the band's end hold whatever the
 // LDS held before): the result is discarded, but it must be a defined one -- two's-complement wrap-around, the instruction the signed
 // forms compile to anyway (found by UBSan on the mock runtime in the multi-pass rows: stale slots of INT_MIN; the code object is the same
@@ -80,6 +82,17 @@ DEVFN int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }   // pin a wa
 DEVFN u64 wave_ballot(bool p) { return __builtin_amdgcn_ballot_w64(p); }
 #else
 DEVFN u64 wave_ballot(bool p) { return __ballot(p); }
+#endif
+// Bit scans of a lane mask as the scalar unit does them: one instruction each, -1 for an empty mask (the C builtins are undefined there, and a guarded
+// form costs a second instruction in the row loops); and "set bit b", which the compiler builds from a shift and an OR.
+#ifdef __HIP_DEVICE_COMPILE__
+DEVFN int mask_first(u64 m) { int r; asm("s_ff1_i32_b64 %0, %1" : "=s"(r) : "s"(m)); return r; }          // number of the lowest set bit
+DEVFN int mask_lead(u64 m) { int r; asm("s_flbit_i32_b64 %0, %1" : "=s"(r) : "s"(m)); return r; }         // zero bits above the highest set bit
+DEVFN u64 mask_set(u64 m, int b) { asm("s_bitset1_b64 %0, %1" : "+s"(m) : "s"(b)); return m; }           // (b < 64)
+#else
+DEVFN int mask_first(u64 m) { return m ? __builtin_ctzll(m) : -1; }
+DEVFN int mask_lead(u64 m) { return m ? __builtin_clzll(m) : -1; }
+DEVFN u64 mask_set(u64 m, int b) { return m | 1ull << (b & 63); }
 #endif
 DEVFN i64 uni64(i64 v)
 {
@@ -226,7 +239,7 @@ template <bool RING> __device__ ExtRes wave_ksw_extend2(const DevIndex &ix, cons
 	const int lane_e = lane * e_ins;
 	// The single-pass rows ("window rows", the form 150 bp reads spend most of their rows in).  The kernel is bound by instruction issue, the
 	// scalar unit first (round 3: 85 scalar and 62 vector instructions per row, one scalar unit per CU against four vector units), so the form is
-	// written for few of both:
+	// written for few of both (one column per lane: 48 vector, 21 scalar instructions and one branch a row; two columns: 79, 38 and one -- profiles/ext_rows.md):
 	//  * lanes keep their columns.  While the band fits the 64 columns [base, base + 64) lane L owns column base + L and keeps its {H, E} slot
 	//    in two registers from row to row -- the slot is read and written by that lane only (H(i,j) reaches column j + 1 by a lane shift) -- so a
 	//    row touches LDS once, for its score.  Lanes outside the band leave their registers alone, which IS the reference's stale-cell rule;
@@ -234,8 +247,9 @@ template <bool RING> __device__ ExtRes wave_ksw_extend2(const DevIndex &ix, cons
 	//  * the band is a pair of lane numbers [lo, hi) and the trimming (ksw.c:502-505) two bit scans of ONE ballot: bit L = column base + L holds
 	//    a non-zero {h, e}, the column `end` (lane hi, which stores {H(i,end-1), 0}, ksw.c:485) included.
 	//  * F's offsets j * e_ins shrink to lane * e_ins: the row's common term cancels between the scan's input and output.  Lanes below the band
-	//    feed the scan its identity, so the first column's F is far below zero instead of the reference's 0 -- H = max(M, E, F) is the same
-	//    number, because E >= 0 everywhere.  Lanes outside the band shift out H = 0, the reference's h1 for beg > 0.
+	//    feed the scan -1, below every live column's term (an inline constant, where W_NEG took a register), so the first column's F is at most
+	//    zero like the reference's 0 -- H = max(M, E, F) is the same number, because E >= 0 everywhere.  Lanes outside the band shift out H = 0,
+	//    the reference's h1 for beg > 0.
 	//  * the row maximum is taken over max(M, E) instead of H = max(M, E, F): F(i,j) <= max(0, max_k M(i,k) - oe_ins) lies strictly below a
 	//    positive row maximum, so neither the maximum nor the "last column wins" choice (ksw.c:473-474) changes, and the two six-step DPP
 	//    chains interleave instead of idling between dependent steps.  The scan's key carries the ABSOLUTE column (score << 11 | column).
@@ -246,6 +260,15 @@ template <bool RING> __device__ ExtRes wave_ksw_extend2(const DevIndex &ix, cons
 	//    together, one lane per row: prefix maxima give every row the (max, max_i, max_j) it would have seen, the first z-drop hit ends the
 	//    extension there (the rows computed past it are simply not counted; the next call re-initialises the columns they wrote), and the
 	//    survivors update the state.
+	//  * one counter and one exit.  The rows of a segment -- up to the next multiple of 64 rows (new reference bases), the 32nd parked row or the target's
+	//    end -- run in a loop whose only counter is the row index i: the lane a row is parked in is compared as lane + i0 + 1 == i + 1, the reference
+	//    bases wait in treg as offsets into the query profile (base * qs), and the loop's four exits (m == 0, an empty band or one that no longer fits
+	//    the form, the segment's last row) are the sign bit of one OR.  What the exit was is read afterwards from key, lo and hi.  The to-end score is
+	//    read every row (lane hi always exists) and replaced by -1 where the band does not touch the query's end.
+	//  * the band's clamps (ksw.c:447-448: beg >= i - w, end <= i + w + 1) are applied between segments, not in the rows: a segment is cut short so
+	//    that neither can bind before its last row -- with mem_chain2aln's bands (w = 100 and its doublings) that is almost never, a band of small w
+	//    gets segments of one row.  Stats runs count a segment's cells the same way and take one-row segments throughout: slower, and only there.
+	//  * the band's bit scans are the scalar unit's own instructions (mask_first, mask_lead, mask_set above).
 	const bool win_ok = !RING && qlen < 2048 && h0 + qlen * mat_max < (1 << 20);      // (score << 11 | column) must fit the scan's 31 bits
 	int hist_k = 0, hist_h1 = -1, hist_n = 0, hist_row0 = 0;
 	auto hist_flush = [&]() -> bool {       // returns true when a parked row ended the extension by z-drop
@@ -301,6 +324,9 @@ template <bool RING> __device__ ExtRes wave_ksw_extend2(const DevIndex &ix, cons
 		return g_run >= 0 && B <= m_run && B < g_run;
 	};
 	int i = 0;
+	// the reference bases of rows i .. i + 63, a lane each.  Short reads keep them as offsets into the query profile (base * qs): a row's score address is one lane read away
+	const int tscale = RING ? 1 : qs;
+	auto load_treg = [&]() { const int ii = i + lane; treg = ii < tlen ? ref_base(ix, t0 + (i64)ii * tdir) * tscale : 0; };
 	while (i < tlen) {
 		if (beg < i - w) beg = i - w;
 		if (end > i + w + 1) end = i + w + 1;
@@ -310,61 +336,75 @@ template <bool RING> __device__ ExtRes wave_ksw_extend2(const DevIndex &ix, cons
 		if (win_ok && end > beg && end - beg <= 63) {
 			const int base = beg, jcol = base + lane;
 			int sth, ste; { const int2 t = eh[jcol]; sth = t.x; ste = t.y; }      // this lane's {H, E} slot (the LDS region is padded by 64 columns)
-			const int8_t *qcol = qp + q0 + jcol * qdir;       // column jcol's score is qcol[tb * qs] (lanes past the band read the profile's padding or its neighbourhood, never past the wave's LDS)
+			const int8_t *qcol = qp + q0 + jcol * qdir;       // column jcol's score is qcol[tb * qs], tb * qs being what treg holds (lanes past the band read the profile's padding or its neighbourhood, never past the wave's LDS)
 			const int e_lane = lane == 0 ? W_NEG : e_ins - lane_e;           // (lane 0 has no column to its left: the shift hands it 0, this makes its F the scan's identity)
 			const int qhi = qlen - base;
 			// H(i,-1) = max(h0 - (o_del + e_del * (i + 1)), 0) (ksw.c:452-455), the value column 0's left neighbour hands over: lane 0 of a window that starts at
-			// column 0 counts it down; every other lane, and every lane of a window further right, shifts in H = 0
+			// column 0 counts it down; every other lane, and every lane of a window further right, shifts in H = 0 (they count down too, from W_NEG: one
+			// subtraction of a scalar for all lanes, and no per-lane step to keep in a register)
 			int hdl = lane == 0 && base == 0 ? h0 - (o_del + e_del * (i + 1)) : W_NEG;
-			const int edel0 = lane == 0 ? e_del : 0;
-			int lo = 0, hi = end - base, lo_min = i - w - base, hi_max = i + w + 1 - base;
+			const int c_lo = -w - base, c_hi = w + 1 - base;  // the band's clamps (ksw.c:447-448) as lane numbers relative to the row: lo >= i + c_lo, hi <= i + c_hi
+			int lo = 0, hi = end - base;
 			hi = uni(hi);                                     // (without the pin the compiler carries the row loop's control in vector registers and branches on exec masks)
-			int why = 0;                                      // 1: the extension ends (m == 0 or z-drop), 2: the band has left the window
-			do {
-				// a segment: rows up to the next multiple of 64 (the reference bases in treg), the 32nd parked row, or the last row
-				if ((i & 63) == 0) { const int ii = i + lane; treg = ii < tlen ? ref_base(ix, t0 + (i64)ii * tdir) : 0; }
-				int i_end = (i | 63) + 1; if (i_end > tlen) i_end = tlen; if (i_end > i + 32 - hist_n) i_end = i + 32 - hist_n;
-				if (i >= tail_from && i_end > i + 2) i_end = i + 2;
-				i_end = uni(i_end);
-				int sc_next = qcol[__builtin_amdgcn_readlane(treg, i & 63) * qs];
-				int key;
+			// the rows of one segment, from row i to the first row that ends it; returns that row's key.
+			auto rows = [&](const int i_end, const int lane_i1) -> int {
+				int sc_next = qcol[__builtin_amdgcn_readlane(treg, i & 63)];
+				DEV_KEEP(sc_next);                                    // (or this load and the row loop's are folded into one at the loop's head, where every row would wait for it)
+				int key, nact = hi - lo, mk = m_run << 11;
 				for (;;) {
 					const int sc = sc_next;
-					sc_next = qcol[__builtin_amdgcn_readlane(treg, (i + 1) & 63) * qs];   // the next row's score, in flight while this row computes (past the segment's end: read and dropped)
-					const int nact = hi - lo;
+					const int i1 = uni(i + 1);                        // (the one counter of the loop: without the pin the compiler splits it into three, an instruction a row each)
+					sc_next = qcol[__builtin_amdgcn_readlane(treg, i1 & 63)];   // the next row's score, in flight while this row computes (past the segment's end: read and dropped)
 					const unsigned rel = (unsigned)(lane - lo);
 					const bool act = rel < (unsigned)nact, wr = rel <= (unsigned)nact;
 					const int M = sth ? sth + sc : 0;          // ksw.c:469: a dead diagonal cell stays dead
 					const int hme = imax(M, ste);
 					const int kmax = wave_incl_scan_max(act ? (hme << 11 | jcol) : -1);
-					const int inc = wave_incl_scan_max(act ? imax(M - oe_ins, 0) + lane_e : W_NEG);
+					const int inc = wave_incl_scan_max(act ? imax(M - oe_ins, 0) + lane_e : -1);
 					const int exc = __builtin_amdgcn_update_dpp(0, inc, DPP_WAVE_SHR1, 0xf, 0xf, true);     // best insertion start left of this column
 					const int h = act ? imax(hme, exc + e_lane) : 0;             // H(i,j) = max(M, E, F), ksw.c:470-471
 					const int e_new = act ? imax(imax(ste - e_del, M - oe_del), 0) : 0;   // E(i+1,j), ksw.c:475-479
 					const int hleft = imax(__builtin_amdgcn_update_dpp(0, h, DPP_WAVE_SHR1, 0xf, 0xf, true), hdl);   // eh[j].h after this row = H(i,j-1)
-					hdl -= edel0;
+					hdl -= e_del;
 					sth = wr ? hleft : sth; ste = wr ? e_new : ste;
 					const u64 nz = wave_ballot((hleft | e_new) != 0) & wave_ballot(wr);      // (two compare masks and a scalar AND: the ballot of a conjunction is rebuilt from 0/1 values)
 					key = __builtin_amdgcn_readlane(kmax, 63);
-					hist_k = lane == hist_n ? key : hist_k;
-					m_run = imax(m_run, key >> 11);
-					if (hi == qhi) {                                  // H(i, end-1) feeds the to-end score (ksw.c:486-489); rows that do not touch the query's end leave the -1 of the last flush
-						const int h1 = __builtin_amdgcn_readlane(hleft, hi);
-						hist_h1 = lane == hist_n ? h1 : hist_h1;
-						g_run = imax(g_run, h1);
-					}
-					++hist_n; ++i; cells32 += (u32)nact;
-					if (key < 2048) break;                           // m == 0 (ksw.c:490)
-					// band for the next row (ksw.c:502-505): skip leading / trailing columns whose {h,e} are both zero (m > 0, so nz != 0), then its clamps
-					lo = __builtin_ctzll(nz | 1ull << hi);
-					hi = 65 - __builtin_clzll(nz); if (hi > qhi) hi = qhi;
-					++lo_min; ++hi_max;
-					if (lo < lo_min) lo = lo_min;
-					if (hi > hi_max) hi = hi_max;
-					if (hi > 63) break;
-					if (hi <= lo) break;
-					if (i == i_end) break;
+					const bool park = lane_i1 == i1;                    // the lane this row's bookkeeping is parked in
+					hist_k = park ? key : hist_k;
+					mk = imax(mk, key);
+					// H(i, end-1) feeds the to-end score when the band touches the query's end (ksw.c:486-489); any other row parks the -1 the last flush left
+					int h1 = __builtin_amdgcn_readlane(hleft, hi);
+					h1 = hi == qhi ? h1 : -1;
+					hist_h1 = park ? h1 : hist_h1;
+					g_run = imax(g_run, h1);
+					i = i1;
+					// band for the next row (ksw.c:502-505): skip leading / trailing columns whose {h,e} are both zero, then its clamps.  (m == 0 may leave nz empty:
+					// the row ends the extension and its band is not used.)
+					const int lead = mask_lead(nz);
+					lo = mask_first(mask_set(nz, hi));
+					hi = 65 - lead;
+					hi = wmin(hi, qhi);
+					nact = hi - lo;
+					// one exit for four reasons, each a sign bit: m == 0 (ksw.c:490; key = m << 11 | column), an empty band, a band past lane 63, the segment's last row
+					if (((key - 2048) | (nact - 1) | (63 - hi) | (i_end - 1 - i1)) < 0) break;
 				}
+				m_run = mk >> 11;
+				return key;
+			};
+			int why = 0;                                      // 1: the extension ends (m == 0 or z-drop), 2: the band has left the window
+			do {
+				// a segment: rows up to the next multiple of 64 (the reference bases in treg), the 32nd parked row, or the last row
+				if ((i & 63) == 0) load_treg();
+				const int hist_i0 = i - hist_n;                   // row r is parked in lane r - hist_i0
+				int i_end = (i | 63) + 1; if (i_end > tlen) i_end = tlen; if (i_end > hist_i0 + 32) i_end = hist_i0 + 32;
+				if (i >= tail_from && i_end > i + 2) i_end = i + 2;
+				if (i_end > 1 - c_lo) i_end = imax(1 - c_lo, i + 1);
+				if (i + 1 + c_hi < wmin(qhi, 65) || L.stat) i_end = i + 1;
+				i_end = uni(i_end);
+				cells32 += (u32)(hi - lo);
+				const int key = rows(i_end, lane + hist_i0 + 1);
+				hist_n = i - hist_i0;
+				lo = imax(lo, i + c_lo); hi = wmin(hi, i + c_hi);
 				if (key < 2048) why = 1;
 				else {
 					if (hi > 63 || hi <= lo) why = 2;
@@ -397,33 +437,29 @@ template <bool RING> __device__ ExtRes wave_ksw_extend2(const DevIndex &ix, cons
 			const int e_laneA = lane == 0 ? W_NEG : e_ins - lane_e2;
 			const int qhi = qlen - base;
 			int hdl = lane == 0 && base == 0 ? h0 - (o_del + e_del * (i + 1)) : W_NEG;
-			const int edel0 = lane == 0 ? e_del : 0;
-			int lo = 0, hi = end - base, lo_min = i - w - base, hi_max = i + w + 1 - base;
+			const int c_lo = -w - base, c_hi = w + 1 - base;
+			int lo = 0, hi = end - base;
 			hi = uni(hi);
-			int why = 0;
-			do {
-				if ((i & 63) == 0) { const int ii = i + lane; treg = ii < tlen ? ref_base(ix, t0 + (i64)ii * tdir) : 0; }
-				int i_end = (i | 63) + 1; if (i_end > tlen) i_end = tlen; if (i_end > i + 32 - hist_n) i_end = i + 32 - hist_n;
-				if (i >= tail_from && i_end > i + 2) i_end = i + 2;
-				i_end = uni(i_end);
-				int scA_next, scB_next; { const int o = __builtin_amdgcn_readlane(treg, i & 63) * qs; scA_next = qcA[o]; scB_next = qcB[o]; }
-				int key;
+			auto rows = [&](const int i_end, const int lane_i1) -> int {
+				int scA_next, scB_next; { const int o = __builtin_amdgcn_readlane(treg, i & 63); scA_next = qcA[o]; scB_next = qcB[o]; }
+				DEV_KEEP(scA_next); DEV_KEEP(scB_next);
+				int key, nact = hi - lo, mk = m_run << 11;
 				for (;;) {
 					const int scA = scA_next, scB = scB_next;
-					{ const int o = __builtin_amdgcn_readlane(treg, (i + 1) & 63) * qs; scA_next = qcA[o]; scB_next = qcB[o]; }
-					const int nact = hi - lo;
+					const int i1 = uni(i + 1);                        // (the one counter of the loop: without the pin the compiler splits it into three, an instruction a row each)
+					{ const int o = __builtin_amdgcn_readlane(treg, i1 & 63); scA_next = qcA[o]; scB_next = qcB[o]; }
 					const unsigned relA = (unsigned)(2 * lane - lo), relB = relA + 1;
 					const bool actA = relA < (unsigned)nact, wrA = relA <= (unsigned)nact, actB = relB < (unsigned)nact, wrB = relB <= (unsigned)nact;
 					const int MA = shA ? shA + scA : 0, MB = shB ? shB + scB : 0;          // ksw.c:469
 					const int hmA = imax(MA, seA), hmB = imax(MB, seB);
 					const int kmax = wave_incl_scan_max(imax(actA ? (hmA << 11 | jA) : -1, actB ? (hmB << 11 | jB) : -1));   // last column wins ties (ksw.c:473-474)
-					const int aA = actA ? imax(MA - oe_ins, 0) + lane_e2 : W_NEG, aB = actB ? imax(MB - oe_ins, 0) + lane_e2 + e_ins : W_NEG;
+					const int aA = actA ? imax(MA - oe_ins, 0) + lane_e2 : -1, aB = actB ? imax(MB - oe_ins, 0) + lane_e2 + e_ins : -1;      // (-1: below every live column's term, as above)
 					const int exc = __builtin_amdgcn_update_dpp(0, wave_incl_scan_max(imax(aA, aB)), DPP_WAVE_SHR1, 0xf, 0xf, true);   // best insertion start among the columns of the lanes below
 					const int hA = actA ? imax(hmA, exc + e_laneA) : 0;                         // ksw.c:470-471
 					const int hB = actB ? imax(hmB, imax(exc, aA) - lane_e2) : 0;
 					const int eA = actA ? imax(imax(seA - e_del, MA - oe_del), 0) : 0, eB = actB ? imax(imax(seB - e_del, MB - oe_del), 0) : 0;   // ksw.c:475-479
 					const int hleftA = imax(__builtin_amdgcn_update_dpp(0, hB, DPP_WAVE_SHR1, 0xf, 0xf, true), hdl);   // H(i, A - 1): the lane below's column B
-					hdl -= edel0;
+					hdl -= e_del;
 					shA = wrA ? hleftA : shA; seA = wrA ? eA : seA;
 					shB = wrB ? hA : shB; seB = wrB ? eB : seB;
 					const u64 mwA = wave_ballot(wrA), mwB = wave_ballot(wrB);
@@ -431,29 +467,41 @@ template <bool RING> __device__ ExtRes wave_ksw_extend2(const DevIndex &ix, cons
 					// column `end` (in one of the two write masks, in neither set of live columns) stands in for "none" in the search from the left
 					const u64 xA = nzA | (mwA & ~wave_ballot(actA)), xB = nzB | (mwB & ~wave_ballot(actB));
 					key = __builtin_amdgcn_readlane(kmax, 63);
-					hist_k = lane == hist_n ? key : hist_k;
-					m_run = imax(m_run, key >> 11);
-					if (hi == qhi) {                                  // H(i, end-1), what column `end` has just stored (ksw.c:485-489)
-						const int h1 = (hi & 1) ? __builtin_amdgcn_readlane(hA, hi >> 1) : __builtin_amdgcn_readlane(hleftA, hi >> 1);
-						hist_h1 = lane == hist_n ? h1 : hist_h1;
-						g_run = imax(g_run, h1);
-					}
-					++hist_n; ++i; cells32 += (u32)nact;
-					if (key < 2048) break;                           // m == 0 (ksw.c:490)
+					const bool park = lane_i1 == i1;
+					hist_k = park ? key : hist_k;
+					mk = imax(mk, key);
+					// H(i, end-1), what column `end` has just stored (ksw.c:485-489): column hi is lane hi / 2's A or B
+					const int h1A = __builtin_amdgcn_readlane(hleftA, hi >> 1), h1B = __builtin_amdgcn_readlane(hA, hi >> 1);
+					int h1 = (hi & 1) ? h1B : h1A;
+					h1 = hi == qhi ? h1 : -1;
+					hist_h1 = park ? h1 : hist_h1;
+					g_run = imax(g_run, h1);
+					i = i1;
 					// band for the next row (ksw.c:502-505), lane-wise: the first lane with a non-zero column (or column `end`) and whether that is its A, the last
-					// lane with a non-zero column and whether that is its B (m > 0, so there is one)
-					{
-						const int lf = __builtin_ctzll(xA | xB), ll = 63 - __builtin_clzll(nzA | nzB);
-						lo = 2 * lf + 1 - (int)(xA >> lf & 1);
-						hi = 2 * ll + (int)(nzB >> ll & 1) + 2; if (hi > qhi) hi = qhi;
-					}
-					++lo_min; ++hi_max;
-					if (lo < lo_min) lo = lo_min;
-					if (hi > hi_max) hi = hi_max;
-					if (hi > 127) break;
-					if (hi - lo <= 63) break;                        // (narrow enough for a column per lane, or empty)
-					if (i == i_end) break;
+					// lane with a non-zero column and whether that is its B (none when m == 0: that row's band is not used)
+					lo = (int)umin32(2u * (u32)mask_first(xA), 2u * (u32)mask_first(xB) | 1u);               // (an empty mask's -1 doubles to the largest numbers)
+					hi = 129 - (int)umin32(2u * (u32)mask_lead(nzA) | 1u, 2u * (u32)mask_lead(nzB));           // column 2 (63 - lead) + 2 for an A, + 3 for a B
+					hi = wmin(hi, qhi);
+					nact = hi - lo;
+					// one exit, a sign bit per reason: m == 0 (ksw.c:490), a band narrow enough for a column per lane (or empty), a band past column 127, the segment's last row
+					if (((key - 2048) | (nact - 64) | (127 - hi) | (i_end - 1 - i1)) < 0) break;
 				}
+				m_run = mk >> 11;
+				return key;
+			};
+			int why = 0;
+			do {
+				if ((i & 63) == 0) load_treg();
+				const int hist_i0 = i - hist_n;
+				int i_end = (i | 63) + 1; if (i_end > tlen) i_end = tlen; if (i_end > hist_i0 + 32) i_end = hist_i0 + 32;
+				if (i >= tail_from && i_end > i + 2) i_end = i + 2;
+				if (i_end > 1 - c_lo) i_end = imax(1 - c_lo, i + 1);
+				if (i + 1 + c_hi < wmin(qhi, 129) || L.stat) i_end = i + 1;
+				i_end = uni(i_end);
+				cells32 += (u32)(hi - lo);
+				const int key = rows(i_end, lane + hist_i0 + 1);
+				hist_n = i - hist_i0;
+				lo = imax(lo, i + c_lo); hi = wmin(hi, i + c_hi);
 				if (key < 2048) why = 1;
 				else {
 					if (hi > 127 || hi - lo <= 63) why = 2;
@@ -476,9 +524,9 @@ template <bool RING> __device__ ExtRes wave_ksw_extend2(const DevIndex &ix, cons
 			beg = base + lo; end = base + hi;
 			continue;
 		}
-		if ((i & 63) == 0) { int ii = i + lane; treg = ii < tlen ? ref_base(ix, t0 + (i64)ii * tdir) : 0; }
-		const int tb = __builtin_amdgcn_readlane(treg, i & 63);
-		const int8_t *qrow = qp + tb * qs + q0;        // column j's score is qrow[j * qdir]
+		if ((i & 63) == 0) load_treg();
+		const int tb = __builtin_amdgcn_readlane(treg, i & 63);       // (short reads: the base times qs)
+		const int8_t *qrow = qp + tb + q0;             // column j's score is qrow[j * qdir]
 		if (RING) {      // first-row values (ksw.c:430-433) for the columns this row can reach for the first time
 			int hi = i + w + 2 < qlen ? i + w + 2 : qlen;
 			if (hi > init_hi) {
