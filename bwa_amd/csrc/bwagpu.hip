@@ -268,6 +268,7 @@ static bool option_in_range(const BwagpuConfig &c, const long long *f, long long
 	if (f == &c.dedup_ring) return value == 0 || (in(256, 4096) && (value & (value - 1)) == 0);
 	if (f == &c.cigl_mib) return in(0, 1 << 20);
 	if (f == &c.cig_tiers || f == &c.chain_regs) return in(0, 2);
+	if (f == &c.seed_jump) return in(-1, 3);
 	if (f == &c.chain_flt_lds) return in(0, CW_FLT_LDS);
 	if (f == &c.ptab_m) return in(0, PTAB_MAX);
 	if (f == &c.occ32_sb_shift) return in(8, 32);
@@ -351,7 +352,10 @@ __global__ void __launch_bounds__(256) k_ptab_level(DevIndex ix, u64 *tab, int j
 	}
 }
 
-// records: for every m-mer W the packed bi-intervals of its m prefixes, gathered from the level tables
+// records: for every m-mer W the packed bi-intervals of its m prefixes, gathered from the level tables.  The entry of the j-base prefix
+// carries, in the 16 bits the packing leaves for `info`, the CHANGE BITS of its own prefixes: bit k-1 = the (k+1)-base prefix has another
+// interval size than the k-base one, 1 <= k < j.  Sizes never grow with depth, so two depths have equal sizes exactly when no change bit
+// lies between them: what a sweep's steps below the tables' depth ask of the index (dev_seed.h, option seed_jump), from one entry.
 __global__ void __launch_bounds__(256) k_ptab_records(const u64 *tab, uint4 *rec, int m)
 {
 	const u64 n = ((u64)1 << (2 * m)) * (u64)m;
@@ -359,6 +363,12 @@ __global__ void __launch_bounds__(256) k_ptab_records(const u64 *tab, uint4 *rec
 		const u64 w = t / (u64)m; const int j = (int)(t % (u64)m) + 1;
 		const u64 *e = tab + ((((u64)1 << (2 * j)) - 4) / 3 + (w >> (2 * (m - j)))) * 3;
 		BiIntv v; v.x0 = e[0]; v.x1 = e[1]; v.x2 = e[2]; v.info = 0;
+		u64 deeper = v.x2;
+		for (int k = j - 1; k >= 1; --k) {
+			const u64 x2 = tab[((((u64)1 << (2 * k)) - 4) / 3 + (w >> (2 * (m - k)))) * 3 + 2];
+			if (x2 != deeper) v.info |= (u64)1 << (k - 1);
+			deeper = x2;
+		}
 		rec[t] = SeedStack::pack(v);
 	}
 }
@@ -773,6 +783,15 @@ extern "C" int bwagpu_debug_prof(bwagpu_t *h, unsigned long long out[16])
 	for (int i = 0; i < 16; ++i) out[i] = c.prof[i];
 	out[8] = c.n_vr_ovf + c.prof[8];       // long-read batches: tasks of pass 1 that were redone on full-size interval stacks; short-read batches: extensions k_ext_pack answered (the one is 0 where the other counts)
 	out[0] = c.n_heavy; out[1] = c.n_p2_tasks;       // short-read batches: reads whose passes 1-2 ran as tasks, and their pass-2 searches
+	return BWAGPU_OK;
+}
+
+// the prefix tables as the kernels read them (DevIndex::ptab): *m = their depth, *bytes = their size; with `out` given, that many bytes are copied there
+extern "C" int bwagpu_debug_ptab(bwagpu_t *h, int32_t *m, uint64_t *bytes, void *out)
+{
+	if (!h || !m || !bytes) return BWAGPU_EINVAL;
+	*m = h->ix.ptab ? h->ix.ptab_m : 0; *bytes = h->ix.ptab ? h->ix.ptab_bytes : 0;
+	if (out && *bytes && hipMemcpy(out, h->ix.ptab, *bytes, hipMemcpyDeviceToHost) != hipSuccess) return BWAGPU_EHIP;
 	return BWAGPU_OK;
 }
 
@@ -1249,6 +1268,7 @@ extern "C" int bwagpu_batch_run(bwagpu_t *h, const bwagpu_opt_t *opt)
 		B.seed_prio = cfg.seed_prio != 0;
 		B.ext_blk = cfg.ext_blk != 0;
 		B.seed_no_virt = cfg.seed_no_virt != 0;
+		B.seed_jump = cfg.seed_jump < 0 ? 3 : (int)cfg.seed_jump;
 		B.seed_pass3_inline = cfg.seed_pass3_inline != 0;
 		B.task_step = opt->min_seed_len; B.n_vreads = n_vreads; B.vr_ovf_run = 0; B.vr_room = 0; B.seed_stack_cap = 0; B.intv_n3 = nullptr;
 		if (seed_tasks) { B.vr_first = h->d_vr_tab.as<i32>(); B.vr_ovf = h->d_vr_ovf.as<i32>(); B.intv_n3 = h->d_intv_n3.as<i32>(); }

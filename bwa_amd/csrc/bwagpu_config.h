@@ -33,6 +33,7 @@
 	X(seed_lds_ent,      -1)   /* seeding: interval-stack entries per lane kept in LDS; auto: 10, or what the read copy leaves                          */ \
 	X(seed_rd_lds,       1)    /* seeding: short reads copied to LDS at 2 bits per base                                                                 */ \
 	X(seed_no_virt,      0)    /* seeding: keep matches shorter than the prefix tables' depth in the stack too (diagnostics)                            */ \
+	X(seed_jump,         -1)   /* seeding: a sweep's steps below the prefix tables' depth answered from ONE table entry and its change bits (k_ptab_records): bit 1 = forward sweeps and k_seed3, bit 2 = the short entries of a backward row; 0 = step by step everywhere (A/B and tests); auto: 3 */ \
 	X(seed_prio,         1)    /* seeding: raised issue priority for the waves holding the heaviest reads                                               */ \
 	X(seed_input_order,  0)    /* seeding: reads in input order instead of heaviest first (diagnostics)                                                 */ \
 	X(seed_pass3_inline, 0)    /* seeding: pass 3 inside k_seed's state machine instead of k_seed3 (A/B)                                                */ \

@@ -170,6 +170,7 @@ struct Batch {
 	int seed_stack_cap;        // entries of a lane's spill area (0: max_len + 1 + PTAB_MAX, the worst case; the task launch of long-read batches: small)
 	int seed_lds_ent;          // stack entries per lane kept in LDS (0 when seq_len >= 2^37 or max_len >= 2^16: the packing would not fit)
 	int seed_no_virt;          // diagnostics: keep short matches in the stack as well (see SeedLane::smask)
+	int seed_jump;             // option seed_jump: bit 1 = forward sweeps and k_seed3 enter at the prefix tables' depth, bit 2 = a backward row's short entries from one look-up (0: step by step)
 	int mem_cap;               // capacity of one read's interval list
 	// --- seeding results
 	i32 *seed_w;               // per read: repetitiveness weight left by k_seed3 (sum of seed-length match occurrences)

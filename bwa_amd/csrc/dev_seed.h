@@ -92,6 +92,7 @@ struct SeedStack {
 	DEVFN BiIntv *glob_col() const { return glob_base + (size_t)(blockIdx.x * blockDim.x + threadIdx.x) * (size_t)glob_cap + PTAB_MAX; }   // (a backward row may add one entry at the deep end, see SeedLane::smask)
 	int stride, n_lds;   // n_lds == 0: intervals not packable for this batch, everything in glob (unpacked)
 	int virt_m;          // matches of fewer bases live in SeedLane::smask instead (0: none do)
+	int jump;            // Batch::seed_jump where virt_m > 0 (else 0): bit 1 = a forward sweep's first virt_m - 1 steps, bit 2 = a backward row's short entries, from one table entry
 	// forward sweep: an entry of the change-point list
 	DEVFN void push_fw(SeedLane &L, const BiIntv &v) const {
 		const int len = (int)v.info - L.sx;
@@ -192,6 +193,16 @@ __global__ void __launch_bounds__(256) k_pack_reads2b(Batch B)
 	}
 }
 
+DEVFN u32 rev32(u32 x)
+{
+#ifdef __clang__
+	return __builtin_bitreverse32(x);
+#else
+	x = (x >> 1 & 0x55555555u) | (x & 0x55555555u) << 1; x = (x >> 2 & 0x33333333u) | (x & 0x33333333u) << 2; x = (x >> 4 & 0x0f0f0f0fu) | (x & 0x0f0f0f0fu) << 4;
+	return __builtin_bswap32(x);
+#endif
+}
+
 DEVFN void smem_finish(SeedLane &L) { if (L.pass == 1) { L.x = L.ret; L.st = SS_PASS1; } else L.st = SS_PASS2; }
 
 // start backward row i (bwt.c:326-345); rows without a usable base (i < 0 or N) need no extension at all
@@ -257,11 +268,19 @@ template <bool WIN = false> DEVFN int ext_one_trip(const DevIndex &ix, const See
 }
 
 // 2-bit code of q[x..x+m), first base most significant; N and positions past the read's end read as 0 (no match that the
-// tables are asked about extends over them)
-DEVFN u32 window_code(SeedLane &L, const u64 *nib, int x, int m)
+// tables are asked about extends over them).  `partial` (may be null): the window holds an N or runs past the read's end -- a
+// sweep that enters at the tables' depth (option seed_jump) needs all m bases.
+#define SEED_JUMP_FLAG 0x80000000u      // SeedLane::smask of a forward sweep whose first extension is the look-up at the tables' depth
+DEVFN u32 window_code(SeedLane &L, const u64 *nib, int x, int m, bool *partial = nullptr)
 {
-	u32 rc = 0;
-	for (int k = 0; k < m; ++k) { const int g = x + k; rc = rc << 2 | (u32)((g < L.len ? seed_q(L, nib, g) : 0) & 3); }
+	u32 rc = 0; bool part = false;
+	for (int k = 0; k < m; ++k) {
+		const int g = x + k;
+		const int c = g < L.len ? seed_q(L, nib, g) : 4;
+		if (c > 3) part = true;
+		rc = rc << 2 | (u32)(c & 3);
+	}
+	if (partial) *partial = part;
 	return rc;
 }
 
@@ -273,7 +292,14 @@ DEVFN void smem_start(const DevIndex &ix, SeedLane &L, const SeedStack &S, const
 	if (c0 > 3) { L.ret = x + 1; smem_finish(L); return; }   // bwt.c:296
 	fm_init(ix, c0, L.ik); L.ik.info = (u64)(x + 1);
 	L.i = x + 1; L.n0 = 0; L.slot = 0; L.smask = 0;
-	L.code = window_code(L, nib, x, ix.ptab_m);
+	bool partial;
+	L.code = window_code(L, nib, x, ix.ptab_m, &partial);
+	if ((S.jump & 1) && !partial) {
+		// The first virt_m - 1 steps can only push entries that live in smask -- at the depths where the interval size changes -- and stop
+		// the sweep where the size falls below min_intv.  The entry of the whole window answers both: its size is the smallest of them,
+		// its change bits are those pushes.  So the sweep's first extension is the look-up at the tables' depth (SS_FWD sees the flag).
+		L.i = x + S.virt_m - 1; L.smask = SEED_JUMP_FLAG; L.st = SS_FWD;
+	} else
 	if (L.i >= L.len || seed_q(L, nib, L.i) > 3) {                          // nothing (more) to extend: push and go backward
 		S.push_fw(L, L.ik); L.ret = (int)L.ik.info;
 		fwd_finish(L, S, nib, ix.ptab_m);
@@ -484,6 +510,7 @@ __global__ void __launch_bounds__(256, OCC) k_seed(DevIndex ix, bwagpu_opt_t opt
 	S.lds_base = seed_lds; S.stride = blockDim.x; S.n_lds = B.seed_lds_ent;
 	S.glob_base = B.tmp_intv; S.glob_cap = cap;
 	S.virt_m = (ix.ptab_m >= 2 && opt.min_seed_len > ix.ptab_m && !B.seed_no_virt) ? ix.ptab_m : 0;
+	S.jump = S.virt_m > 0 ? B.seed_jump : 0;
 	L.smask = L.srem = L.snew = 0; L.ncl = 0;
 	L.em.intv = B.intv; L.em.r = -1; L.em.cap = B.mem_cap; L.em.min_seed_len = opt.min_seed_len;
 	L.em.split_len = split_len; L.em.split_width = (u64)opt.split_width; L.em.cand = 0; L.em.base = 0; L.em.shared_n = LR == 1 ? B.intv_n : nullptr;
@@ -692,7 +719,7 @@ __global__ void __launch_bounds__(256, OCC) k_seed(DevIndex ix, bwagpu_opt_t opt
 		BiIntv ok, src, p;        // p: the stack entry a backward step extends (it lives for this iteration only)
 		p.x0 = p.x1 = p.x2 = p.info = 0;
 		const int back = st == SS_BWD;
-		bool short_ent = false;
+		bool short_ent = false, first_short = false;
 		int cb = 0, tl = 0;
 		ok.x0 = ok.x1 = ok.x2 = ok.info = 0; src = ok;
 		if (ext) {
@@ -702,6 +729,7 @@ __global__ void __launch_bounds__(256, OCC) k_seed(DevIndex ix, bwagpu_opt_t opt
 					if (MRG == 2 && pf.w != 0) p = SeedStack::unpack(pf); else p = S.load(L, L.j);
 				} else {                                 // the stack's entries are done: the short ones, longest first
 					const int len = 32 - __clz((int)L.srem);
+					first_short = (S.jump & 2) && L.srem == L.smask;      // the longest of the row's short entries
 					L.srem &= ~(1u << (len - 1));
 					p.x0 = p.x1 = p.x2 = 0; p.info = (u64)(L.i + 1 + len); short_ent = true;
 				}
@@ -755,17 +783,23 @@ __global__ void __launch_bounds__(256, OCC) k_seed(DevIndex ix, bwagpu_opt_t opt
 				L.st = SS_FINAL;
 			} else
 			if (st == SS_FWD) {           // forward sweep of bwt_smem1a (bwt.c:304-320)
-				bool stop = false;
-				if (ok.x2 != L.ik.x2) {
-					S.push_fw(L, L.ik); L.ret = (int)L.ik.info;
-					if (ok.x2 < L.min_intv) stop = true;
+				const bool jumped = (L.smask & SEED_JUMP_FLAG) != 0;      // (smem_start) this was the look-up of the whole window
+				if (jumped && ok.x2 < L.min_intv) { L.smask = 0; L.i = L.sx + 1; }      // the sweep stops inside the window (a re-seeding search on a frequent m-mer, an m-mer the genome does not hold): step by step from the start
+				else {
+					bool stop = false;
+					if (jumped) L.smask = (u32)ok.info;      // the pushes of the steps not taken: the entry's change bits (none of them stops: sizes only fall)
+					else if (ok.x2 != L.ik.x2) {
+						S.push_fw(L, L.ik); L.ret = (int)L.ik.info;
+						if (ok.x2 < L.min_intv) stop = true;
+					}
+					if (!stop) {
+						ok.info = (u64)(L.i + 1); L.ik = ok; ++L.i;
+						if (L.i >= L.len || seed_q(L, nib, L.i) > 3) { S.push_fw(L, L.ik); L.ret = (int)L.ik.info; stop = true; }
+					}
+					if (stop) fwd_finish(L, S, nib, ix.ptab_m);
 				}
-				if (!stop) {
-					ok.info = (u64)(L.i + 1); L.ik = ok; ++L.i;
-					if (L.i >= L.len || seed_q(L, nib, L.i) > 3) { S.push_fw(L, L.ik); L.ret = (int)L.ik.info; stop = true; }
-				}
-				if (stop) fwd_finish(L, S, nib, ix.ptab_m);
 			} else if (st == SS_BWD) {    // one interval of one backward row (bwt.c:328-342)
+				const u32 chg = (u32)ok.info;      // (a table entry's change bits)
 				if (ok.x2 < L.min_intv) {
 					if (L.nc == 0 && (!L.any || L.i + 1 < L.last_start)) {
 						L.em.add(p.x0, p.x2, L.i + 1, (int)p.info); L.any = true; L.last_start = L.i + 1;
@@ -776,6 +810,17 @@ __global__ void __launch_bounds__(256, OCC) k_seed(DevIndex ix, bwagpu_opt_t opt
 					if (nl < S.virt_m) L.snew |= 1u << (nl - 1);
 					else { S.store(L, L.ncl, ok); ++L.ncl; }   // in place: ncl <= j, or one past the deep end for a short entry that has grown up
 					++L.nc; L.last_x2 = ok.x2;
+				}
+				if (first_short && L.srem && ok.x2 >= L.min_intv) {
+					// The row's longest short entry has survived: the shorter ones, prefixes of the same window, are at least as frequent and survive
+					// too, and each is kept where its size differs from that of the entry before it (bwt.c:340) -- where a change bit of the
+					// look-up just made lies between the two depths.  Entry bit b (b + 2 bases once extended) after entry bit b' asks for a bit in
+					// (b, b'].  On reversed words, with the change bits moved up by one, those are fields that end in the entry's own bit, and
+					// adding the mask of the bits below it carries into that bit where the field holds a one.
+					const int b1 = (int)p.info - L.i - 2;
+					const u32 rs = rev32(L.srem), below = ~(rs | 0x80000000u >> b1), c2 = rev32((chg & ((2u << b1) - 1)) >> 1);
+					const u32 kept = rev32((((c2 & below) + below) | c2) & rs);
+					L.snew |= kept << 1; L.nc += __popc(kept); L.srem = 0;
 				}
 				if (!short_ent) ++L.j;
 				if (L.j >= L.nprev && L.srem == 0) {
@@ -845,6 +890,7 @@ template <int BLK, bool MRG = false> __global__ void __launch_bounds__(256, 3) k
 	enum { T_FETCH = 0, T_START, T_EXT, T_DONE };
 	int st = T_FETCH, pool_base = 0, pool_cnt = 0;
 	u32 nblk = 0, ntab = 0, weight = 0;
+	const bool jump = (B.seed_jump & 1) && ix.ptab_m >= 2 && ix.ptab_m <= opt.min_seed_len;      // option seed_jump
 	SeedBufs bf;
 	if (MRG && BLK == 1) { bf.occ = occ32_bufs(ix); bf.ptab = buf_rsrc(ix.ptab, ix.ptab_bytes); bf.stk = buf_rsrc(nullptr, 0); bf.nib = bf.stk; }
 	while (__ballot(st != T_DONE)) {
@@ -878,7 +924,12 @@ template <int BLK, bool MRG = false> __global__ void __launch_bounds__(256, 3) k
 				st = T_FETCH;
 			} else {
 				fm_init(ix, seed_q(L, nib, L.x), L.ik); L.sx = L.x; L.i = L.x + 1;
-				L.code = window_code(L, nib, L.x, ix.ptab_m);
+				bool partial;
+				L.code = window_code(L, nib, L.x, ix.ptab_m, &partial);
+				// the steps below the tables' depth neither emit nor stop (tl <= ptab_m <= min_seed_len), and the window's own entry holds
+				// what they lead to, empty intervals included: the walk enters there
+				if (jump && !partial) { L.i = L.x + ix.ptab_m - 1; st = T_EXT; }
+				else
 				if (L.i >= L.len) L.x = L.len;
 				else if (seed_q(L, nib, L.i) > 3) L.x = L.i + 1;
 				else st = T_EXT;

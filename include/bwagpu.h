@@ -215,6 +215,10 @@ int bwagpu_debug_hist(bwagpu_t *h, unsigned long long out[256]);
 /* Diagnostics (stats on): the seeding kernel's index-block look-ups by interval size.  out[0] / out[1] = forward / backward extension steps that read
  * index blocks, out[2] / out[3] = those whose interval is a single row (a unique match), out[4] / out[5] = maximal runs of such steps. */
 int bwagpu_debug_seed_x2(bwagpu_t *h, unsigned long long out[8]);
+/* Diagnostics: the prefix tables as the seeding kernels read them.  *m = their depth (0: none), *bytes = 16 m 4^m; with `out` non-NULL the entries are
+ * copied there: entry [W * m + j - 1] = the j-base prefix of m-mer W (first base most significant) as four 32-bit words -- the low words of x0, x1, x2, then
+ * their bits 32..36 in 5-bit fields and, in the top 16 bits, the prefix's change bits (bit k-1: its (k+1)-base prefix has another size than its k-base one). */
+int bwagpu_debug_ptab(bwagpu_t *h, int32_t *m, uint64_t *bytes, void *out);
 /* Diagnostics (stats on): the chaining kernel's reads by size and form.  out[t * 64 + b] = reads whose seeds were chained in form t (0: in registers,
  * 1: in the B-tree) with 16 b .. 16 b + 15 chains (before the chain filter) (b = 31: more); out[t * 64 + 32 + b] = with 32 b .. 32 b + 31 seeds.
  * out[128 .. 136] = the kernel's wave time in 10 ns ticks by phase (seed loop in registers, in the tree, repeat fraction + in-order list, weights, sort,
