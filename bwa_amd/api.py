@@ -741,6 +741,14 @@ class BgzfInfo(C.Structure):
         return {k: (float(getattr(self, k)) if k == "inflate_ms" else int(getattr(self, k))) for k, _ in self._fields_}
 
 
+class BgzfOutInfo(C.Structure):
+    """bwagpu_bgzf_out_info_t"""
+    _fields_ = [("n_blocks", C.c_int64), ("text_len", C.c_int64), ("comp_len", C.c_int64), ("deflate_ms", C.c_float)]
+
+    def as_dict(self) -> dict:
+        return {k: (float(getattr(self, k)) if k == "deflate_ms" else int(getattr(self, k))) for k, _ in self._fields_}
+
+
 class FastqParser:
     """The device FASTQ reader (bwagpu_fastq_*): windows of FASTQ text in, the batch bseq_read would cut from them out.  It needs no index.
     lib_path selects another build of the library (the CPU tests pass the mock-runtime one); there is no CPU implementation."""
@@ -753,6 +761,9 @@ class FastqParser:
         L.bwagpu_fastq_batch.argtypes = [P, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p]
         L.bwagpu_bgzf_inflate.argtypes = [P, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]
         L.bwagpu_fastq_batch_bgzf.argtypes = [P, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.bwagpu_bgzf_deflate.argtypes = [P, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        L.bwagpu_bgzf_out_limits.argtypes = [C.c_void_p]
+        L.bwagpu_bgzf_out_limits.restype = None
         L.bwagpu_fastq_batch_fasta.argtypes = L.bwagpu_fastq_batch.argtypes
         L.bwagpu_fastq_batch_fasta_bgzf.argtypes = L.bwagpu_fastq_batch_bgzf.argtypes
         L.bwagpu_fasta_reads_limits.argtypes = [C.c_void_p]
@@ -906,6 +917,29 @@ class FastqParser:
         self._chk(rc, "bwagpu_bgzf_inflate")
         d = info.as_dict()
         return (None if d["damaged_at"] >= 0 else dst[:d["inflated"]].tobytes()), d
+
+    def deflate_bgzf_rc(self, text, text_len, block_size, eof_marker, comp, info):
+        """the bare call (tests of the error paths): returns the library's code"""
+        return self.L.bwagpu_bgzf_deflate(self.h, text, text_len, block_size, eof_marker, comp, info)
+
+    def deflate_bgzf(self, text, block_size: int = 0, eof_marker: bool = True):
+        """text: bytes-like.  Returns (the text as a BGZF stream of blocks of block_size text bytes -- 0: 0xff00 --, with bgzip's end-of-file
+        block behind them if eof_marker; info dict with bwagpu_bgzf_out_info_t's fields).  The bytes depend on text and block_size alone."""
+        b = np.frombuffer(text, dtype=np.uint8) if len(text) else np.zeros(1, dtype=np.uint8)
+        comp = C.c_void_p()
+        info = BgzfOutInfo()
+        self._chk(self.L.bwagpu_bgzf_deflate(self.h, b.ctypes.data, len(text), int(block_size), int(bool(eof_marker)), C.byref(comp), C.byref(info)), "bwagpu_bgzf_deflate")
+        try:
+            data = C.string_at(comp.value, info.comp_len) if info.comp_len else b""
+        finally:
+            self.L.bwagpu_free(comp)
+        return data, info.as_dict()
+
+    def bgzf_out_limits(self) -> dict:
+        """what dev_bgzf_out.h's kernel uses: the largest block text, the shortest and longest match, the largest distance"""
+        v = (C.c_int32 * 4)()
+        self.L.bwagpu_bgzf_out_limits(v)
+        return {"max_block_text": v[0], "min_match": v[1], "max_match": v[2], "max_dist": v[3]}
 
     def batch_bgzf_rc(self, w1, w2, chunk_size, out, info):
         """the bare call (tests of the error paths): returns the library's code"""

@@ -24,7 +24,7 @@ def build(force: bool = False, verbose: bool = True) -> str:
     # two translation units (the index builder pulls in rocPRIM's sort templates and rarely changes): objects are rebuilt
     # only when one of their own sources is newer
     objs = []
-    index_srcs = [os.path.join(CSRC, f) for f in ("bwagpu_index.hip", "dev_fasta.h", "dev_fastq.h", "dev_fastq_smart.h", "dev_bgzf.h")] + [srcs[-1]]
+    index_srcs = [os.path.join(CSRC, f) for f in ("bwagpu_index.hip", "dev_fasta.h", "dev_fastq.h", "dev_fastq_smart.h", "dev_bgzf.h", "dev_bgzf_out.h")] + [srcs[-1]]
     for tu, deps in (("bwagpu.hip", [s for s in srcs if s not in index_srcs[:3]]), ("bwagpu_index.hip", index_srcs)):
         obj = os.path.join(CSRC, tu.replace(".hip", ".o"))
         if force or not os.path.exists(obj) or any(os.path.getmtime(obj) < os.path.getmtime(d) for d in deps):

@@ -44,6 +44,7 @@ typedef unsigned char u8;
 #include "dev_fasta_reads.h"      // FASTA read windows -> batches (bwagpu_fastq_batch_fasta*)
 #include "dev_fastq_smart.h"      // ... classified and split for `mem -p` (bwagpu_fastq_batch_smart*)
 #include "dev_bgzf.h"             // BGZF blocks -> text (bwagpu_bgzf_inflate, bwagpu_fastq_batch_bgzf)
+#include "dev_bgzf_out.h"         // text -> BGZF blocks (bwagpu_bgzf_deflate)
 
 namespace {
 
@@ -857,6 +858,7 @@ struct bwagpu_fastq_parser_s {
 	Buf o_seqs, o_off, o_names, o_name_off, o_quals, o_com, o_com_off, o_has, o_recs;
 	Buf d_eqv, d_runs, d_cls, d_sums, d_sscan, o_idx;      // bwagpu_fastq_batch_smart: dev_fastq_smart.h's arrays
 	Buf d_lflag[2], d_lines[2], d_lscan[2], d_hline[2], d_bend[2];      // bwagpu_fastq_batch_fasta: dev_fasta_reads.h's arrays
+	Buf d_otext, d_otok, d_oslot, d_osize, d_ooff, d_opack;      // bwagpu_bgzf_deflate: dev_bgzf_out.h's text, tokens, slots, sizes, offsets and packed blocks
 	std::string err;
 
 	~bwagpu_fastq_parser_s()
@@ -1234,6 +1236,62 @@ extern "C" int bwagpu_bgzf_inflate(bwagpu_fastq_parser_t *p, const void *comp, i
 	info->next_coff = P.used; info->next_uoff = 0;
 	if (info->damaged_at >= 0 || !P.inflated) return 0;
 	if (p->hip("download", hipMemcpyAsync(dst, p->d_buf[0].p, (size_t)P.inflated, hipMemcpyDeviceToHost, p->st)) || p->hip("sync", hipStreamSynchronize(p->st))) return BWAGPU_EHIP;
+	return 0;
+}
+
+// ---- text -> BGZF blocks (dev_bgzf_out.h) ---------------------------------------------------------------------------------------------
+// The host cuts the text into blocks and launches of BO_LAUNCH blocks; per launch the device compresses every block into its slot, scans
+// the sizes and packs the slots, and the host waits twice: for the packed length, then for the bytes.
+#define BO_LAUNCH 1024
+
+extern "C" void bwagpu_bgzf_out_limits(int32_t out[4])
+{
+	out[0] = (int32_t)BO_MAX_TEXT; out[1] = (int32_t)BO_MIN_MATCH; out[2] = (int32_t)BO_MAX_MATCH; out[3] = (int32_t)BO_MAX_DIST;
+}
+
+extern "C" int bwagpu_bgzf_deflate(bwagpu_fastq_parser_t *p, const void *text, int64_t text_len, int block_size, int eof_marker, void **comp, bwagpu_bgzf_out_info_t *info)
+{
+	static const u8 eof_block[28] = { 0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0 };
+	if (!p) return BWAGPU_EINVAL;
+	if (comp) *comp = nullptr;
+	if (!text || text_len < 0 || !comp || !info || block_size < 0 || block_size > (int)BO_MAX_TEXT)
+		return p->fail(BWAGPU_EINVAL, "bwagpu_bgzf_deflate: NULL argument, negative length or block_size outside 0..0xff00");
+	p->err.clear();
+	memset(info, 0, sizeof *info);
+	const u64 bs = block_size ? (u64)block_size : BO_MAX_TEXT, n = (u64)text_len, nb_all = (n + bs - 1) / bs;
+	const u64 cap = n + 31 * nb_all + sizeof eof_block;          // (no block is larger than its stored form)
+	u8 *dst = (u8*)bwagpu_alloc_host(cap);
+	if (!dst) return p->fail(BWAGPU_ENOMEM, "bwagpu_bgzf_deflate: no host memory for the blocks");
+	if (hipSetDevice(p->device) != hipSuccess) { bwagpu_free(dst); return p->fail(BWAGPU_ENODEV, "hipSetDevice failed"); }
+	u64 at = 0;
+	int rc = 0;
+	for (u64 b0 = 0; b0 < nb_all && !rc; b0 += BO_LAUNCH) {
+		const u64 nb = nb_all - b0 < BO_LAUNCH ? nb_all - b0 : BO_LAUNCH, t0 = b0 * bs, tn = n - t0 < nb * bs ? n - t0 : nb * bs;
+		if (p->d_otext.ensure(tn + 16) || p->d_otok.ensure(nb * BO_MAX_TEXT * 4) || p->d_oslot.ensure(nb * BO_SLOT) || p->d_osize.ensure(nb * 8 + 8) ||
+			p->d_ooff.ensure(nb * 8 + 8) || p->d_opack.ensure(tn + 31 * nb)) { rc = p->fail(BWAGPU_ENOMEM, "hipMalloc failed (BGZF output)"); break; }
+		BoArgs A; A.text = p->d_otext.as<u8>(); A.text_len = tn; A.block_size = (u32)bs; A.n_blocks = (u32)nb; A.tok = p->d_otok.as<u32>(); A.slot = p->d_oslot.as<u8>(); A.sizes = p->d_osize.as<u64>();
+		BoPack G; G.slot = A.slot; G.sizes = A.sizes; G.off = p->d_ooff.as<u64>(); G.dst = p->d_opack.as<u8>(); G.n_blocks = (u32)nb;
+		if (p->hip("copy text", hipMemcpyAsync(p->d_otext.p, (const u8*)text + t0, tn, hipMemcpyHostToDevice, p->st)) ||
+			p->hip("memset", hipMemsetAsync(p->d_oslot.p, 0, nb * BO_SLOT, p->st))) { rc = BWAGPU_EHIP; break; }
+		(void)hipEventRecord(p->ev[4], p->st);
+		hipLaunchKernelGGL(k_bo_deflate, dim3((unsigned)nb), dim3(BO_WAVE), 0, p->st, A);
+		(void)hipEventRecord(p->ev[5], p->st);
+		if ((rc = p->scan_excl(A.sizes, p->d_ooff.as<u64>(), nb))) break;
+		hipLaunchKernelGGL(k_bo_gather, dim3((unsigned)nb), dim3(256), 0, p->st, G);
+		u64 last[2] = { 0, 0 };
+		if (p->hip("read back the packed length", hipMemcpyAsync(&last[0], p->d_ooff.as<u64>() + nb - 1, 8, hipMemcpyDeviceToHost, p->st)) ||
+			p->hip("read back the packed length", hipMemcpyAsync(&last[1], A.sizes + nb - 1, 8, hipMemcpyDeviceToHost, p->st)) ||
+			p->hip("sync", hipStreamSynchronize(p->st)) || p->hip("BGZF output kernels", hipGetLastError())) { rc = BWAGPU_EHIP; break; }
+		const u64 packed = last[0] + last[1];
+		if (packed > tn + 31 * nb || at + packed + sizeof eof_block > cap) { rc = p->fail(BWAGPU_EHIP, "bwagpu_bgzf_deflate: the device reported blocks larger than their stored form"); break; }
+		if (p->hip("download", hipMemcpyAsync(dst + at, p->d_opack.p, packed, hipMemcpyDeviceToHost, p->st)) || p->hip("sync", hipStreamSynchronize(p->st))) { rc = BWAGPU_EHIP; break; }
+		float ms = 0; if (hipEventElapsedTime(&ms, p->ev[4], p->ev[5]) == hipSuccess) info->deflate_ms += ms;
+		at += packed;
+	}
+	if (rc) { bwagpu_free(dst); return rc; }
+	if (eof_marker) { memcpy(dst + at, eof_block, sizeof eof_block); at += sizeof eof_block; }
+	info->n_blocks = (int64_t)nb_all; info->text_len = text_len; info->comp_len = (int64_t)at;
+	*comp = dst;
 	return 0;
 }
 

@@ -414,6 +414,42 @@ static void encode_sub(const Batch &in, Sub &u)
 static std::mutex g_dev_mutex;
 static bool g_dev_serialize = false;   // BWAGPU_CLI_SERIALIZE=1: one device call at a time (the mock HIP runtime of the CPU tests is not thread-safe)
 
+// BWAGPU_CLI_BGZF_OUT=1: everything that goes to stdout (or -o) goes out as one BGZF stream compressed on the first device
+// (bwagpu_bgzf_deflate, dev_bgzf_out.h): the header lines, every batch's text in input order -- gathered into one page-locked buffer,
+// the one host copy this costs --, bgzip's end-of-file block at the end.  The same bytes go in that would have been written.
+struct BgzfOut {
+	bwagpu_fastq_parser_t *p = nullptr;
+	char *buf = nullptr; size_t cap = 0;          // the gather buffer (bwagpu_alloc_host), kept from batch to batch
+	long n_blocks = 0, n_text = 0, n_comp = 0; double ms = 0, gather_s = 0;
+	bool open(int device)
+	{
+		char eb[256];
+		const int rc = bwagpu_fastq_begin(&p, device, eb, sizeof eb);
+		if (rc != BWAGPU_OK) fprintf(stderr, "[E::%s] BWAGPU_CLI_BGZF_OUT: bwagpu_fastq_begin: %s %s\n", "main_mem", bwagpu_strerror(rc), eb);
+		return rc == BWAGPU_OK;
+	}
+	char *room(size_t n)
+	{
+		if (n > cap) { bwagpu_free(buf); cap = n + n / 4 + 4096; buf = (char*)bwagpu_alloc_host(cap); if (!buf) { fprintf(stderr, "[E::%s] BWAGPU_CLI_BGZF_OUT: out of memory\n", "main_mem"); fflush(stderr); fflush(stdout); _exit(EXIT_FAILURE); } }
+		return buf;
+	}
+	// n bytes of text (at buf or elsewhere) -> blocks on stdout; n == 0 with last: the end-of-file block alone
+	void write(const void *text, size_t n, bool last)
+	{
+		if (!n && !last) return;
+		void *comp = nullptr; bwagpu_bgzf_out_info_t info;
+		std::unique_lock<std::mutex> serial(g_dev_mutex, std::defer_lock);
+		if (g_dev_serialize) serial.lock();
+		const int rc = bwagpu_bgzf_deflate(p, text, (int64_t)n, 0, last ? 1 : 0, &comp, &info);
+		if (rc != BWAGPU_OK) { fprintf(stderr, "[E::%s] bwagpu_bgzf_deflate: %s: %s\n", "main_mem", bwagpu_strerror(rc), bwagpu_fastq_last_error(p)); fflush(stderr); fflush(stdout); _exit(EXIT_FAILURE); }
+		if (g_dev_serialize) serial.unlock();
+		fwrite(comp, 1, (size_t)info.comp_len, stdout);
+		bwagpu_free(comp);
+		n_blocks += (long)info.n_blocks; n_text += (long)n; n_comp += (long)info.comp_len; ms += info.deflate_ms;
+	}
+	void close() { bwagpu_free(buf); buf = nullptr; cap = 0; if (p) bwagpu_fastq_end(p); p = nullptr; }
+};
+
 // ---- BWAGPU_CLI_FASTQ: the input stage on the device ------------------------------------------------------------------------------
 // The plain input files are mapped; per batch a window of each goes to bwagpu_fastq_batch from the current offsets (about three bytes per base of the chunk plus slack,
 // doubled when the device answers MORE), and the offsets advance by what the batch consumed.  The batch's records come out of the record table: every field is copied
@@ -1296,14 +1332,19 @@ int main(int argc, char *argv[])
 		if (opt.flag & F_PE) { if (g_verbose >= 2) fprintf(stderr, "[W::%s] when '-p' is in use, the second query file is ignored.\n", "main_mem"); }
 		else { if (!r2.open(argv[optind + 2], parse_pool.get())) { fprintf(stderr, "[E::%s] fail to open file `%s'.\n", "main_mem", argv[optind + 2]); return 1; } pr2 = &r2; opt.flag |= F_PE; }
 	}
+	std::unique_ptr<BgzfOut> bgzf_out;
+	if (env_int("BWAGPU_CLI_BGZF_OUT", 0) && !getenv("BWAGPU_CLI_PARSE_ONLY")) { bgzf_out.reset(new BgzfOut()); if (!bgzf_out->open(device)) return 1; }
 	// SAM header (bwa_print_sam_hdr, bwa.c:407-439)
 	{
 		bool has_hd = hdr_line.rfind("@HD\t", 0) == 0 || hdr_line.find("\n@HD\t") != std::string::npos;
 		bool has_sq = hdr_line.rfind("@SQ\t", 0) == 0 || hdr_line.find("\n@SQ\t") != std::string::npos;
-		if (!has_hd) fputs("@HD\tVN:1.5\tSO:unsorted\tGO:query\n", stdout);
-		if (!has_sq) for (auto &ctg : ref.ctg) { printf("@SQ\tSN:%s\tLN:%d", ctg.name.c_str(), ctg.len); fputs(ctg.is_alt ? "\tAH:*\n" : "\n", stdout); }
-		if (!hdr_line.empty()) printf("%s\n", hdr_line.c_str());
-		printf("%s\n", pg.c_str());
+		std::string hd;
+		if (!has_hd) hd += "@HD\tVN:1.5\tSO:unsorted\tGO:query\n";
+		if (!has_sq) for (auto &ctg : ref.ctg) { hd += "@SQ\tSN:" + ctg.name + "\tLN:" + std::to_string(ctg.len); hd += ctg.is_alt ? "\tAH:*\n" : "\n"; }
+		if (!hdr_line.empty()) hd += hdr_line + "\n";
+		hd += pg + "\n";
+		if (bgzf_out) bgzf_out->write(hd.data(), hd.size(), false);
+		else fwrite(hd.data(), 1, hd.size(), stdout);
 	}
 	const int chunk = fixed_chunk > 0 ? fixed_chunk : opt.chunk_size * opt.n_threads;
 	const bool long_preset = mode && (strcmp(mode, "pacbio") == 0 || strcmp(mode, "pbref") == 0 || strcmp(mode, "ont2d") == 0);
@@ -1540,7 +1581,16 @@ int main(int argc, char *argv[])
 		if (getenv("BWAGPU_CLI_OUT_FROM_BATCH") && atol(getenv("BWAGPU_CLI_OUT_FROM_BATCH")) > 0 && g_verbose >= 2)
 			fprintf(stderr, "[W::%s] BWAGPU_CLI_OUT_FROM_BATCH=%s: the records of the batches before that one are NOT written\n", "main_mem", getenv("BWAGPU_CLI_OUT_FROM_BATCH"));
 		const long out_from = getenv("BWAGPU_CLI_OUT_FROM_BATCH") ? atol(getenv("BWAGPU_CLI_OUT_FROM_BATCH")) : 0;      // (bench.py's tail check: only the records of batches out_from.. are written)
-		while (to_out.pop(w)) { const double tw = now_s(); if (w->no >= out_from) for (auto &t : w->out) fwrite(t.data(), 1, w->by_read ? strnlen(t.data(), t.size()) : t.size(), stdout);
+		while (to_out.pop(w)) { const double tw = now_s();
+			if (w->no >= out_from && bgzf_out) {
+				size_t n = 0, at = 0;
+				for (auto &t : w->out) n += w->by_read ? strnlen(t.data(), t.size()) : t.size();
+				char *b = bgzf_out->room(n);
+				for (auto &t : w->out) { const size_t k = w->by_read ? strnlen(t.data(), t.size()) : t.size(); memcpy(b + at, t.data(), k); at += k; }
+				bgzf_out->gather_s += now_s() - tw;
+				bgzf_out->write(b, n, false);
+			} else
+			if (w->no >= out_from) for (auto &t : w->out) fwrite(t.data(), 1, w->by_read ? strnlen(t.data(), t.size()) : t.size(), stdout);
 			if (!w->by_read) { std::lock_guard<std::mutex> l(pool_m); if (out_pool.size() < 4) out_pool.push_back(std::move(w->out)); } /* (the reference fputs() a read's records, fastmap.c:116: a NUL -- the letter of base code 5, a '-' in the input -- ends them) */ busy_write += now_s() - tw; }
 		cpu_write = thread_cpu_s();
 	});
@@ -1574,6 +1624,12 @@ int main(int argc, char *argv[])
 	to_out.close();
 	writer.join();
 	all_done = true; watchdog.join();
+	if (bgzf_out) {
+		bgzf_out->write("", 0, true);
+		if (tl_trace) fprintf(stderr, "[D::output] %ld blocks, %ld text bytes, %ld compressed bytes, %.3f ms on the device\n", bgzf_out->n_blocks, bgzf_out->n_text, bgzf_out->n_comp, bgzf_out->ms);
+		if (tl_trace) fprintf(stderr, "[D::output] gathering the batches' text into the upload buffer took %.3f ms\n", bgzf_out->gather_s * 1e3);
+		bgzf_out->close();
+	}
 	if (dev_in && tl_trace) fprintf(stderr, "[D::input] %ld batches (%ld reads) parsed on the device, %ld by the host reader\n", dev_in->n_dev_batches, dev_in->n_dev_reads, dev_in->n_host_batches);
 	if (dev_in && dev_in->bgzf && tl_trace) fprintf(stderr, "[D::input] %ld BGZF blocks inflated on the device\n", dev_in->n_bgzf_blocks);
 	if (g_device_rescue && tl_trace && hostmem::g_pairs_merged_on_device.load() > 0)

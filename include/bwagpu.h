@@ -724,6 +724,18 @@ int  bwagpu_bgzf_inflate(bwagpu_fastq_parser_t *p, const void *comp, int64_t com
 int  bwagpu_fastq_batch_bgzf(bwagpu_fastq_parser_t *p, const bwagpu_bgzf_win_t *w1, const bwagpu_bgzf_win_t *w2 /* NULL: one file */,
                              int chunk_size, bwagpu_fastq_out_t *out, bwagpu_bgzf_info_t info[2]);
 
+/* bwagpu_bgzf_deflate: the other direction -- text (host memory) compressed into a BGZF stream (SAM specification 4.1) that bgzip -d,
+ * samtools, htslib and bwagpu_bgzf_inflate read.  The text is cut into blocks of block_size bytes (1..0xff00; 0: 0xff00, bgzip's), each
+ * compressed on its own by one wavefront (dev_bgzf_out.h: hash-based match search, greedy parse, length-limited canonical codes; the
+ * smallest of dynamic, fixed and stored per block) and never larger than its text + 31 bytes.  The compressed bytes depend on the text
+ * and block_size alone.  eof_marker: bgzip's 28-byte end-of-file block behind the last block (text_len == 0: that block alone, or
+ * nothing).  *comp: info->comp_len bytes, free with bwagpu_free; text of 2^31 bytes or more takes several launches.  BWAGPU_EINVAL:
+ * NULL p / text / comp / info, text_len < 0, block_size outside 0..0xff00. */
+typedef struct { int64_t n_blocks, text_len, comp_len; float deflate_ms; } bwagpu_bgzf_out_info_t;
+int  bwagpu_bgzf_deflate(bwagpu_fastq_parser_t *p, const void *text, int64_t text_len, int block_size /* 1..0xff00, 0: 0xff00 */,
+                         int eof_marker, void **comp /* bwagpu_free */, bwagpu_bgzf_out_info_t *info);
+void bwagpu_bgzf_out_limits(int32_t out[4]);   /* largest block text, min match, max match, max distance the kernel uses */
+
 /* ---- interleaved input: `mem -p' ("smart pairing"), on the same parser ------------------------------------------------------------ */
 /* ---- FASTA read files on the same parser (the FASTA half of kseq_read, kseq.h:175-204) ---------------------------------------- */
 /* bwagpu_fastq_batch_fasta: bwagpu_fastq_batch for windows of FASTA text -- the same arguments, BWAGPU_EINVAL cases, statuses,
